@@ -21,6 +21,13 @@ Scaling (--gpus N > 1): default = WEAK (every rank owns the workload's envs and 
 16384 x N) - and the same line carries a `strong` record: cfg3 measured by the same process group right behind the weak
 timed region (value, per-rank times, wire time, RCCL world, rank 0's roofline fraction; --no-strong skips it).  --workload cfg3 is BASELINE configs[2] as written - 16384 envs and a 16384-sample minibatch GLOBAL, sharded
 over the ranks - i.e. STRONG scaling of a fixed job.
+
+A plain run sets up, warms up, times the K steps and prints the line (headline value, ms_per_step, phase device times).
+Everything measured beyond that headline takes --full: the same K iterations without the read-back, the roofline of the
+minibatch group, GAE at config size and on the HBM sweep, the split-bf16 `secondary` record, `cpu_baseline`, and with
+--gpus N > 1 the serialised wire time (`comm`) and the `strong` record.
+--dump-outputs DIR writes what the timed path computed in its LAST timed step as DIR/<name>.npy (float32 / float64; see
+dump_outputs), right after the timed region and before any --full measurement touches the trainer again.
 """
 from __future__ import annotations
 
@@ -404,6 +411,46 @@ def secondary_record(a, w, dev_index, steps, warmup):
                          "frac_profiled": None if not prof_us else 3.0 * flops / prof_us / 1e6 / MFMA_BF16_PEAK_TFLOPS}}
 
 
+DUMP_BUDGET_BYTES = 60 << 20         # --dump-outputs: under 64 MB in all, .npy headers included
+DUMP_SAMPLE_SEED = 20240601
+
+
+def dump_outputs(trainer, stats, out_dir):
+    """What a caller of the timed path holds after its last step (rank 0's shard): the diagnostics run_iteration returned
+    (stat_<key>, float64 scalars), the flat parameters and Adam moments, both running normalisers, and the rollout
+    buffers the update consumed (time-major [T(+1), N, ...] planes, float32; fp16 planes widened, observation padding
+    dropped).  Over DUMP_BUDGET_BYTES the env axis of the rollout buffers is cut to a fixed sample of envs drawn with
+    DUMP_SAMPLE_SEED, and rollout_env_index holds the envs kept.  Returns {name: shape}."""
+    a, T, N, D = trainer.agent, trainer.T, trainer.N, trainer.D
+    whole = {"params": a.flat, "adam_exp_avg": trainer.exp_avg, "adam_exp_avg_sq": trainer.exp_avg_sq,
+             "obs_rms_mean": a.obs_rms.running_mean, "obs_rms_var": a.obs_rms.running_var,
+             "obs_rms_count": a.obs_rms.count, "value_rms_mean": a.value_rms.running_mean,
+             "value_rms_var": a.value_rms.running_var, "value_rms_count": a.value_rms.count}
+    per_env = {"rollout_obs": trainer.obs[:, :, :D], "rollout_actions": trainer.actions,
+               "rollout_logprobs": trainer.logprobs, "rollout_rewards": trainer.rewards, "rollout_values": trainer.values,
+               "rollout_dones": trainer.dones, "rollout_true_dones": trainer.true_dones,
+               "advantages": trainer.advantages, "returns": trainer.returns, "values_normalised": trainer.values_n,
+               "returns_normalised": trainer.returns_n, "next_value": trainer.next_value[None]}
+    fixed = 4 * sum(t.numel() for t in whole.values()) + 8 * len(stats or {}) + 256 * (len(whole) + len(per_env) + 9)
+    per_env_bytes = 4 * sum(t.numel() // N for t in per_env.values()) + 8       # (+ its entry in rollout_env_index)
+    keep = max(1, min(N, (DUMP_BUDGET_BYTES - fixed) // per_env_bytes))
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in whole.items()}
+    if keep < N:
+        idx = np.sort(np.random.RandomState(DUMP_SAMPLE_SEED).choice(N, keep, replace=False))
+        sel = torch.from_numpy(idx).to(trainer.device)
+        arrays.update({k: v.detach().index_select(1, sel).float().cpu().numpy() for k, v in per_env.items()})
+        arrays["rollout_env_index"] = idx.astype(np.float64)
+    else:
+        arrays.update({k: v.detach().float().cpu().numpy() for k, v in per_env.items()})
+    arrays["next_value"] = arrays["next_value"][0]
+    for k, v in (stats or {}).items():
+        arrays["stat_" + k] = np.asarray(v, dtype=np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(v))
+    return {k: list(v.shape) for k, v in arrays.items()}
+
+
 def self_launch(n_ranks: int) -> int:
     """`python bench.py --gpus N` with no launcher around it (WORLD_SIZE unset): start the N ranks of this node here -
     the same command line under torch.distributed.run, one process per rank, rendezvous on 127.0.0.1 (the container
@@ -472,9 +519,16 @@ def main():
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--print-launch", action="store_true",
                     help="print the torch.distributed.run command a bare `--gpus N` would start, and exit")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: iterations without the read-back, roofline, GAE, "
+                         "the secondary record, cpu_baseline, and with --gpus N > 1 the wire time and the strong record")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path computed in its last timed step as DIR/<name>.npy (rank 0)")
     a = ap.parse_args()
     if a.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.workload is None:
         a.workload = "cfg3" if a.scaling == "strong" else "cfg2"
     if a.scaling is not None and (a.scaling == "strong") != bool(WORKLOADS[a.workload].get("strong")):
@@ -538,6 +592,9 @@ def main():
     # stdout carries ONE line (the JSON record): what building the env prints (the reference's "[INFO] Constraint
     # Manager" table) goes to stderr
     import contextlib
+    # the agent's initial weights are drawn from torch's global generator, whose start state is not fixed across processes:
+    # seeded, the same arguments give the same inputs in every run (--dump-outputs compares runs array by array)
+    torch.manual_seed(a.seed)
     with contextlib.redirect_stdout(sys.stderr):
         env, trainer, agent_cfg = build(a.workload, a.seed + rank, dev_index, a.mlp_precision, shard_world, rank, overrides)
     nat = trainer.nat
@@ -564,7 +621,7 @@ def main():
         orig(*args, **kw)
         e1.record()
         ev.append((e0, e1))
-    if not trainer.graph_update:
+    if a.full and not trainer.graph_update:
         nat.ppo_minibatch_grad_packed = timed_grad
     trainer.time_phases = True
     barrier()
@@ -572,7 +629,7 @@ def main():
     # (CATPPO_BENCH_TIMED_LOG=0: A/B of what the read-back costs - never the reported configuration)
     timed_log = os.environ.get("CATPPO_BENCH_TIMED_LOG", "1") != "0"
     for _ in range(a.steps):
-        trainer.run_iteration(log=timed_log)      # log=True: the per-iteration diagnostics read-back is inside the metric
+        stats = trainer.run_iteration(log=timed_log)   # log=True: the per-iteration diagnostics read-back is inside the metric
     barrier()
     dt = time.perf_counter() - t0
     nat.ppo_minibatch_grad_packed = orig
@@ -591,13 +648,19 @@ def main():
     steps_total = env_total * w["num_steps"] * a.steps
     value = steps_total / dt
 
-    # the same K iterations without the read-back (host free to run ahead), for comparison only
-    barrier()
-    t1 = time.perf_counter()
-    for _ in range(a.steps):
-        trainer.run_iteration(log=False)
-    barrier()
-    dt_nolog = time.perf_counter() - t1
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        dumped = dump_outputs(trainer, stats, a.dump_outputs)
+
+    dt_nolog = None
+    if a.full:
+        # the same K iterations without the read-back (host free to run ahead), for comparison only
+        barrier()
+        t1 = time.perf_counter()
+        for _ in range(a.steps):
+            trainer.run_iteration(log=False)
+        barrier()
+        dt_nolog = time.perf_counter() - t1
 
     # device time inside the exchange points of one iteration (all-gather of the env-step record, normaliser / advantage
     # moments, gradient all-reduce, diagnostics): HIP events around every collective cat_envs.parallel issues, on the
@@ -605,7 +668,7 @@ def main():
     # library beside the backward launches, cannot be bracketed from here: this pass runs the same iteration with both
     # switched off, i.e. it reports the SERIALISED wire time (what overlap can at most hide), outside the timed region.
     comm = None
-    if parallel.active():
+    if a.full and parallel.active():
         g_was, ov_was = trainer.graph_update, trainer.grad_overlap
         trainer.graph_update = False
         if ov_was:
@@ -624,40 +687,16 @@ def main():
             trainer.grad_overlap = nat.set_grad_overlap(getattr(trainer, '_grad_overlap_mode', True))
 
     strong = None
-    if world > 1 and not w.get("strong") and not a.no_strong:
+    if a.full and world > 1 and not w.get("strong") and not a.no_strong:
         strong = strong_record(a, world, rank, dev_index, shared, max(2, a.steps // 2), max(1, a.warmup // 2))
 
     if rank == 0:
         M = trainer.M
-        if trainer.graph_update or not ev:         # eager replay of the group on the data of the last iteration
-            # (also when the eager trainer took the one-call optimiser step, which the wrapper above does not see)
-            # rank 0 is alone here: with gradient buckets on, the gradient call itself would all-reduce - and wait for
-            # peers that are already at the final barrier
-            ov_replay = bool(trainer.grad_overlap)
-            if ov_replay:
-                nat.set_grad_overlap(False)
-            grad_us, n_timed = time_group_eager(trainer)
-            if ov_replay:
-                nat.set_grad_overlap(getattr(trainer, '_grad_overlap_mode', True))
-        else:
-            grad_us, n_timed = float(np.mean([e0.elapsed_time(e1) for e0, e1 in ev])) * 1e3, len(ev)
         macs = fwd_macs(w["obs_dim"], w["hidden"])
         flops_per_launch = 3 * 2 * macs * M                       # fwd + bwd = 3x fwd, per minibatch
-        ach = flops_per_launch / grad_us / 1e6
         prec = agent_cfg.mlp_precision
-        bf16 = prec != "fp32"
-        peak = MFMA_BF16_PEAK_TFLOPS if bf16 else MFMA_F32_PEAK_TFLOPS
-        # bf16x3 issues three bf16 MFMAs per algorithmic product: the matrix pipe executes 3x the algorithmic FLOPs
-        mfma_flops_factor = 3.0 if prec == "bf16x3" else 1.0
-        # PMC / trace summaries of a non-default precision carry it in their name: r5_pmc_traffic_cfg2_bf16x3.json
-        wl_key = a.workload if prec == w.get("mlp_precision", "fp32") else f"{a.workload}_{prec}"
-        traffic, traffic_src, traffic_note = pmc_traffic(wl_key, a.profile_tag)
-        if traffic_note:
-            print(f"[bench] roofline.traffic = null: {traffic_note}", file=sys.stderr)
-        prof_us, prof_src = profiled_group_us(wl_key, a.profile_tag)
         n_mb_steps = int(agent_cfg.updates_epochs) * trainer.n_mb
         it_flops = (w["num_steps"] * trainer.N * 2 * macs) + n_mb_steps * flops_per_launch     # rollout fwd + update
-        from cat_envs import native
         out = {
             "metric": "env-steps/s CaT-PPO iteration (rollout + GAE + PPO update)", "value": value,
             "unit": "env-steps/s", "n_gpus": world, "physical_gpus": min(world, n_dev), "ranks_share_gpus": shared,
@@ -696,73 +735,15 @@ def main():
                        "simulated_shard_of_world": a.shard_of if a.shard_of > 0 else None,
                        "rng": trainer.rng, "fused_rollout": trainer.sink is not None,
                        "graph_update": trainer.graph_update, "graph_nodes": trainer.graph_nodes,
-                       "overrides": overrides},
+                       "overrides": overrides, "full": a.full},
             "per_rank_ms": per_rank_ms,
-            "ms_per_step_no_readback": 1e3 * dt_nolog / a.steps,
-            "comm_ms_per_iteration": None if comm is None else comm["ms"] / comm["iterations"],
-            "comm": None if comm is None else {
-                "collectives_per_iteration": comm["calls"] / comm["iterations"],
-                "bytes_per_iteration": comm["bytes"] / comm["iterations"],
-                "ms_by_kind_per_iteration": {k: v[0] / comm["iterations"] for k, v in comm["by_kind"].items()},
-                "calls_by_kind_per_iteration": {k: v[1] / comm["iterations"] for k, v in comm["by_kind"].items()},
-                "measured": "HIP events around every exchange point of an un-graphed, un-overlapped iteration after the "
-                            "timed region (serialised wire time)"},
             "phases_device_ms": phases,
             "iteration_tflops": it_flops / (1e9 * dt / a.steps) / 1e3,
-            "roofline": {"bound": "mfma", "kernel": "catppo_ppo_minibatch_grad_packed (row-resident fp32-MFMA forward of the hidden layers "
-                         "below the last - or grouped forward GEMM launches - then the last layer with heads + loss + head backward "
-                         "in its epilogue from 4096 rows up, else a head+loss launch; paired split-K dW + dX GEMM launches, "
-                         "partial fold) per " + str(M) + "-sample minibatch",
-                         "achieved": ach * mfma_flops_factor, "peak": peak, "unit": "TFLOP/s",
-                         "frac": ach * mfma_flops_factor / peak, "algorithmic_tflops": ach,
-                         # what the matrix pipe executes per launch (padded observations, no first-layer data gradient,
-                         # 16-output head tiles), x 3 MFMAs per product in the split-bf16 mode
-                         "executed_flops": 2 * executed_macs(trainer.Dp, w["hidden"]) * M * mfma_flops_factor,
-                         "executed_over_algorithmic_flops": 2 * executed_macs(trainer.Dp, w["hidden"]) * M * mfma_flops_factor
-                                                            / flops_per_launch,
-                         "traffic": traffic, "avg_launch_us": grad_us, "launches_timed": n_timed,
-                         "dominant_kernel_us_profiled": prof_us, "profiled_source": prof_src,
-                         # the same FLOPs over the COMMITTED rocprofv3 duration of the group (profiler on, another box)
-                         "frac_profiled": None if not prof_us else
-                                          flops_per_launch / prof_us / 1e6 * mfma_flops_factor / peak,
-                         "timed": "eager replay after the timed region (update phase runs from a hipGraph)"
-                                  if trainer.graph_update else "HIP events inside the timed region",
-                         "flops_per_launch": flops_per_launch,
-                         "traffic_source": traffic_src, "traffic_note": traffic_note, "csrc_hash": csrc_hash()},
-            "gae": {"config_size": gae_roofline(nat, w["num_steps"], trainer.N),
-                    "config_size_scan": gae_roofline(nat, w["num_steps"], trainer.N, mode=native.GAE_SCAN),
-                    "hbm_sweep": [gae_roofline(nat, 24, 1 << 20, 20), gae_roofline(nat, 48, 1 << 22, 10)],
-                    "bound": "hbm", "peak_GBps": HBM_PEAK_GBPS, "bytes_per_env_step": 24},
         }
-        # (--no-cpu-baseline = the diagnostic form the A/B and profiling scripts use: no secondary record either, so that a
-        # kernel trace of that command holds the kernels of ONE precision)
-        if prec == "bf16":
-            # BASELINE configs[4] (bf16 MFMA operands): the matrix work shrinks 16x while every activation still crosses HBM
-            # in fp32 - the group is HBM-bound, and its roofline object says so.  Algorithmic bytes of one
-            # minibatch group = a layer-wise step that moves every tensor once each way: the gathered
-            # inputs, every hidden activation written and read back, every dZ above the first layer written and read back.
-            hid = list(w["hidden"])
-            # round 6: hidden activations and dZ are STORED as bf16 from 4096-row minibatches up (csrc/gemm_f32.h "act16")
-            el = 2 if (M >= 4096 and os.environ.get("CATPPO_ACT16", "1") != "0") else 4
-            act_b = M * sum(hid) * el * 2
-            dz_b = M * sum(hid[1:]) * el * 2
-            alg_bytes = 2 * act_b + 2 * dz_b + M * (trainer.Dp + trainer.A + 4) * 4
-            mf = out["roofline"]
-            out["roofline"] = {"bound": "hbm", "kernel": mf["kernel"], "achieved": alg_bytes / grad_us / 1e3, "peak": HBM_PEAK_GBPS,
-                               "unit": "GB/s", "frac": alg_bytes / grad_us / 1e3 / HBM_PEAK_GBPS, "algorithmic_bytes": alg_bytes,
-                               "activation_element_bytes": el,
-                               "traffic": traffic, "traffic_GBps": None if not traffic else traffic / grad_us / 1e3,
-                               "hbm_frac": None if not traffic else traffic / grad_us / 1e3 / HBM_PEAK_GBPS,
-                               "avg_launch_us": grad_us, "launches_timed": n_timed, "timed": mf["timed"],
-                               "traffic_source": traffic_src, "traffic_note": traffic_note, "csrc_hash": mf["csrc_hash"],
-                               "mfma": {k: mf[k] for k in ("achieved", "peak", "unit", "frac", "algorithmic_tflops", "executed_flops",
-                                                          "flops_per_launch", "dominant_kernel_us_profiled", "frac_profiled")}}
-        if world == 1 and prec == "fp32" and not a.no_secondary and not a.no_cpu_baseline and a.shard_of == 0:
-            out["secondary"] = secondary_record(a, w, dev_index, max(3, a.steps // 2), max(2, a.warmup // 2))
-        if world == 1 and not a.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(a.workload, trainer, env, agent_cfg)
-        if strong is not None:
-            out["strong"] = strong
+        if dumped is not None:
+            out["outputs"] = {"dir": os.path.abspath(a.dump_outputs), "arrays": dumped}
+        if a.full:
+            out.update(full_record(a, w, world, trainer, agent_cfg, env, dev_index, ev, dt_nolog, comm, strong))
     else:
         out = None
     if torch.distributed.is_initialized():
@@ -780,6 +761,103 @@ def main():
         assert out["n_gpus"] == a.gpus
         print(json.dumps(out), flush=True)
     return 0
+
+
+def full_record(a, w, world, trainer, agent_cfg, env, dev_index, ev, dt_nolog, comm, strong):
+    """--full, rank 0: what the line carries beyond the headline - measured after the timed region (and after the dump)"""
+    from cat_envs import native
+    nat, M = trainer.nat, trainer.M
+    if trainer.graph_update or not ev:         # eager replay of the group on the data of the last iteration
+        # (also when the eager trainer took the one-call optimiser step, which the wrapper above does not see)
+        # rank 0 is alone here: with gradient buckets on, the gradient call itself would all-reduce - and wait for
+        # peers that are already at the final barrier
+        ov_replay = bool(trainer.grad_overlap)
+        if ov_replay:
+            nat.set_grad_overlap(False)
+        grad_us, n_timed = time_group_eager(trainer)
+        if ov_replay:
+            nat.set_grad_overlap(getattr(trainer, '_grad_overlap_mode', True))
+    else:
+        grad_us, n_timed = float(np.mean([e0.elapsed_time(e1) for e0, e1 in ev])) * 1e3, len(ev)
+    macs = fwd_macs(w["obs_dim"], w["hidden"])
+    flops_per_launch = 3 * 2 * macs * M                       # fwd + bwd = 3x fwd (SURVEY 8d), per minibatch
+    ach = flops_per_launch / grad_us / 1e6
+    prec = agent_cfg.mlp_precision
+    bf16 = prec != "fp32"
+    peak = MFMA_BF16_PEAK_TFLOPS if bf16 else MFMA_F32_PEAK_TFLOPS
+    # bf16x3 issues three bf16 MFMAs per algorithmic product: the matrix pipe executes 3x the algorithmic FLOPs
+    mfma_flops_factor = 3.0 if prec == "bf16x3" else 1.0
+    # PMC / trace summaries of a non-default precision carry it in their name: r5_pmc_traffic_cfg2_bf16x3.json
+    wl_key = a.workload if prec == w.get("mlp_precision", "fp32") else f"{a.workload}_{prec}"
+    traffic, traffic_src, traffic_note = pmc_traffic(wl_key, a.profile_tag)
+    if traffic_note:
+        print(f"[bench] roofline.traffic = null: {traffic_note}", file=sys.stderr)
+    prof_us, prof_src = profiled_group_us(wl_key, a.profile_tag)
+    out = {
+        "ms_per_step_no_readback": 1e3 * dt_nolog / a.steps,
+        "comm_ms_per_iteration": None if comm is None else comm["ms"] / comm["iterations"],
+        "comm": None if comm is None else {
+            "collectives_per_iteration": comm["calls"] / comm["iterations"],
+            "bytes_per_iteration": comm["bytes"] / comm["iterations"],
+            "ms_by_kind_per_iteration": {k: v[0] / comm["iterations"] for k, v in comm["by_kind"].items()},
+            "calls_by_kind_per_iteration": {k: v[1] / comm["iterations"] for k, v in comm["by_kind"].items()},
+            "measured": "HIP events around every exchange point of an un-graphed, un-overlapped iteration after the "
+                        "timed region (serialised wire time)"},
+        "roofline": {"bound": "mfma", "kernel": "catppo_ppo_minibatch_grad_packed (row-resident fp32-MFMA forward of the hidden layers "
+                     "below the last - or grouped forward GEMM launches - then the last layer with heads + loss + head backward "
+                     "in its epilogue from 4096 rows up, else a head+loss launch; paired split-K dW + dX GEMM launches, "
+                     "partial fold) per " + str(M) + "-sample minibatch",
+                     "achieved": ach * mfma_flops_factor, "peak": peak, "unit": "TFLOP/s",
+                     "frac": ach * mfma_flops_factor / peak, "algorithmic_tflops": ach,
+                     # what the matrix pipe executes per launch (padded observations, no first-layer data gradient,
+                     # 16-output head tiles), x 3 MFMAs per product in the split-bf16 mode
+                     "executed_flops": 2 * executed_macs(trainer.Dp, w["hidden"]) * M * mfma_flops_factor,
+                     "executed_over_algorithmic_flops": 2 * executed_macs(trainer.Dp, w["hidden"]) * M * mfma_flops_factor
+                                                        / flops_per_launch,
+                     "traffic": traffic, "avg_launch_us": grad_us, "launches_timed": n_timed,
+                     "dominant_kernel_us_profiled": prof_us, "profiled_source": prof_src,
+                     # the same FLOPs over the COMMITTED rocprofv3 duration of the group (profiler on, another box)
+                     "frac_profiled": None if not prof_us else
+                                      flops_per_launch / prof_us / 1e6 * mfma_flops_factor / peak,
+                     "timed": "eager replay after the timed region (update phase runs from a hipGraph)"
+                              if trainer.graph_update else "HIP events inside the timed region",
+                     "flops_per_launch": flops_per_launch,
+                     "traffic_source": traffic_src, "traffic_note": traffic_note, "csrc_hash": csrc_hash()},
+        "gae": {"config_size": gae_roofline(nat, w["num_steps"], trainer.N),
+                "config_size_scan": gae_roofline(nat, w["num_steps"], trainer.N, mode=native.GAE_SCAN),
+                "hbm_sweep": [gae_roofline(nat, 24, 1 << 20, 20), gae_roofline(nat, 48, 1 << 22, 10)],
+                "bound": "hbm", "peak_GBps": HBM_PEAK_GBPS, "bytes_per_env_step": 24},
+    }
+    # (--no-cpu-baseline = the diagnostic form the A/B and profiling scripts use: no secondary record either, so that a
+    # kernel trace of that command holds the kernels of ONE precision)
+    if prec == "bf16":
+        # BASELINE configs[4] (bf16 MFMA operands): the matrix work shrinks 16x while every activation still crosses HBM
+        # in fp32 - the group is HBM-bound (VERDICT r5 item 6), and its roofline object says so.  Algorithmic bytes of one
+        # minibatch group = a layer-wise step that moves every tensor once each way (DESIGN section 5): the gathered
+        # inputs, every hidden activation written and read back, every dZ above the first layer written and read back.
+        hid = list(w["hidden"])
+        # round 6: hidden activations and dZ are STORED as bf16 from 4096-row minibatches up (csrc/gemm_f32.h "act16")
+        el = 2 if (M >= 4096 and os.environ.get("CATPPO_ACT16", "1") != "0") else 4
+        act_b = M * sum(hid) * el * 2
+        dz_b = M * sum(hid[1:]) * el * 2
+        alg_bytes = 2 * act_b + 2 * dz_b + M * (trainer.Dp + trainer.A + 4) * 4
+        mf = out["roofline"]
+        out["roofline"] = {"bound": "hbm", "kernel": mf["kernel"], "achieved": alg_bytes / grad_us / 1e3, "peak": HBM_PEAK_GBPS,
+                           "unit": "GB/s", "frac": alg_bytes / grad_us / 1e3 / HBM_PEAK_GBPS, "algorithmic_bytes": alg_bytes,
+                           "activation_element_bytes": el,
+                           "traffic": traffic, "traffic_GBps": None if not traffic else traffic / grad_us / 1e3,
+                           "hbm_frac": None if not traffic else traffic / grad_us / 1e3 / HBM_PEAK_GBPS,
+                           "avg_launch_us": grad_us, "launches_timed": n_timed, "timed": mf["timed"],
+                           "traffic_source": traffic_src, "traffic_note": traffic_note, "csrc_hash": mf["csrc_hash"],
+                           "mfma": {k: mf[k] for k in ("achieved", "peak", "unit", "frac", "algorithmic_tflops", "executed_flops",
+                                                      "flops_per_launch", "dominant_kernel_us_profiled", "frac_profiled")}}
+    if world == 1 and prec == "fp32" and not a.no_secondary and not a.no_cpu_baseline and a.shard_of == 0:
+        out["secondary"] = secondary_record(a, w, dev_index, max(3, a.steps // 2), max(2, a.warmup // 2))
+    if world == 1 and not a.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline(a.workload, trainer, env, agent_cfg)
+    if strong is not None:
+        out["strong"] = strong
+    return out
 
 
 if __name__ == "__main__":

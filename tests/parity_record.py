@@ -1,12 +1,13 @@
-"""Achieved parity errors of the config-size GPU tests, written to profiles/r6_parity.json (round 4: r4_parity.json) (the
-whole-iteration tests printed their errors and threw them away).  One entry per test name: max abs errors per tensor,
-sizes, seed.  The file is merged, not overwritten, so one pytest run (or several gpurun calls) accumulate into it; on
-the GPU box it is written under gpurun_out/ as well so that it travels back."""
+"""Achieved parity errors of the config-size GPU tests (the whole-iteration tests printed their errors and
+threw them away).  One entry per test name: max abs errors per tensor, sizes, seed.  The file is merged, not overwritten,
+so one pytest run (or several) accumulate into it.  By default it is parity_out/parity.json at the repository root
+(git-ignored: a test run leaves the tree clean); CATPPO_PARITY_RECORD=<path> writes elsewhere, e.g. the committed
+profiles/r6_parity.json when a round's record is refreshed on purpose."""
 import json
 import os
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PATHS = [os.path.join(ROOT, "profiles", "r6_parity.json"), os.path.join(ROOT, "gpurun_out", "r6_parity.json")]
+PATHS = [os.path.abspath(os.environ.get("CATPPO_PARITY_RECORD") or os.path.join(ROOT, "parity_out", "parity.json"))]
 
 
 def record(name, errors, sizes=None, seed=None, note=None):

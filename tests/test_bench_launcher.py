@@ -55,7 +55,7 @@ def test_bench_gpus_2_starts_two_ranks_itself(tmp_path):
     """the launcher proven on whatever box this runs on: with fewer than two GPUs the two ranks share cuda:0 and exchange
     through gloo with host staging (the transport of test_gpu_two_rank_trainer.py); with two or more they use RCCL"""
     import torch
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full"],
                        capture_output=True, text=True, env=_env(), timeout=1500, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
@@ -88,3 +88,39 @@ def test_bench_gpus_2_starts_two_ranks_itself(tmp_path):
     assert len(st["per_rank_ms"]["by_rank"]) == 2 and st["comm_ms_per_iteration"] > 0
     assert st["collectives_per_iteration"] >= 24 + 5 * 24 and 0 < st["roofline"]["frac"] < 1
     assert st["rccl_world"] == d["config"]["rccl_world"]
+
+
+def test_steps_below_one_is_refused():
+    r = subprocess.run([sys.executable, BENCH, "--steps", "0"], capture_output=True, text=True, env=_env(), timeout=300)
+    assert r.returncode == 2 and "--steps" in r.stderr
+
+
+@pytest.mark.gpu
+def test_plain_line_and_dumped_outputs_repeat(tmp_path):
+    """a plain run prints the headline fields and nothing that needs a run of its own (those take --full); two runs with the
+    same arguments dump the same arrays, float32 / float64 only"""
+    import numpy as np
+    lines = []
+    for k in range(2):
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--workload", "cfg1", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / f"run{k}")],
+                           capture_output=True, text=True, env=_env(), timeout=600, cwd=str(tmp_path))
+        assert r.returncode == 0, r.stderr[-4000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    d = lines[0]
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["higher_is_better"] is True and d["unit"] == "env-steps/s"
+    assert d["metric"] and d["dtype"] == "f32" and d["ms_per_step"] > 0
+    assert abs(d["value"] - 64 * 24 / (d["ms_per_step"] * 1e-3)) < 1e-3 * d["value"]
+    for k in ("roofline", "gae", "secondary", "cpu_baseline", "ms_per_step_no_readback", "comm", "strong"):
+        assert k not in d, k
+    assert d["config"]["full"] is False
+    names = sorted(os.listdir(tmp_path / "run0"))
+    assert names == sorted(os.listdir(tmp_path / "run1")) == sorted(n + ".npy" for n in d["outputs"]["arrays"])
+    assert {"params.npy", "rollout_obs.npy", "advantages.npy", "stat_approx_kl.npy"} <= set(names)
+    total = 0
+    for n in names:
+        x, y = np.load(tmp_path / "run0" / n), np.load(tmp_path / "run1" / n)
+        assert x.dtype in (np.float32, np.float64) and x.shape == y.shape, n
+        np.testing.assert_array_equal(x, y, err_msg=n)
+        total += os.path.getsize(tmp_path / "run0" / n)
+    assert total <= 64e6

@@ -4,7 +4,7 @@ set -u
 REPO=$PWD; OUT=$PWD/gpurun_out; mkdir -p $OUT; export TMPDIR=/tmp
 TAG=$1; shift
 rm -rf /tmp/prof_$TAG
-(cd /tmp && env "$@" timeout -s KILL 240 rocprofv3 --kernel-trace -d /tmp/prof_$TAG -- python $REPO/bench.py --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/trace_$TAG.log" 2>&1)
+(cd "$TMPDIR" && env "$@" timeout -s KILL 240 rocprofv3 --kernel-trace -d "$TMPDIR"/prof_$TAG -- python $REPO/bench.py --steps 3 --warmup 1 --no-cpu-baseline --full > "$OUT/trace_$TAG.log" 2>&1)
 DB=$(find /tmp/prof_$TAG -name '*.db' | head -1)
 [ -n "$DB" ] && python tools/rocpd_stats.py "$DB" > "$OUT/kernel_stats_$TAG.csv"
 python - "$OUT/kernel_stats_$TAG.csv" <<'PY'

@@ -19,7 +19,7 @@ SPECS=("$@")
 for r in $(seq 1 ${ROUNDS:-3}); do
   for spec in "${SPECS[@]}"; do
     set -- $spec; wl=$1; tag=$2; shift 2
-    env "$@" X=1 timeout 300 python bench.py --steps ${STEPS:-10} --warmup 3 --no-cpu-baseline --workload $wl ${EXTRA:-} 2>/dev/null | tail -1 | python -c "
+    env "$@" X=1 timeout 300 python bench.py --steps ${STEPS:-10} --warmup 3 --no-cpu-baseline --full --workload $wl ${EXTRA:-} 2>/dev/null | tail -1 | python -c "
 import json,sys
 try:
     d=json.loads(sys.stdin.read())

@@ -10,7 +10,7 @@ T0=$(date +%s)
 # SKIP_TESTS=1: profile passes and bench lines only (a second box for the same, already validated tree)
 if [ "${SKIP_TESTS:-0}" != "1" ]; then
 echo "== GPU suite"
-timeout 1500 python -m pytest tests -m gpu -q --timeout 600 -p no:cacheprovider -x > "$OUT/final_tests.log" 2>&1
+CATPPO_PARITY_RECORD="$OUT/${TAG}_parity.json" timeout 1500 python -m pytest tests -m gpu -q --timeout 600 -p no:cacheprovider -x > "$OUT/final_tests.log" 2>&1
 tail -6 "$OUT/final_tests.log" | cut -c1-220
 echo "== smoke ($(( $(date +%s) - T0 )) s)"
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
@@ -31,8 +31,8 @@ mkdir -p profiles && cp "$OUT/${TAG}_pmc_traffic_cfg2.json" "$OUT/${TAG}_bench_c
 bash tools/gpu_trace_one.sh reference $TAG > /dev/null 2>&1
 python tools/explain_plan.py --all > "$OUT/${TAG}_explain_plan.txt" 2>/dev/null
 echo "== bench lines ($(( $(date +%s) - T0 )) s)"
-timeout 400 python bench.py 2> "$OUT/${TAG}_bench_cfg2.err" | tail -1 > "$OUT/${TAG}_bench_cfg2.json"
-B="timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline"
+timeout 400 python bench.py --full 2> "$OUT/${TAG}_bench_cfg2.err" | tail -1 > "$OUT/${TAG}_bench_cfg2.json"
+B="timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --full"
 $B --workload reference 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_reference.json"
 $B --workload cfg2 --mlp-precision bf16x3 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_cfg2_bf16x3.json"
 : > "$OUT/${TAG}_bench_other_configs.jsonl"
@@ -41,10 +41,10 @@ CATPPO_FORCE_DIST=1 $B --workload cfg2 2>/dev/null | tail -1 > "$OUT/${TAG}_benc
 : > "$OUT/${TAG}_bench_cfg3_shares.jsonl"
 for W in 1 2 4 8; do $B --workload cfg3 --shard-of $W 2>/dev/null | tail -1 >> "$OUT/${TAG}_bench_cfg3_shares.jsonl"; done
 echo "== launcher proof: bench.py starts two ranks itself (one GPU: gloo host staging) ($(( $(date +%s) - T0 )) s)"
-timeout 600 python bench.py --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline 2> "$OUT/${TAG}_bench_cfg2_gpus2_selflaunch.err" | tail -1 > "$OUT/${TAG}_bench_cfg2_gpus2_selflaunch.json"
+timeout 600 python bench.py --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline --full 2> "$OUT/${TAG}_bench_cfg2_gpus2_selflaunch.err" | tail -1 > "$OUT/${TAG}_bench_cfg2_gpus2_selflaunch.json"
 echo "== three more default lines back to back (run-to-run spread) ($(( $(date +%s) - T0 )) s)"
 : > "$OUT/${TAG}_bench_cfg2_repeats.jsonl"
-for i in 1 2 3; do timeout 300 python bench.py --no-cpu-baseline 2>/dev/null | tail -1 >> "$OUT/${TAG}_bench_cfg2_repeats.jsonl"; done
+for i in 1 2 3; do timeout 300 python bench.py --no-cpu-baseline --full 2>/dev/null | tail -1 >> "$OUT/${TAG}_bench_cfg2_repeats.jsonl"; done
 if [ -f tools/bin/libcatppo_s16tl.so ]; then
   echo "== step16 timeline ($(( $(date +%s) - T0 )) s)"
   (for net in ref cfg2; do echo "==== $net"; CATPPO_LIB=$PWD/tools/bin/libcatppo_s16tl.so timeout 120 python tools/step16_timeline.py 2048 $net; done) 2>&1 | grep -v amdgpu.ids > "$OUT/${TAG}_step16_timeline.txt"

@@ -6,7 +6,7 @@ WL=${WL:-cfg2}
 for name in "$@"; do
   if [ "$name" = tree ]; then lib=$R/constraints-as-terminations_amd/lib/libcatppo.so; else lib=$R/tools/bin/libcatppo_$name.so; fi
   dir=/tmp/prof_$name; rm -rf $dir
-  (cd /tmp && CATPPO_LIB=$lib timeout -s KILL 200 rocprofv3 --kernel-trace -d $dir -- python $R/bench.py --workload $WL --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/trace_$name.log" 2>&1)
+  (cd "$TMPDIR" && CATPPO_LIB=$lib timeout -s KILL 200 rocprofv3 --kernel-trace -d $dir -- python $R/bench.py --workload $WL --steps 3 --warmup 1 --no-cpu-baseline --full > "$OUT/trace_$name.log" 2>&1)
   DB=$(find $dir -name '*.db' | head -1)
   [ -n "$DB" ] && python tools/rocpd_stats.py "$DB" > "$OUT/kstats_${WL}_$name.csv"
   echo "== $name"; python - <<PY

@@ -11,7 +11,7 @@ SFX=${3:-}
 OUT=$PWD/gpurun_out
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-CMD="python $PWD/bench.py --workload $WL --steps 3 --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-}"
+CMD="python $PWD/bench.py --workload $WL --steps 3 --warmup 1 --no-cpu-baseline --full ${BENCH_ARGS:-}"
 run_pass() {   # name, rocprof args...
   local name=$1; shift
   local dir=/tmp/prof_$name
