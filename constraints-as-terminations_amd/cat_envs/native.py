@@ -245,7 +245,7 @@ def layout_of(shape: MlpShape) -> MlpLayout:
     if rc != 0:
         raise ValueError(f"unsupported MLP shape (obs={shape.obs_dim}, act={shape.act_dim}, "
                          f"hidden={list(shape.hidden)[:shape.n_hidden]}): hidden widths must be multiples of 64, "
-                         "the last one in {64,128,256,512}, act_dim <= 15")
+                         "the last one in {64,128,256,512}, 1 <= act_dim <= 63")
     return lay
 
 

@@ -26,6 +26,7 @@ namespace {
 #include "mlp_common.h"
 #include "mlp_forward.h"
 #include "mlp_loss.h"
+#include "mlp_wide.h"
 #include "step16.h"
 #include "mlp_backward.h"
 #include "mlp_optim.h"
@@ -79,6 +80,7 @@ bool fused_fwd_plan(const catppo_mlp_shape* sh, const catppo_mlp_layout& L, int6
   static const int max_rows = env_int("CATPPO_FUSED_FWD_MAX_ROWS", 4096);
   static const int min_rows = env_int("CATPPO_FUSED_FWD_MIN_ROWS", 2049);
   if (!enabled || rows > max_rows || rows < min_rows || sh->mfma_bf16 != 0) return false;
+  if (sh->act_dim >= kMaxA) return false;     // fused_head: 16 slots
   const int nl = sh->n_hidden;
   const int hl = sh->hidden[nl - 1];
   if (hl != 128 && hl != 256 && hl != 512) return false;
@@ -114,6 +116,7 @@ bool fused_fwd_plan(const catppo_mlp_shape* sh, const catppo_mlp_layout& L, int6
 bool rows_fwd_plan(const catppo_mlp_shape* sh, const catppo_mlp_layout& L, int n_layers, int R, FusedFwdArgs* fa,
                    size_t* lds) {
   if (sh->mfma_bf16 != 0 || n_layers < 1 || n_layers > sh->n_hidden) return false;
+  if (sh->act_dim >= kMaxA) return false;     // fused_head of the rollout form: 16 slots
   for (int l = 0; l < n_layers; ++l)
     if (sh->hidden[l] != rowsfwd::kWidth) return false;
   const int wmax = L.obs_pad > rowsfwd::kWidth ? L.obs_pad : rowsfwd::kWidth;
@@ -186,6 +189,7 @@ bool rows_fwd_launch_rollout(const FusedFwdArgs& fa, size_t lds, int64_t rows, i
 bool rows_wide_plan(const catppo_mlp_shape* sh, const catppo_mlp_layout& L, int n_layers, int R, FusedFwdArgs* fa,
                     size_t* lds, int* nch) {
   if (sh->mfma_bf16 != 0 || n_layers < 1 || n_layers > 3 || n_layers > sh->n_hidden) return false;
+  if (sh->act_dim >= kMaxA) return false;     // fused_head of the rollout form: 16 slots
   if (L.obs_pad > 64) return false;
   const int w0 = sh->hidden[0];
   if (w0 != 128 && w0 != 256 && w0 != 512) return false;
@@ -263,7 +267,8 @@ int policy_core(catppo_ctx* ctx, const catppo_mlp_shape* shape, const float* par
     // CATPPO_STEP16_FWD=0 keeps the layer-wise launches (A/B); CATPPO_STEP16_FWD_MAX_ROWS moves the bound.
     static const int s16f_on = env_int("CATPPO_STEP16_FWD", 1);
     static const int s16f_max = env_int("CATPPO_STEP16_FWD_MAX_ROWS", 2048);
-    if (s16f_on && N <= s16f_max && shape->mfma_bf16 == 0 && shape->n_hidden == 3 && N * 512 * 4 < (int64_t(1) << 31)) {
+    if (s16f_on && N <= s16f_max && shape->mfma_bf16 == 0 && shape->n_hidden == 3 && shape->act_dim < kMaxA &&
+        N * 512 * 4 < (int64_t(1) << 31)) {
       FusedFwdArgs fa{};
       fa.x = x, fa.params = params, fa.M = N, fa.Dp = L.obs_pad, fa.n_hidden = 3, fa.n_flat = L.n_flat;
       for (int net = 0; net < 2; ++net)
@@ -372,11 +377,38 @@ int policy_core(catppo_ctx* ctx, const catppo_mlp_shape* shape, const float* par
   if (fwd16) forward_hidden16(shape, L, params, x, N, w, critic_only ? 1 : 2, s, shape->n_hidden, true);
   else forward_hidden(shape, L, params, x, N, w, 0, critic_only ? 1 : 2, s);
   if (fwd16) catppo_plan_note(ctx, "rollout forward, %lld rows: bf16-stored activations between the layer-wise launches", (long long)N);
+  const int nl = shape->n_hidden, A = critic_only ? 0 : shape->act_dim;
+  if (shape->act_dim >= kMaxA) {
+    // 16 <= A <= 63 (mlp_wide.h): the heads of a row in the 64 lanes of its wave; 8 rows per workgroup amortise the staging
+    // of the A x HL actor weights.  The critic-only call takes the same kernel: its values equal the full call's bit for bit.
+    const float* nul = nullptr;
+    catppo_plan_note(ctx, "rollout forward, %lld rows: %d layer-wise GEMM launches (%s) + head_act_wide_kernel%s "
+                     "[act_dim %d >= %d: no one-launch forward has wide heads]", (long long)N, shape->n_hidden,
+                     fwd16 ? "bf16-stored activations" : "gemm_f32_kernel", critic_only ? " (critic only)" : "",
+                     shape->act_dim, kMaxA);
+    CATPPO_CHECK_LAUNCH(ctx);
+    int64_t nblk = cdiv64(N, 8);
+    if (nblk > 2048) nblk = 2048;
+    const int rc = dispatch_cpl(shape->hidden[nl - 1], [&](auto cpl) {
+      constexpr int CPL = decltype(cpl)::value;
+      const size_t lds = wide_w_lds<CPL>() ? sizeof(float) * A * shape->hidden[nl - 1] : 0;
+      auto kern = head_act_wide_kernel<CPL>;
+      if (lds > 64 * 1024)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(256), lds, s, (const float*)w.H[0][nl - 1],
+                         critic_only ? nul : (const float*)w.H[1][nl - 1], params + L.off_w[0][nl], params + L.off_b[0][nl],
+                         params + L.off_w[1][nl], params + L.off_b[1][nl], params + L.off_logstd, eps, given_action, N, A,
+                         action, logprob, value, (int)(value_dtype == CATPPO_F16), critic_only ? nullptr : rng_state,
+                         rng_step, eps_out);
+    });
+    if (rc) return catppo_fail(ctx, CATPPO_E_ARG, "%s: last hidden width unsupported", fn);
+    CATPPO_CHECK_LAUNCH(ctx);
+    return CATPPO_OK;
+  }
   catppo_plan_note(ctx, "rollout forward, %lld rows: %d layer-wise GEMM launches (gemm_f32_kernel) + head_act_kernel "
                    "[outside the one-launch window %s, or operand precision %d != fp32]", (long long)N, shape->n_hidden,
                    "CATPPO_FUSED_FWD_MIN_ROWS..MAX_ROWS (2049..4096)", shape->mfma_bf16);
   CATPPO_CHECK_LAUNCH(ctx);
-  const int nl = shape->n_hidden, A = critic_only ? 0 : shape->act_dim;
   // one row per wave (4 per workgroup), up to 2048 workgroups: measured 9.5 us at 4096 rows against 13.7 us with 16 rows
   // per workgroup - the parallelism of many short workgroups beats amortising the 16 x HL head-weight staging
   int64_t nblk = cdiv64(N, 4);
@@ -694,25 +726,44 @@ int minibatch_grad_core(catppo_ctx* ctx, const catppo_mlp_shape* shape, const ca
     g.vrms_mean = vrms_mean, g.vrms_var = vrms_var;
     g.part_w = w.head_w, g.part_s = w.head_s, g.branch_out = ctx->branch_out;
     g.M = M, g.A = A, g.hp = *hp;
-    const int rc = dispatch_cpl(HL, [&](auto cpl) {
-      constexpr int CPL = decltype(cpl)::value;
-      if constexpr (CPL <= 4) {
-        if (small_tiles) {
-          head_loss_kernel<CPL, 16><<<dim3(nbh), dim3(head_waves<CPL>() * 64), head_lds, s>>>(g);
-          return;
+    if (A >= kMaxA) {
+      // 16 <= A <= 63 (mlp_wide.h): head_loss_kernel's contract with the heads of a row in the 64 lanes of its wave
+      int nbw = (int)cdiv64(M, kWideHeadRows);
+      if (nbw > kHeadMaxBlocks) nbw = kHeadMaxBlocks;
+      const int rc = dispatch_cpl(HL, [&](auto cpl) {
+        constexpr int CPL = decltype(cpl)::value;
+        const size_t lds = wide_head_lds_bytes<CPL>(A);
+        auto kern = head_loss_wide_kernel<CPL>;
+        if (lds > 64 * 1024)
+          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        kern<<<dim3(nbw), dim3(kWideHeadThreads), lds, s>>>(g);
+      });
+      if (rc) return catppo_fail(ctx, CATPPO_E_ARG, "%s: last hidden width unsupported", __func__);
+      nbh = nbw;
+      catppo_plan_note(ctx, "minibatch %lld rows: %d layer-wise forward GEMM launches + head_loss_wide_kernel (%d-row tiles, %d blocks) "
+                       "[act_dim %d >= %d: the 16-slot head kernels do not apply]", (long long)M, nl, kWideHeadRows, nbh, A, kMaxA);
+      CATPPO_CHECK_LAUNCH(ctx);
+    } else {
+      const int rc = dispatch_cpl(HL, [&](auto cpl) {
+        constexpr int CPL = decltype(cpl)::value;
+        if constexpr (CPL <= 4) {
+          if (small_tiles) {
+            head_loss_kernel<CPL, 16><<<dim3(nbh), dim3(head_waves<CPL>() * 64), head_lds, s>>>(g);
+            return;
+          }
         }
-      }
-      auto kern = head_loss_kernel<CPL>;
-      if (head_lds > 64 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)head_lds);
-      kern<<<dim3(nbh), dim3(head_waves<CPL>() * 64), head_lds, s>>>(g);
-    });
-    if (rc) return catppo_fail(ctx, CATPPO_E_ARG, "%s: last hidden width unsupported", __func__);
-    catppo_plan_note(ctx, "minibatch %lld rows: %d layer-wise forward GEMM launches + head_loss_kernel (%d-row tiles, %d blocks) "
-                     "[fused last-layer launch needs a 128 / 256-wide last layer and >= %d workgroups = %d rows]",
-                     (long long)M, nl, TRh, nbh, fused_head_min, fused_head_min * 32);
-    CATPPO_CHECK_LAUNCH(ctx);
+        auto kern = head_loss_kernel<CPL>;
+        if (head_lds > 64 * 1024)
+          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)head_lds);
+        kern<<<dim3(nbh), dim3(head_waves<CPL>() * 64), head_lds, s>>>(g);
+      });
+      if (rc) return catppo_fail(ctx, CATPPO_E_ARG, "%s: last hidden width unsupported", __func__);
+      catppo_plan_note(ctx, "minibatch %lld rows: %d layer-wise forward GEMM launches + head_loss_kernel (%d-row tiles, %d blocks) "
+                       "[fused last-layer launch needs a 128 / 256-wide last layer and >= %d workgroups = %d rows]",
+                       (long long)M, nl, TRh, nbh, fused_head_min, fused_head_min * 32);
+      CATPPO_CHECK_LAUNCH(ctx);
+    }
   }
 
   // 4. backward through the hidden layers; split-K partials for every weight gradient

@@ -7,7 +7,8 @@
 using gemm::Operands;
 using gemm::Params;
 
-constexpr int kMaxA = 16;
+constexpr int kMaxA = 16;        // slots of the 16-slot head kernels (reduce16): A <= 15 actor outputs + the critic
+constexpr int kMaxAWide = 64;    // lanes of the wide head kernels (mlp_wide.h): 16 <= A <= 63 actor outputs + the critic
 constexpr float kHalfLog2Pi = 0.91893853320467274178f;   // log(sqrt(2*pi))
 constexpr float kEntConst = 1.41893853320467274178f;     // 0.5 + 0.5*log(2*pi)
 constexpr int kHeadRowsPerBlock = 32;                    // head_loss row tile (16 rows when the last layer is 512 wide)
@@ -17,7 +18,7 @@ constexpr int kGatherRows = 64;
 // ------------------------------------------------------------------------------- layout
 int layout_of(const catppo_mlp_shape* s, catppo_mlp_layout* L) {
   if (!s || !L) return CATPPO_E_ARG;
-  if (s->obs_dim < 1 || s->act_dim < 1 || s->act_dim >= kMaxA) return CATPPO_E_ARG;  // slot act_dim = critic
+  if (s->obs_dim < 1 || s->act_dim < 1 || s->act_dim >= kMaxAWide) return CATPPO_E_ARG;  // one slot / lane for the critic
   if (s->mfma_bf16 < 0 || s->mfma_bf16 > 2) return CATPPO_E_ARG;
   if (s->n_hidden < 1 || s->n_hidden > CATPPO_MAX_HIDDEN) return CATPPO_E_ARG;
   for (int l = 0; l < s->n_hidden; ++l)

@@ -249,7 +249,9 @@ int catppo_rms_merge(catppo_ctx* ctx, const double* sums, double n, int D, float
 
 typedef struct catppo_mlp_shape {
   int32_t obs_dim;                  /* D  */
-  int32_t act_dim;                  /* A  (<= 15) */
+  int32_t act_dim;                  /* A  (1..63): A <= 15 runs the 16-slot head kernels (one-launch forwards, step16,
+                                       fused last layer); 16..63 the wide heads (64 lanes: A actor outputs + the critic)
+                                       behind the layer-wise hidden-layer launches */
   int32_t n_hidden;                 /* L  (1..CATPPO_MAX_HIDDEN) */
   int32_t hidden[CATPPO_MAX_HIDDEN]; /* widths, each a multiple of 64 */
   int32_t mfma_bf16;                /* 0: fp32-input MFMA (reference numerics, default).  1: the hidden-layer GEMMs
@@ -408,11 +410,15 @@ int catppo_kl_adaptive_lr(catppo_ctx* ctx, catppo_iter_state* state, const float
  *   eps          supplied N(0,1) noise [N, A]: a = mu + sigma * eps (Normal.sample(), cleanrl/ppo.py:111)
  *   state, step  on-device noise: Philox4x32-10 + Box-Muller inside the head kernel; element (env i, dim k) of rollout
  *                step `step` of iteration state->iteration uses counter {i, k/4, step, iteration}, key = state->seed,
- *                lane k%4 of the block; eps_out ([N, A], may be NULL) receives it, so a parity test can replay it
+ *                lane k%4 of the block (independent of A: dimension k draws the same noise at every action width);
+ *                eps_out ([N, A], may be NULL) receives it, so a parity test can replay it
  *   given_action evaluate these actions (log-prob / value of stored actions)
  * value_dtype: CATPPO_F32, or CATPPO_F16 to store `value` as IEEE half (fp16 rollout planes).
  * Kernels by batch size (catppo_plan_log names them): <= 2048 rows step16_fwd_kernel (16-row tiles), 2049-4096 the 32-row
- * row-resident kernels, else layer-wise GEMM launches + head_act_kernel. */
+ * row-resident kernels, else layer-wise GEMM launches + head_act_kernel.  act_dim >= 16: always the layer-wise hidden-layer
+ * launches (fp32-stored, or bf16-stored in the bf16-operand mode from 4096 rows) + head_act_wide_kernel, the critic-only
+ * form included (its values equal the full call's bit for bit); the optimiser step of such a shape runs the layer-wise
+ * forward + head_loss_wide_kernel in place of head_loss_kernel. */
 int catppo_policy_step(catppo_ctx* ctx, const catppo_mlp_shape* shape, const float* params, const float* x, int64_t N,
                        const float* eps, const float* given_action, const catppo_iter_state* state, int32_t step,
                        float* eps_out, float* action, float* logprob, void* value, int value_dtype, void* stream);

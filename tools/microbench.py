@@ -1,7 +1,7 @@
 """Per-kernel-group timings on one MI355X (HIP events on torch's current stream, which is the
 stream every libcatppo call is enqueued on).  Prints one JSON object per line.
 
-    python tools/microbench.py [--reps 50]
+    python tools/microbench.py [--reps 50] [--act 12]
 """
 import argparse
 import ctypes as C
@@ -42,6 +42,7 @@ def timeit(fn, reps, warmup=5):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--act", type=int, default=12, help="action dimensions of the MLP sections (16..63: the wide head kernels)")
     a = ap.parse_args()
     nat = native.Native()
     dev = "cuda"
@@ -115,7 +116,7 @@ def main():
     # ---- MLP
     for D, hidden, bf16 in [(45, (512, 256, 128), 0), (48, (256, 256, 256), 0), (48, (256, 256, 256), 2),
                             (48, (256, 256, 256), 1)]:
-        A = 12
+        A = a.act
         shape = native.shape_of(D, A, hidden, mfma_bf16=bf16)
         tag = {0: "", 1: "[bf16 operands]", 2: "[bf16x3 split operands]"}[bf16]
         lay = native.layout_of(shape)
