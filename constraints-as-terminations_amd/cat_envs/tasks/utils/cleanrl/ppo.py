@@ -496,12 +496,11 @@ class PPOTrainer:
         self._grad_overlap_mode = go
         # single process: an optimiser step is ONE library call (catppo_ppo_minibatch_step_packed) whose fold launches
         # emit the squared gradient norm of the clip - the launch that re-read the gradient for it is gone.  Not with
-        # exchange points on (the gradient all-reduce sits between fold and clip) nor with the side-stream experiment.
+        # exchange points on (the gradient all-reduce sits between fold and clip).
         ocs = getattr(c, "one_call_step", None)
         if os.environ.get("CATPPO_ONE_CALL_STEP") is not None:
             ocs = os.environ["CATPPO_ONE_CALL_STEP"] == "1"
-        self.one_call_step = (True if ocs is None else bool(ocs)) and not parallel.active() and \
-            os.environ.get("CATPPO_SIDE_STREAM", "0") != "1"
+        self.one_call_step = (True if ocs is None else bool(ocs)) and not parallel.active()
         self._graph_id = None
         self._eager_updates_left = 1 if parallel.active() else 0
         self.graph_nodes = 0

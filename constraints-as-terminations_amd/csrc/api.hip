@@ -27,9 +27,6 @@ extern "C" int catppo_create(int device, catppo_ctx** out) {
   catppo_ctx* ctx = new catppo_ctx();
   ctx->device = device;
   ctx->n_cu = prop.multiProcessorCount;
-  // measured on MI355X: forking the weight-gradient GEMMs to a side stream is 5% SLOWER for the whole
-  // iteration (both chains are MFMA bound; they only steal each other's CUs) - off unless asked for
-  if (const char* e = getenv("CATPPO_SIDE_STREAM")) ctx->use_side = (e[0] == '1');
   *out = ctx;
   int cur = 0;
   (void)hipGetDevice(&cur);

@@ -208,8 +208,6 @@ extern "C" int catppo_set_grad_overlap(catppo_ctx* ctx, int on) {
   CATPPO_CHECK_ARG(ctx, ctx != nullptr);
   if (on == -1) return (ctx->grad_overlap && ctx->comm != nullptr) ? 1 : 0;
   CATPPO_CHECK_ARG(ctx, on == 0 || on == 1 || on == 2);
-  if (on && ctx->use_side)
-    return catppo_fail(ctx, CATPPO_E_ARG, "catppo_set_grad_overlap: the side stream is taken by CATPPO_SIDE_STREAM=1");
   ctx->grad_overlap = on;
   return CATPPO_OK;
 }

@@ -15,10 +15,9 @@ struct catppo_ctx {
   int n_cu = 256;
   void* ws = nullptr;        // generic workspace (device)
   uint64_t ws_bytes = 0;
-  // side stream + events: the weight-gradient GEMMs of the backward pass run beside the
-  // data-gradient chain (fork/join around catppo_ppo_minibatch_grad, capturable in a hipGraph)
+  // side stream + events: the gradient exchange of an optimiser step (buckets / tail, see grad_overlap) runs beside
+  // the backward launches (fork/join inside catppo_ppo_minibatch_grad*, capturable in a hipGraph)
   hipStream_t side = nullptr;
-  bool use_side = false;     // CATPPO_SIDE_STREAM=1 forks the weight-gradient GEMMs (measured slower)
   hipEvent_t ev_fork[CATPPO_MAX_HIDDEN + 1] = {};
   hipEvent_t ev_join = nullptr;
   hipEvent_t ev_tail = nullptr;     // rollout.hip: orders another stream behind a deferred post tail (created on first use)

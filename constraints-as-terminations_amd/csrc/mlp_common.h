@@ -1,11 +1,36 @@
-// Shared pieces of the actor-critic MLP translation unit (mlp.hip): flat parameter layout, workspace carving, GEMM launch
-// helpers (tile choice), wave-level helpers.  Included INSIDE mlp.hip's anonymous namespace - one translation unit, split by
-// role for reading (round 5): mlp_common.h | mlp_forward.h | mlp_loss.h | mlp_backward.h | mlp_optim.h.
+// Shared pieces of the actor-critic MLP translation unit (mlp.hip): the run-time switches, the two launch helpers
+// (launch_lds, dispatch_value), flat parameter layout, workspace carving, GEMM launch helpers (tile choice), wave-level
+// helpers.  Included INSIDE mlp.hip's anonymous namespace - one translation unit, split by role for reading: every header
+// holds the kernels of its role and, at its end, the host functions that launch them:
+// mlp_common.h | mlp_forward.h | mlp_loss.h | mlp_wide.h | step16.h | mlp_step.h | mlp_backward.h | mlp_optim.h.
 #pragma once
-
 
 using gemm::Operands;
 using gemm::Params;
+
+// ------------------------------------------------------------------------------- launch helpers
+// Launch with `lds_bytes` of dynamic LDS; above 64 KB the kernel's limit is raised first - per call, not once per
+// process: the attribute belongs to the current device's copy of the kernel.
+template <typename... KArgs, typename... Args>
+void launch_lds(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s, Args&&... args) {
+  if (lds_bytes > 64 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+  hipLaunchKernelGGL(kernel, grid, block, lds_bytes, s, static_cast<KArgs>(args)...);
+}
+
+// Run-time integer -> compile-time value: calls f(std::integral_constant<int, V>{}) for the V of the list that equals v.
+// Returns whether one did; every caller's list holds all values layout_of and the plans admit, so no match is a bug.
+template <int... Vs, typename F>
+bool dispatch_value(int v, F&& f) {
+  const bool matched = ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+  assert(matched && "dispatch_value: a value outside the compiled list");
+  return matched;
+}
+// last hidden width (64 / 128 / 256 / 512) -> columns per lane of the wave-per-row head kernels
+template <typename F>
+bool dispatch_cpl(int hl, F&& f) {
+  return dispatch_value<64, 128, 256, 512>(hl, [&](auto w) { f(std::integral_constant<int, decltype(w)::value / 64>{}); });
+}
 
 constexpr int kMaxA = 16;        // slots of the 16-slot head kernels (reduce16): A <= 15 actor outputs + the critic
 constexpr int kMaxAWide = 64;    // lanes of the wide head kernels (mlp_wide.h): 16 <= A <= 63 actor outputs + the critic
@@ -87,6 +112,9 @@ inline int split_cap(int out, int in) {
   return (int)(cap > kMaxSplitCap ? kMaxSplitCap : cap);
 }
 
+// rows of the widest 16-row-tile step: carve() holds head partial rows for (rows / 16) tiles x 2 networks up to here, and
+// switches() clamps both step16 windows to it
+constexpr int kStep16MaxRows = 8192;
 bool carve(const catppo_mlp_shape* s, const catppo_mlp_layout& L, int64_t M, bool training, char* base,
            uint64_t cap, MlpWs* w) {
   uint64_t used = 0;
@@ -100,7 +128,7 @@ bool carve(const catppo_mlp_shape* s, const catppo_mlp_layout& L, int64_t M, boo
   };
   const int nl = s->n_hidden, A = s->act_dim;
   // upper bound of the head partial rows: head_loss blocks (16-row tiles at most), or step16's 16-row tiles x 2 networks
-  const int64_t nbg = cdiv64(M, kGatherRows), nbh = M <= 8192 ? 2 * cdiv64(M, 16) : cdiv64(M, 16);
+  const int64_t nbg = cdiv64(M, kGatherRows), nbh = M <= kStep16MaxRows ? 2 * cdiv64(M, 16) : cdiv64(M, 16);
   // reduction partials first: the non-MLP calls use the front of the workspace too, but never
   // concurrently with an MLP call on the same stream
   w->xmb = (float*)take(sizeof(float) * M * L.obs_pad);
@@ -130,37 +158,64 @@ bool carve(const catppo_mlp_shape* s, const catppo_mlp_layout& L, int64_t M, boo
   return ok;
 }
 
-// ------------------------------------------------------------------------------- GEMM launch
-constexpr int kSmallRows = 4096;    // see launch_dw_dx_pair
-
+// ------------------------------------------------------------------------------- switches
 static int env_int(const char* name, int dflt) {
   const char* e = getenv(name);
   return e ? atoi(e) : dflt;
 }
-// Params::xcd_legacy = 1 is the round-2 workgroup -> tile order (gemm::xcd_tile_of); its A/B switch went with round 6's prune
-static int xcd_legacy() { return 0; }
 
-// fp32 launch with a wider contraction slab (latency-bound small-M launches: fewer global round trips per tile)
-template <int BM, int BN, bool A_KC, bool B_KC, int EPI, int BKT>
-void launch_gemm_bk(const Params& p, hipStream_t s) {
-  dim3 grid(((p.J + BN - 1) / BN) * ((p.I + BM - 1) / BM), 1, p.nets * p.splits);
-  constexpr size_t lds = gemm::smem_bytes<BM, BN, A_KC, B_KC, BKT>();
-  auto kern = gemm::gemm_f32_kernel<BM, BN, A_KC, B_KC, EPI, BKT>;
-  if (lds > 64 * 1024)     // per call, not once per process: the attribute belongs to the current device's copy of the kernel
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  kern<<<grid, dim3(256), lds, s>>>(p);
+// Every environment switch of the MLP dispatch, read once per process (switches()).  The non-default values are A/B
+// forms; the tests use them as the reference of their bit-identity checks.
+struct MlpSwitches {
+  // rollout forward
+  int fused_fwd = env_int("CATPPO_FUSED_FWD", 1);                        // 0: no fused_fwd_kernel (layer-wise launches instead)
+  int fused_fwd_min_rows = env_int("CATPPO_FUSED_FWD_MIN_ROWS", 2049);   // row window of the 32-row one-launch forwards (fused_fwd_plan
+  int fused_fwd_max_rows = env_int("CATPPO_FUSED_FWD_MAX_ROWS", 4096);   //   has the measurements; the tests pin it open for small batches)
+  int step16_fwd = env_int("CATPPO_STEP16_FWD", 1);                      // 0: layer-wise launches below the 32-row kernels' window
+  int step16_fwd_max_rows = env_int("CATPPO_STEP16_FWD_MAX_ROWS", 2048); // upper bound of step16_fwd_kernel's window (<= kStep16MaxRows)
+  int rows_fwd_rollout = env_int("CATPPO_ROWS_FWD_ROLLOUT", 1);          // 0: fused_fwd_kernel instead of rows_fwd_kernel<32>
+  int rows_wide = env_int("CATPPO_ROWS_WIDE", 1);                        // 0: no rows_fwd_wide_kernel, rollout or training
+  int rows_wide_rollout = env_int("CATPPO_ROWS_WIDE_ROLLOUT", 1);        // 0: fused_fwd_kernel instead of rows_fwd_wide_kernel<32>
+  // both
+  int act16 = env_int("CATPPO_ACT16", 1);                                // 0: fp32-stored activations rounded at every use (bf16 operands)
+  // optimiser step
+  int fused_head = env_int("CATPPO_FUSED_HEAD", 1);                      // 0: last-layer GEMM and head_loss_kernel as two launches
+  int fused_head_min_wg = env_int("CATPPO_FUSED_HEAD_MIN_WG", 128);      // workgroups the fused launch needs (128 = 4096 rows)
+  int step16 = env_int("CATPPO_STEP16", 1);                              // 0: layer-wise launches for small minibatches
+  int step16_max_rows = env_int("CATPPO_STEP16_MAX_ROWS", 4096);         // upper bound of step16_kernel's window (<= kStep16MaxRows)
+  int rows_fwd = env_int("CATPPO_ROWS_FWD", 1);                          // 0: layer-wise forward below the last hidden layer
+  int rows_fwd_min_rows = env_int("CATPPO_ROWS_FWD_MIN_ROWS", 8192);     // rows the row-resident training forward needs
+  int dw0_fold = env_int("CATPPO_DW0_FOLD", 1);                          // 0: first layer's weight gradient and the fold as two launches
+  int dw_fill = env_int("CATPPO_DW_FILL", 1);                            // 0: 128x128 weight-gradient tiles even when they underfill the chip
+};
+inline const MlpSwitches& switches() {
+  static const MlpSwitches sw = [] {
+    MlpSwitches d;
+    if (d.step16_max_rows > kStep16MaxRows) d.step16_max_rows = kStep16MaxRows;
+    if (d.step16_fwd_max_rows > kStep16MaxRows) d.step16_fwd_max_rows = kStep16MaxRows;
+    return d;
+  }();
+  return sw;
 }
 
+// ------------------------------------------------------------------------------- GEMM launch
+constexpr int kSmallRows = 4096;    // see launch_dw_dx_pair
+
+// (Params::xcd_legacy = 1 is the round-2 workgroup -> tile order, gemm::xcd_tile_of; its A/B switch has been pruned: every
+// Params here is value-initialised, which leaves it 0)
+template <int BM, int BN>
+constexpr int tiles_of(const Params& p) { return ((p.J + BN - 1) / BN) * ((p.I + BM - 1) / BM); }   // 1-D tile index, see kernel
+
+// one operand-precision mode, explicitly (the bf16-stored modes 3 .. 6 of gemm_f32.h)
+template <int BM, int BN, bool A_KC, bool B_KC, int EPI, int PREC>
+void launch_gemm_prec(const Params& p, hipStream_t s) {
+  dim3 grid(tiles_of<BM, BN>(p), 1, p.nets * p.splits);
+  constexpr size_t lds = gemm::smem_bytes<BM, BN, A_KC, B_KC>();
+  gemm::gemm_f32_kernel<BM, BN, A_KC, B_KC, EPI, gemm::BK, PREC><<<grid, dim3(256), lds, s>>>(p);
+}
 template <int BM, int BN, bool A_KC, bool B_KC, int EPI>
-void launch_gemm(const Params& p, hipStream_t s, int prec) {
-  dim3 grid(((p.J + BN - 1) / BN) * ((p.I + BM - 1) / BM), 1, p.nets * p.splits);   // 1-D tile index, see kernel
-  const size_t lds = gemm::smem_bytes<BM, BN, A_KC, B_KC>();
-  if (prec == 2)
-    gemm::gemm_f32_kernel<BM, BN, A_KC, B_KC, EPI, gemm::BK, 2><<<grid, dim3(256), lds, s>>>(p);
-  else if (prec == 1)
-    gemm::gemm_f32_kernel<BM, BN, A_KC, B_KC, EPI, gemm::BK, 1><<<grid, dim3(256), lds, s>>>(p);
-  else
-    gemm::gemm_f32_kernel<BM, BN, A_KC, B_KC, EPI><<<grid, dim3(256), lds, s>>>(p);
+void launch_gemm(const Params& p, hipStream_t s, int prec) {      // prec 0 / 1 / 2: layout_of admits no other operand precision
+  dispatch_value<0, 1, 2>(prec, [&](auto pr) { launch_gemm_prec<BM, BN, A_KC, B_KC, EPI, decltype(pr)::value>(p, s); });
 }
 
 // Tile choice from tools/gemm_probe on MI355X (M=16384, both nets per launch): 128x128 pays only when
@@ -180,87 +235,53 @@ void launch_gemm_auto(const Params& p, hipStream_t s, int prec) {
   if constexpr (EPI != gemm::EPI_PARTIAL) {
     constexpr int small_bk = 64;      // see kSmallRows (32-wide slabs measured in between, round 2)
     if (prec == 0 && p.I <= kSmallRows && p.Kc % small_bk == 0 && p.Kc >= 2 * small_bk) {
-      launch_gemm_bk<64, 64, A_KC, B_KC, EPI, 64>(p, s);
+      // fp32 with a wider contraction slab (latency-bound small-M launches: fewer global round trips per tile)
+      launch_lds(gemm::gemm_f32_kernel<64, 64, A_KC, B_KC, EPI, small_bk>, dim3(tiles_of<64, 64>(p), 1, p.nets * p.splits),
+                 dim3(256), gemm::smem_bytes<64, 64, A_KC, B_KC, small_bk>(), s, p);
       return;
     }
   }
   launch_gemm<64, 64, A_KC, B_KC, EPI>(p, s, prec);
 }
 
-template <int BM, int BN>
-constexpr int tiles_of(const Params& p) { return ((p.J + BN - 1) / BN) * ((p.I + BM - 1) / BM); }
-
-// one operand-precision mode, explicitly (the bf16-stored modes 3 / 4 of gemm_f32.h)
-template <int BM, int BN, bool A_KC, bool B_KC, int EPI, int PREC>
-void launch_gemm_prec(const Params& p, hipStream_t s) {
-  dim3 grid(tiles_of<BM, BN>(p), 1, p.nets * p.splits);
-  constexpr size_t lds = gemm::smem_bytes<BM, BN, A_KC, B_KC>();
-  gemm::gemm_f32_kernel<BM, BN, A_KC, B_KC, EPI, gemm::BK, PREC><<<grid, dim3(256), lds, s>>>(p);
-}
-
-// bf16-stored mode: weight gradient (both operands bf16-stored, IILoop16) + data gradient against the TRANSPOSED bf16 weight
-// copy (K-contiguous x K-contiguous) in one launch; tile rules of launch_dw_dx_pair
-template <int BM0, int BN0, int BM1, int BN1>
-void launch_pair_tiles16(const Params& pw, const Params& px, hipStream_t s) {
-  const int t0 = tiles_of<BM0, BN0>(pw), n0 = t0 * pw.nets * pw.splits;
-  const int t1 = tiles_of<BM1, BN1>(px), n1 = t1 * px.nets * px.splits;
-  constexpr size_t lds0 = gemm::smem_bytes<BM0, BN0, false, false>();
-  constexpr size_t lds1 = gemm::smem_bytes<BM1, BN1, true, true>();
-  constexpr size_t lds = lds0 > lds1 ? lds0 : lds1;
-  gemm::gemm_pair_kernel<BM0, BN0, false, false, gemm::EPI_PARTIAL, BM1, BN1, true, true, gemm::EPI_MUL_DELU, 3>
-      <<<dim3(n0 + n1), dim3(256), lds, s>>>(pw, px, t0, n0, t1);
-}
-void launch_dw_dx_pair16(const Params& pw, const Params& px, hipStream_t s, int n_cu) {
-  const bool underfilled = tiles_of<128, 128>(pw) * pw.nets * pw.splits < n_cu;
-  const bool big = pw.I >= 128 && pw.J >= 128 && pw.kc_per_split >= 256 && !underfilled;
-  const bool wide = px.J >= 128;
-  if (big && wide) launch_pair_tiles16<128, 128, 64, 128>(pw, px, s);
-  else if (big) launch_pair_tiles16<128, 128, 64, 64>(pw, px, s);
-  else if (wide) launch_pair_tiles16<64, 64, 64, 128>(pw, px, s);
-  else launch_pair_tiles16<64, 64, 64, 64>(pw, px, s);
-}
-
 // weight gradient (problem 0: 128x128 tiles when the layer allows, else 64x64) + data gradient (problem 1: 64x128
 // tiles - measured best inside the pair on MI355X, 350 -> 338 us per minibatch against 64x64 - or 64x64 for
-// layers narrower than 128) of one layer in one launch
-template <int BM0, int BN0, int BM1, int BN1>
+// layers narrower than 128) of one layer in one launch.  ACT16, the bf16-stored mode: both operands of the weight
+// gradient bf16-stored (IILoop16), the data gradient against the TRANSPOSED bf16 weight copy (K-contiguous x K-contiguous).
+template <int BM0, int BN0, int BM1, int BN1, bool ACT16>
 void launch_pair_tiles(const Params& pw, const Params& px, hipStream_t s, int prec) {
   const int t0 = tiles_of<BM0, BN0>(pw), n0 = t0 * pw.nets * pw.splits;
   const int t1 = tiles_of<BM1, BN1>(px), n1 = t1 * px.nets * px.splits;
   constexpr size_t lds0 = gemm::smem_bytes<BM0, BN0, false, false>();
-  constexpr size_t lds1 = gemm::smem_bytes<BM1, BN1, true, false>();
+  constexpr size_t lds1 = gemm::smem_bytes<BM1, BN1, true, ACT16>();
   constexpr size_t lds = lds0 > lds1 ? lds0 : lds1;
-  if (prec == 2)
-    gemm::gemm_pair_kernel<BM0, BN0, false, false, gemm::EPI_PARTIAL, BM1, BN1, true, false, gemm::EPI_MUL_DELU, 2>
+  auto launch = [&](auto pr) {
+    gemm::gemm_pair_kernel<BM0, BN0, false, false, gemm::EPI_PARTIAL, BM1, BN1, true, ACT16, gemm::EPI_MUL_DELU, decltype(pr)::value>
         <<<dim3(n0 + n1), dim3(256), lds, s>>>(pw, px, t0, n0, t1);
-  else if (prec == 1)
-    gemm::gemm_pair_kernel<BM0, BN0, false, false, gemm::EPI_PARTIAL, BM1, BN1, true, false, gemm::EPI_MUL_DELU, 1>
-        <<<dim3(n0 + n1), dim3(256), lds, s>>>(pw, px, t0, n0, t1);
-  else
-    gemm::gemm_pair_kernel<BM0, BN0, false, false, gemm::EPI_PARTIAL, BM1, BN1, true, false, gemm::EPI_MUL_DELU>
-        <<<dim3(n0 + n1), dim3(256), lds, s>>>(pw, px, t0, n0, t1);
+  };
+  if constexpr (ACT16) launch(std::integral_constant<int, 3>{});
+  else dispatch_value<0, 1, 2>(prec, launch);
 }
 
 // Minibatches of at most kSmallRows rows leave every CU with one or two workgroups: each wave is alone on its SIMD and
 // every contraction slab costs a full global round trip.  There the weight gradient runs on 64x64 tiles (4x the
 // workgroups of the 128x128 choice: 2048 rows, 256x512 layer: 35 -> 27 us for the pair) and the forward GEMMs walk
 // the contraction in 64-wide slabs (4x fewer round trips; 112 -> 100 us per optimiser step together; measured with
-// switches that went with round 6's prune).
-void launch_dw_dx_pair(const Params& pw, const Params& px, hipStream_t s, int prec, int n_cu = 256) {
-  constexpr int small_tile = 1;
-  // Round 5: a weight gradient whose 128x128 tiling yields fewer long workgroups than there are CUs (a 128-wide layer - the
-  // reference's last hidden layer: 2 tiles x 2 networks x 32 splits = 128 on 256 CUs) takes 64x64 tiles instead (512
-  // shorter workgroups, same splits, same contraction order per element: bit-identical): the reference's layer-2 pair
-  // 60.1 -> 50.6 us, update phase 11.70 -> 11.51 ms (profiles/r5_ab_dw_fill.txt).  CATPPO_DW_FILL=0: the 128x128 tiling.
-  static const int dw_fill = env_int("CATPPO_DW_FILL", 1);
-  const bool underfilled = dw_fill && tiles_of<128, 128>(pw) * pw.nets * pw.splits < n_cu;      // (the device's CU count)
+// switches that have since been pruned).  The bf16-stored mode starts at 4096 rows and has no small-rows rule.
+// A weight gradient whose 128x128 tiling yields fewer long workgroups than there are CUs (a 128-wide layer - the
+// reference's last hidden layer: 2 tiles x 2 networks x 32 splits = 128 on 256 CUs) takes 64x64 tiles instead (512
+// shorter workgroups, same splits, same contraction order per element: bit-identical): the reference's layer-2 pair
+// 60.1 -> 50.6 us, update phase 11.70 -> 11.51 ms (profiles/r5_ab_dw_fill.txt).  CATPPO_DW_FILL=0: the 128x128 tiling.
+template <bool ACT16>
+void launch_dw_dx_pair(const Params& pw, const Params& px, hipStream_t s, int prec, int n_cu) {
+  const bool underfilled = (ACT16 || switches().dw_fill) && tiles_of<128, 128>(pw) * pw.nets * pw.splits < n_cu;   // the device's CU count
   const bool big = pw.I >= 128 && pw.J >= 128 && pw.kc_per_split >= 256 &&   // launch_gemm_auto's rule for EPI_PARTIAL
-                   !(px.I <= kSmallRows && small_tile) && !underfilled;
+                   (ACT16 || px.I > kSmallRows) && !underfilled;
   const bool wide = px.J >= 128;
-  if (big && wide) launch_pair_tiles<128, 128, 64, 128>(pw, px, s, prec);
-  else if (big) launch_pair_tiles<128, 128, 64, 64>(pw, px, s, prec);
-  else if (wide) launch_pair_tiles<64, 64, 64, 128>(pw, px, s, prec);
-  else launch_pair_tiles<64, 64, 64, 64>(pw, px, s, prec);
+  if (big && wide) launch_pair_tiles<128, 128, 64, 128, ACT16>(pw, px, s, prec);
+  else if (big) launch_pair_tiles<128, 128, 64, 64, ACT16>(pw, px, s, prec);
+  else if (wide) launch_pair_tiles<64, 64, 64, 128, ACT16>(pw, px, s, prec);
+  else launch_pair_tiles<64, 64, 64, 64, ACT16>(pw, px, s, prec);
 }
 
 // hidden-layer forward for `nets` networks starting at net index net0
@@ -269,15 +290,9 @@ void forward_hidden(const catppo_mlp_shape* sh, const catppo_mlp_layout& L, cons
   if (n_layers < 0) n_layers = sh->n_hidden;
   for (int l = 0; l < n_layers; ++l) {
     Params p{};
-    p.xcd_legacy = xcd_legacy();
-    p.nets = nets;
-    p.splits = 1;
-    p.I = (int)M;
-    p.J = sh->hidden[l];
-    p.Kc = L.in_dim[l];
-    p.lda = L.in_dim[l];
-    p.ldb = L.in_dim[l];
-    p.ldc = sh->hidden[l];
+    p.nets = nets, p.splits = 1;
+    p.I = (int)M, p.J = sh->hidden[l], p.Kc = L.in_dim[l];
+    p.lda = L.in_dim[l], p.ldb = L.in_dim[l], p.ldc = sh->hidden[l];
     for (int n = 0; n < nets; ++n) {
       const int net = net0 + n;
       p.op[n].A = l == 0 ? x : w.H[net][l - 1];

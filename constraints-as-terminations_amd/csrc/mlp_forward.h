@@ -1,6 +1,6 @@
 // Forward kernels of the actor-critic MLP (cleanrl/ppo.py:78-123): the rollout head (head_act_kernel), the one-launch
 // small-batch forward of round 3 (fused_fwd_kernel) and the row-resident forwards of rounds 4 / 5 (rows_fwd_kernel,
-// fwd_rows.h; rows_fwd_wide_kernel, fwd_rows_wide.h).  Part of mlp.hip's translation unit (see mlp_common.h).
+// fwd_rows.h; rows_fwd_wide_kernel, fwd_rows_wide.h), the bf16-stored layer-wise forward, and at the end their plans and launches.  Part of mlp.hip's translation unit (see mlp_common.h).
 #pragma once
 
 // ------------------------------------------------------------------------------- rollout head
@@ -631,3 +631,287 @@ extern "C" int catppo_debug_fused_tl(void* buf) {     // timeline builds only: n
   return hipMemcpyToSymbol(HIP_SYMBOL(g_fftl), &pbuf, sizeof(pbuf)) == hipSuccess ? 0 : -1;
 }
 #endif
+
+// ------------------------------------------------------------------------------- bf16 weight copies (bf16-stored mode)
+// W_l (l >= 1) of both networks as bf16, as stored ([out][in]: forward operand) and transposed ([in][out]: the data gradient's
+// K-contiguous operand), once per optimiser step from the fp32 master parameters - 0.26 M elements at cfg5.
+struct W16Segs {
+  int n;
+  int64_t off[2 * CATPPO_MAX_HIDDEN];
+  int out[2 * CATPPO_MAX_HIDDEN], in[2 * CATPPO_MAX_HIDDEN];
+  int64_t first[2 * CATPPO_MAX_HIDDEN + 1];
+};
+__device__ __forceinline__ void w16_convert_block(const float* __restrict__ params, uint16_t* __restrict__ w16,
+                                                  uint16_t* __restrict__ w16t, const W16Segs& t, const int block) {
+  const int64_t e = (int64_t)block * 256 + threadIdx.x;
+  if (e >= t.first[t.n]) return;
+  int i = 0;
+  while (i + 1 < t.n && e >= t.first[i + 1]) ++i;
+  const int64_t le = e - t.first[i];
+  w16[t.off[i] + le] = __builtin_bit_cast(uint16_t, (__bf16)params[t.off[i] + le]);
+  // transposed copy: consecutive threads WRITE consecutive elements ([in][out], r fastest) and read a column of W from L2
+  const int c = (int)(le / t.out[i]), r = (int)(le % t.out[i]);
+  w16t[t.off[i] + le] = __builtin_bit_cast(uint16_t, (__bf16)params[t.off[i] + (int64_t)r * t.in[i] + c]);
+}
+
+// The first layer's forward (fp32-stored observations and W_0, bf16-stored output: PREC 4) with the weight conversion riding in
+// the same launch: workgroups [0, n_conv) convert (n_conv a multiple of 8: the XCD of a GEMM workgroup is that of its tile index),
+// the rest run 64x64 tiles.  Nothing in this launch reads the copies; the next launch (layer 1) does.
+__global__ __launch_bounds__(256) void fwd0_w16_kernel(const gemm::Params p, const int n_conv, const int tiles,
+                                                       const float* __restrict__ params, uint16_t* __restrict__ w16,
+                                                       uint16_t* __restrict__ w16t, const W16Segs t) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int b = blockIdx.x;
+  if (b < n_conv) {
+    w16_convert_block(params, w16, w16t, t, b);
+    return;
+  }
+  const gemm::TileId id = gemm::xcd_tile_of(b - n_conv, tiles, (gridDim.x - n_conv) / tiles, p.xcd_legacy);
+  gemm::gemm_body<64, 64, true, true, gemm::EPI_BIAS_ELU, gemm::BK, 4>(p, id.tile, id.bz, smem);
+}
+
+// Layer-wise forward of hidden layers 0 .. n_layers - 1 with bf16-STORED activations (gemm_f32.h "act16"), `nets` networks from
+// network 0: the first layer's launch also makes the bf16 weight copies of layers 1 .. nl - 1 (stored + transposed) that
+// every later launch of the step reads.  last_fp32: the last of these layers writes fp32 (a consumer that reads fp32
+// activations follows: head_act_kernel of the rollout forward).  Returns the number of weights converted.
+int64_t forward_hidden16(const catppo_mlp_shape* sh, const catppo_mlp_layout& L, const float* params, const float* x, int64_t M,
+                         const MlpWs& w, int nets, hipStream_t s, int n_layers, bool last_fp32) {
+  const int nl = sh->n_hidden;
+  W16Segs ws16{};
+  int64_t tot = 0;
+  for (int net = 0; net < nets; ++net)
+    for (int l = 1; l < nl; ++l) {
+      const int i = ws16.n++;
+      ws16.off[i] = L.off_w[net][l], ws16.out[i] = sh->hidden[l], ws16.in[i] = L.in_dim[l];
+      ws16.first[i] = tot;
+      tot += (int64_t)sh->hidden[l] * L.in_dim[l];
+    }
+  ws16.first[ws16.n] = tot;
+  for (int l = 0; l < n_layers; ++l) {
+    Params pf{};
+    pf.nets = nets, pf.splits = 1;
+    pf.I = (int)M, pf.J = sh->hidden[l];
+    pf.ldc = sh->hidden[l];                           // bf16 or fp32 elements
+    for (int net = 0; net < nets; ++net) {
+      pf.op[net].bias = params + L.off_b[net][l];
+      pf.op[net].C = w.H[net][l];
+      if (l == 0) {
+        pf.op[net].A = x, pf.op[net].B = params + L.off_w[net][0];
+      } else {
+        pf.op[net].A = w.H[net][l - 1];
+        pf.op[net].B = reinterpret_cast<const float*>(w.w16 + L.off_w[net][l]);
+      }
+    }
+    const bool out32 = last_fp32 && l == n_layers - 1;
+    if (l == 0) {                                        // fp32-stored operands (observations, W_0), bf16-stored output
+      pf.Kc = L.in_dim[0], pf.lda = L.in_dim[0], pf.ldb = L.in_dim[0];
+      const int n_conv = (int)((cdiv64(tot, 256) + 7) / 8 * 8), t0 = tiles_of<64, 64>(pf);
+      constexpr size_t lds0 = gemm::smem_bytes<64, 64, true, true>();
+      hipLaunchKernelGGL(fwd0_w16_kernel, dim3((unsigned)(n_conv + t0 * nets)), dim3(256), lds0, s, pf, n_conv, t0, params, w.w16,
+                         w.w16t, ws16);
+    } else {                                             // bf16-stored operands: contraction sizes in FLOAT units
+      pf.Kc = L.in_dim[l] / 2, pf.lda = L.in_dim[l] / 2, pf.ldb = L.in_dim[l] / 2;
+      const bool big = pf.J >= 128 && L.in_dim[l] >= 256;
+      if (out32) {
+        if (big) launch_gemm_prec<128, 128, true, true, gemm::EPI_BIAS_ELU, 6>(pf, s);
+        else launch_gemm_prec<64, 64, true, true, gemm::EPI_BIAS_ELU, 6>(pf, s);
+      } else {
+        if (big) launch_gemm_prec<128, 128, true, true, gemm::EPI_BIAS_ELU, 3>(pf, s);
+        else launch_gemm_prec<64, 64, true, true, gemm::EPI_BIAS_ELU, 3>(pf, s);      // (64x64 for a wide layer: measured 0.8 us slower)
+      }
+    }
+  }
+  return tot;
+}
+
+// =============================================================================== host side: plans and launches
+// A `*_plan` function says whether a one-launch forward applies to a shape and fills the per-path fields of its
+// FusedFwdArgs (Dp, n_hidden, hidden, ld0 / ld1, offsets) and its LDS bytes; it makes no HIP call.
+
+// fused_fwd_kernel applies when: fp32 MFMA, every hidden width a multiple of 128 (a wave owns 32 columns of a 256 /
+// 128-column chunk), a head width the head code knows, the two activation tiles + the weight rings fit the LDS, and the
+// batch is in the window where one 32-row workgroup per CU (x 2 networks) beats the layer-wise launches: 2049-4096
+// rows (measured: 4096 rows -0.2 ms per 24-step rollout, 2048 rows equal, below that the workgroup's ~35 us serial
+// time loses to the launch-bound small GEMMs).  CATPPO_FUSED_FWD=0 disables it (A/B), CATPPO_FUSED_FWD_MIN_ROWS /
+// _MAX_ROWS move the window (the tests pin it open to cover small and ragged batches).
+bool fused_fwd_plan(const catppo_mlp_shape* sh, const catppo_mlp_layout& L, int64_t rows, FusedFwdArgs* fa, size_t* lds) {
+  const MlpSwitches& sw = switches();
+  if (!sw.fused_fwd || rows > sw.fused_fwd_max_rows || rows < sw.fused_fwd_min_rows || sh->mfma_bf16 != 0) return false;
+  if (sh->act_dim >= kMaxA) return false;     // fused_head: 16 slots
+  const int nl = sh->n_hidden;
+  const int hl = sh->hidden[nl - 1];
+  if (hl != 128 && hl != 256 && hl != 512) return false;
+  int w0 = L.obs_pad, w1 = 0;
+  for (int l = 0; l < nl; ++l) {
+    if (sh->hidden[l] % 128 != 0) return false;
+    int& dst = (l % 2 == 0) ? w1 : w0;       // layer l writes act1 for even l, act0 for odd l
+    dst = dst > sh->hidden[l] ? dst : sh->hidden[l];
+  }
+  fa->Dp = L.obs_pad, fa->n_hidden = nl;
+  fa->ld0 = w0 + 4, fa->ld1 = w1 + 4;
+  for (int l = 0; l < nl; ++l) fa->hidden[l] = sh->hidden[l];
+  for (int net = 0; net < 2; ++net)
+    for (int l = 0; l <= nl; ++l) fa->off_w[net][l] = L.off_w[net][l], fa->off_b[net][l] = L.off_b[net][l];
+  *lds = sizeof(float) * ((size_t)kFR * (fa->ld0 + fa->ld1) + kFRing);
+  // fused_chunk's pipeline deliberately runs past the end of a contraction: its last iterations stage up to three 16-k
+  // weight slabs beyond the last row of a chunk (never multiplied) and read A fragments past K in the LDS tile.  Both
+  // are in bounds only because of how the buffers are laid out - checked here instead of assumed: (1) every hidden
+  // weight matrix is followed by at least 64 more floats of the flat parameter buffer (its bias, the next layer),
+  // (2) the two activation tiles are followed by the weight rings inside the same dynamic-LDS allocation (act0's
+  // overrun lands in act1, act1's in the rings: >= 64 floats each).  A layout that breaks either takes the layer-wise path.
+  for (int net = 0; net < 2; ++net)
+    for (int l = 0; l < nl; ++l)
+      if (L.off_w[net][l] + (int64_t)sh->hidden[l] * L.in_dim[l] + 64 > L.n_flat) return false;
+  static_assert(kFRing >= 64, "the weight rings double as the over-read margin of the activation tiles");
+  if ((size_t)kFR * fa->ld1 < 64) return false;
+  return *lds <= 160 * 1024;
+}
+
+// rows_fwd_kernel<R> applies when: fp32 MFMA, every layer it computes is 256 wide (eight waves x 32 columns, outputs of a
+// layer held in accumulators until the tile may be overwritten), at most three of them (the compiled layer counts), the
+// tile + rings fit the LDS.  `n_layers` hidden layers are computed (training: all but the last; rollout: all).
+bool rows_fwd_plan(const catppo_mlp_shape* sh, const catppo_mlp_layout& L, int n_layers, int R, FusedFwdArgs* fa,
+                   size_t* lds) {
+  if (sh->mfma_bf16 != 0 || n_layers < 1 || n_layers > 3 || n_layers > sh->n_hidden) return false;
+  if (sh->act_dim >= kMaxA) return false;     // fused_head of the rollout form: 16 slots
+  for (int l = 0; l < n_layers; ++l)
+    if (sh->hidden[l] != rowsfwd::kWidth) return false;
+  const int wmax = L.obs_pad > rowsfwd::kWidth ? L.obs_pad : rowsfwd::kWidth;
+  fa->Dp = L.obs_pad, fa->n_hidden = n_layers;
+  fa->ld0 = wmax + 4, fa->ld1 = 0;            // (w + 4) / 4 odd: 16 rows of a b128 read hit 16 distinct 4-bank slots
+  for (int l = 0; l < n_layers; ++l) fa->hidden[l] = sh->hidden[l];
+  for (int net = 0; net < 2; ++net)
+    for (int l = 0; l <= sh->n_hidden; ++l) fa->off_w[net][l] = L.off_w[net][l], fa->off_b[net][l] = L.off_b[net][l];
+  // a 48-wide first layer reads its second 32-k slab 16 floats past every weight row: the last row's over-read must
+  // stay inside the flat buffer (it lands in the bias that follows)
+  // and the run-ahead requests of slabs past the last one read up to 160 floats past every weight matrix (its bias
+  // and the next layer follow it in the flat buffer)
+  for (int net = 0; net < 2; ++net)
+    for (int l = 0; l < n_layers; ++l)
+      if (L.off_w[net][l] + (int64_t)sh->hidden[l] * L.in_dim[l] + 160 > L.n_flat) return false;
+  if (L.obs_pad > 256) return false;          // observation tile: eight float4 per thread
+  *lds = R == 64 ? rowsfwd::lds_bytes<64>(fa->ld0) : rowsfwd::lds_bytes<32>(fa->ld0);
+  return *lds <= 160 * 1024;
+}
+
+// rows_fwd_wide_kernel (fwd_rows_wide.h) applies when: fp32 MFMA, the first layer is 128 / 256 / 512 wide (512: consumed
+// in two 256-column chunks by the layer above, which must be computed here too), every other computed layer 128 / 256
+// wide, the padded observation width <= 64 (the observation tile persists next to the activation tile), and the run-ahead
+// weight requests stay inside the flat parameter buffer.  Networks whose computed layers are ALL 256 wide keep
+// rows_fwd_kernel (one in-place tile: also fits wide observations).
+bool rows_wide_plan(const catppo_mlp_shape* sh, const catppo_mlp_layout& L, int n_layers, int R, FusedFwdArgs* fa,
+                    size_t* lds, int* nch) {
+  if (sh->mfma_bf16 != 0 || n_layers < 1 || n_layers > 3 || n_layers > sh->n_hidden) return false;
+  if (sh->act_dim >= kMaxA) return false;     // fused_head of the rollout form: 16 slots
+  if (L.obs_pad > 64) return false;
+  const int w0 = sh->hidden[0];
+  if (w0 != 128 && w0 != 256 && w0 != 512) return false;
+  if (w0 == 512 && n_layers < 2) return false;
+  for (int l = 1; l < n_layers; ++l)
+    if (sh->hidden[l] != 128 && sh->hidden[l] != 256) return false;
+  *nch = w0 == 512 ? 2 : 1;
+  fa->Dp = L.obs_pad, fa->n_hidden = n_layers;
+  fa->ld0 = rowsfwd::kTileLd, fa->ld1 = L.obs_pad + 4;      // (w + 4) / 4 odd for Dp = 16 / 32 / 48 / 64: conflict-free b128 rows
+  for (int l = 0; l < n_layers; ++l) fa->hidden[l] = sh->hidden[l];
+  for (int net = 0; net < 2; ++net)
+    for (int l = 0; l <= sh->n_hidden; ++l) fa->off_w[net][l] = L.off_w[net][l], fa->off_b[net][l] = L.off_b[net][l];
+  // over-reads: `pre` reads k 32..63 of every first-layer row (a 48-wide row: 16 floats into the next row / the bias),
+  // the long contractions request up to three 32-k slabs past the end of a weight row range (<= 160 floats past a matrix)
+  for (int net = 0; net < 2; ++net)
+    for (int l = 0; l < n_layers; ++l)
+      if (L.off_w[net][l] + (int64_t)sh->hidden[l] * L.in_dim[l] + 160 > L.n_flat) return false;
+  *lds = R == 64 ? rowsfwd::wide_lds_bytes<64>(fa->ld1) : rowsfwd::wide_lds_bytes<32>(fa->ld1);
+  return *lds <= 160 * 1024;
+}
+
+// The layer counts (and, wide form, first-layer chunk counts) below are the ones the plans admit: a planned launch never declines.
+template <int R, bool TRAIN, int NETS>
+void rows_fwd_launch(const FusedFwdArgs& a, size_t lds, int64_t tiles, int nets, hipStream_t s) {
+  dispatch_value<1, 2, 3>(a.n_hidden, [&](auto nl) {
+    launch_lds(rows_fwd_kernel<R, TRAIN, NETS, decltype(nl)::value>, dim3((unsigned)tiles, NETS == 2 ? 1 : nets),
+               dim3(rowsfwd::kThreads), lds, s, a);
+  });
+}
+template <int R, bool TRAIN, int NETS>
+void rows_wide_launch(const FusedFwdArgs& a, size_t lds, int64_t tiles, int nets, int nch, hipStream_t s) {
+  dispatch_value<1, 2, 3>(a.n_hidden, [&](auto nl) {
+    dispatch_value<1, 2>(nch, [&](auto ch) {
+      constexpr int NL = decltype(nl)::value, NCH = decltype(ch)::value;
+      if constexpr (NCH == 1 || NL >= 2)      // a 512-wide first layer (two chunks) comes with the layer that consumes it
+        launch_lds(rows_fwd_wide_kernel<R, TRAIN, NETS, NL, NCH>, dim3((unsigned)tiles, NETS == 2 ? 1 : nets),
+                   dim3(rowsfwd::kThreads), lds, s, a);
+    });
+  });
+}
+
+// training launch of either row-resident kernel (R = 64, activations stored): one to three layers.  Enough row tiles
+// to fill the chip: one workgroup walks both networks (one round of workgroups, the observation tile of a row block
+// fetched by one CU); fewer: one workgroup per (tile, network).  nch == 0: rows_fwd_kernel, else the wide kernel.
+void rows_launch_train(const FusedFwdArgs& fa, size_t lds, int nch, int64_t rows, int n_cu, hipStream_t s) {
+  FusedFwdArgs a = fa;
+  const int64_t tiles = cdiv64(rows, 64);
+  a.nets_per_wg = tiles >= n_cu ? 2 : 1;
+  a.store_policy = 0;
+  dispatch_value<1, 2>(a.nets_per_wg, [&](auto nets) {
+    if (nch == 0) rows_fwd_launch<64, true, decltype(nets)::value>(a, lds, tiles, 2, s);
+    else rows_wide_launch<64, true, decltype(nets)::value>(a, lds, tiles, 2, nch, s);
+  });
+}
+
+// ------------------------------------------------------------------------------- rollout forward: the one-launch candidates
+// Each takes the call's FusedFwdArgs (pointers, heads, noise source, outputs), declines (false) or launches for `nets`
+// networks (1: critic only) and writes its plan note.  policy_core walks them in order.
+
+// row-resident forward with full-line weight loads for networks whose hidden layers are all 256 wide, same window as
+// fused_fwd_kernel (which keeps the other shapes): 32.1 -> 30 us per env step at cfg2, rollout 1.75 -> 1.70 ms
+// (interleaved A/B, profiles/r4_ab_rows_fwd.txt); CATPPO_ROWS_FWD_ROLLOUT=0 falls back to fused_fwd_kernel
+bool rollout_rows_fwd(catppo_ctx* ctx, const catppo_mlp_shape* shape, const catppo_mlp_layout& L, const FusedFwdArgs& call,
+                      int nets, hipStream_t s) {
+  const MlpSwitches& sw = switches();
+  const int64_t N = call.M;
+  FusedFwdArgs a = call;
+  size_t lds = 0;
+  if (!(sw.rows_fwd_rollout && N <= sw.fused_fwd_max_rows && N >= sw.fused_fwd_min_rows && shape->n_hidden <= 3 &&
+        rows_fwd_plan(shape, L, shape->n_hidden, 32, &a, &lds)))
+    return false;
+  a.nets_per_wg = 1;      // one workgroup per (tile, network)
+  rows_fwd_launch<32, false, 1>(a, lds, cdiv64(N, 32), nets, s);
+  catppo_plan_note(ctx, "rollout forward, %lld rows: rows_fwd_kernel<32> + heads, %lld tiles x %d networks, ONE launch "
+                   "[every hidden layer 256 wide, %d..%d rows, fp32]", (long long)N, (long long)cdiv64(N, 32), nets,
+                   sw.fused_fwd_min_rows, sw.fused_fwd_max_rows);
+  return true;
+}
+
+// networks that are not 256 wide throughout (the reference's 512 / 256 / 128) - rows_fwd_wide_kernel<32>;
+// CATPPO_ROWS_WIDE=0 / CATPPO_ROWS_WIDE_ROLLOUT=0 fall back to fused_fwd_kernel (A/B)
+bool rollout_rows_wide(catppo_ctx* ctx, const catppo_mlp_shape* shape, const catppo_mlp_layout& L, const FusedFwdArgs& call,
+                       int nets, hipStream_t s) {
+  const MlpSwitches& sw = switches();
+  const int64_t N = call.M;
+  FusedFwdArgs a = call;
+  size_t lds = 0;
+  int nch = 1;
+  const int hl = shape->hidden[shape->n_hidden - 1];
+  if (!(sw.rows_wide && sw.rows_wide_rollout && N <= sw.fused_fwd_max_rows && N >= sw.fused_fwd_min_rows &&
+        (hl == 128 || hl == 256) && rows_wide_plan(shape, L, shape->n_hidden, 32, &a, &lds, &nch)))
+    return false;
+  a.nets_per_wg = 1;
+  rows_wide_launch<32, false, 1>(a, lds, cdiv64(N, 32), nets, nch, s);
+  catppo_plan_note(ctx, "rollout forward, %lld rows: rows_fwd_wide_kernel<32> + heads, %lld tiles x %d networks, ONE launch "
+                   "[first layer %d wide in %d chunk(s), other layers 128 / 256, padded observations <= 64, fp32]",
+                   (long long)N, (long long)cdiv64(N, 32), nets, shape->hidden[0], nch);
+  return true;
+}
+
+// every layer + the head in one launch for the shapes the row-resident kernels leave
+bool rollout_fused_fwd(catppo_ctx* ctx, const catppo_mlp_shape* shape, const catppo_mlp_layout& L, const FusedFwdArgs& call,
+                       int nets, hipStream_t s) {
+  const int64_t N = call.M;
+  FusedFwdArgs a = call;
+  size_t lds = 0;
+  if (!fused_fwd_plan(shape, L, N, &a, &lds)) return false;
+  launch_lds(fused_fwd_kernel, dim3((unsigned)cdiv64(N, kFR), nets), dim3(kFT), lds, s, a);
+  catppo_plan_note(ctx, "rollout forward, %lld rows: fused_fwd_kernel (round 3: two ping-pong tiles, 16-k slabs), ONE launch "
+                   "[shape outside the row-resident kernels: widths / observation width / 512-wide head]", (long long)N);
+  return true;
+}

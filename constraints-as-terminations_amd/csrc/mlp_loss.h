@@ -919,3 +919,83 @@ extern "C" int catppo_debug_fwd_head_tl(void* buf) {     // timeline builds only
   return hipMemcpyToSymbol(HIP_SYMBOL(g_fhtl), &pbuf, sizeof(pbuf)) == hipSuccess ? 0 : -1;
 }
 #endif
+
+// =============================================================================== host side
+// The head kernels' view of a gathered minibatch - the one place HeadArgs is filled.  A kernel reads the fields of its
+// form only (step16_kernel and fwd_head_kernel keep the last activations on the CU and never read Hc / Ha).
+HeadArgs head_args(const catppo_mlp_shape* shape, const catppo_mlp_layout& L, const MlpWs& w, const catppo_ppo_hparams* hp,
+                   const float* params, int64_t M, const float* vrms_mean, const float* vrms_var, const float* adv_stats,
+                   int32_t* branch_out) {
+  const int nl = shape->n_hidden;
+  HeadArgs g{};
+  g.Hc = w.H[0][nl - 1], g.Ha = w.H[1][nl - 1];
+  g.dZc = w.dZ[0][nl - 1], g.dZa = w.dZ[1][nl - 1];
+  g.W4c = params + L.off_w[0][nl], g.b4c = params + L.off_b[0][nl];
+  g.W4a = params + L.off_w[1][nl], g.b4a = params + L.off_b[1][nl];
+  g.logstd = params + L.off_logstd;
+  g.act = w.act, g.oldlogp = w.scal, g.adv = w.scal + M, g.ret_n = w.scal + 2 * M, g.val_n = w.scal + 3 * M;
+  g.adv_part = w.adv_part, g.n_adv_part = (int)cdiv64(M, kGatherRows);
+  g.adv_stats = hp->adv_stats_external ? adv_stats : nullptr;
+  g.vrms_mean = vrms_mean, g.vrms_var = vrms_var;
+  g.part_w = w.head_w, g.part_s = w.head_s, g.branch_out = branch_out;
+  g.M = M, g.A = shape->act_dim, g.hp = *hp;
+  return g;
+}
+
+// head_loss_kernel's row tile, block count and LDS bytes.  Small minibatches (env-sharded runs: 2048 samples per rank):
+// 16-row tiles double the workgroup count of a launch that would otherwise occupy a quarter of the CUs.  Blocks =
+// weight-gradient partials folded afterwards; the LDS tile decides residency: when only one block fits a CU (HL >= 256)
+// a second round of blocks cannot overlap the first, so one block per CU walks several tiles and pays the set-up (head
+// weights, advantage statistics, partial flush) once.
+struct HeadLossTiling {
+  bool small_tiles;
+  int rows, blocks;
+  size_t lds;
+};
+HeadLossTiling head_loss_tiling(int HL, int64_t M) {
+  HeadLossTiling t{};
+  t.small_tiles = HL <= 256 && cdiv64(M, head_rows(HL)) < 128;
+  t.rows = t.small_tiles ? 16 : head_rows(HL);
+  t.blocks = (int)cdiv64(M, t.rows);
+  t.lds = sizeof(float) * ((size_t)16 * HL + 2 * (size_t)t.rows * HL + t.rows * 16 + 48 + 4);
+  const int cap = 2 * t.lds > 160 * 1024 ? kHeadMaxBlocks / 2 : kHeadMaxBlocks;
+  if (t.blocks > cap) t.blocks = cap;
+  return t;
+}
+
+void launch_head_loss(const HeadArgs& g, int HL, const HeadLossTiling& t, hipStream_t s) {
+  dispatch_cpl(HL, [&](auto cpl) {      // layout_of admits only these widths
+    constexpr int CPL = decltype(cpl)::value;
+    if constexpr (CPL <= 4)      // (no 16-row form of the 512-wide kernel)
+      if (t.small_tiles) return launch_lds(head_loss_kernel<CPL, 16>, dim3(t.blocks), dim3(head_waves<CPL>() * 64), t.lds, s, g);
+    launch_lds(head_loss_kernel<CPL>, dim3(t.blocks), dim3(head_waves<CPL>() * 64), t.lds, s, g);
+  });
+}
+
+// last hidden layer + heads + PPO loss + head backward in ONE launch: HL 128 / 256, `prec` the operand precision of the
+// layer's GEMM (0 fp32, 1 bf16, 2 split-bf16, 3 bf16-STORED operands: act16).  The activations of the last layer never
+// leave the CU.
+void launch_fwd_head(const catppo_mlp_shape* shape, const catppo_mlp_layout& L, const MlpWs& w, const float* params,
+                     int64_t M, int prec, const HeadArgs& g, hipStream_t s) {
+  const int nl = shape->n_hidden, HL = shape->hidden[nl - 1];
+  const bool act16 = prec == 3;
+  Params p{};
+  p.nets = 2, p.splits = 1;
+  p.I = (int)M, p.J = HL, p.Kc = L.in_dim[nl - 1];
+  p.lda = p.Kc, p.ldb = p.Kc, p.ldc = HL;
+  for (int net = 0; net < 2; ++net) {
+    p.op[net].A = w.H[net][nl - 2];
+    p.op[net].B = params + L.off_w[net][nl - 1];
+    p.op[net].bias = params + L.off_b[net][nl - 1];
+    p.op[net].C = nullptr;
+    if (act16) p.op[net].B = reinterpret_cast<const float*>(w.w16 + L.off_w[net][nl - 1]);
+  }
+  if (act16) p.Kc /= 2, p.lda /= 2, p.ldb /= 2;      // bf16-stored operands: FLOAT units (gemm_f32.h)
+  dispatch_value<128, 256>(HL, [&](auto hl) {
+    dispatch_value<0, 1, 2, 3>(prec, [&](auto pr) {
+      constexpr int HLc = decltype(hl)::value;
+      launch_lds(fwd_head_kernel<HLc, decltype(pr)::value>, dim3((unsigned)cdiv64(M, 64), 1, 2), dim3(256),
+                 sizeof(float) * fwd_head_lds_floats<HLc>(), s, p, g);
+    });
+  });
+}

@@ -931,3 +931,77 @@ __global__ __launch_bounds__(step16::kThreads) void step16_fwd_kernel(const Fuse
   if (a.do_head) fused_head<N2, kR>(a, t2, ld2, net, r0, t0);      // (the first activation tile is free: head weights go there)
 }
 #undef STEP16_MFMA
+
+// =============================================================================== host side
+// THE list of shapes the two 16-row kernels are compiled for: f(DP, N0, N1, N2 as integral constants) for the entry that
+// matches (padded observation width, three hidden widths).  Returns whether one did.
+template <int DP, int N0, int N1, int N2, typename F>
+bool step16_try_shape(int dp, const int* hidden, F& f) {
+  if (dp != DP || hidden[0] != N0 || hidden[1] != N1 || hidden[2] != N2) return false;
+  using std::integral_constant;
+  f(integral_constant<int, DP>{}, integral_constant<int, N0>{}, integral_constant<int, N1>{}, integral_constant<int, N2>{});
+  return true;
+}
+template <typename F>
+bool step16_dispatch(int dp, const int* hidden, F&& f) {
+  return step16_try_shape<48, 512, 256, 128>(dp, hidden, f) ||      // the reference's Agent (45 / 48-d observations): cfg1, cfg3
+         step16_try_shape<48, 256, 256, 256>(dp, hidden, f);        // BASELINE configs[1]
+}
+// what both kernels need of a shape and a row count besides their own switch and window: fp32, three hidden layers, the
+// 16-slot heads, a compiled shape, and byte offsets of the widest activation matrix that fit 31 bits
+bool step16_applies(const catppo_mlp_shape* shape, const catppo_mlp_layout& L, int64_t rows) {
+  return shape->mfma_bf16 == 0 && shape->n_hidden == 3 && shape->act_dim < kMaxA && rows * 512 * 4 < (int64_t(1) << 31) &&
+         step16_dispatch(L.obs_pad, shape->hidden, [](auto...) {});
+}
+
+// Rollout forward for batches below the 32-row kernels' window - 2048 envs of an env-sharded rank, cfg1.
+// CATPPO_STEP16_FWD=0 keeps the layer-wise launches (A/B); CATPPO_STEP16_FWD_MAX_ROWS moves the bound.
+bool rollout_step16(catppo_ctx* ctx, const catppo_mlp_shape* shape, const catppo_mlp_layout& L, const FusedFwdArgs& call,
+                    int nets, hipStream_t s) {
+  const MlpSwitches& sw = switches();
+  const int64_t N = call.M;
+  if (!(sw.step16_fwd && N <= sw.step16_fwd_max_rows && step16_applies(shape, L, N))) return false;
+  FusedFwdArgs fa = call;
+  fa.Dp = L.obs_pad, fa.n_hidden = 3, fa.n_flat = L.n_flat;
+  for (int net = 0; net < 2; ++net)
+    for (int l = 0; l <= 3; ++l) fa.off_w[net][l] = L.off_w[net][l], fa.off_b[net][l] = L.off_b[net][l];
+  const int tiles16 = (int)cdiv64(N, step16::kR);
+  [[maybe_unused]] const bool compiled = step16_dispatch(L.obs_pad, shape->hidden, [&](auto dp, auto n0, auto n1, auto n2) {
+    constexpr int DP = decltype(dp)::value, N0 = decltype(n0)::value, N1 = decltype(n1)::value, N2 = decltype(n2)::value;
+    launch_lds(step16_fwd_kernel<DP, N0, N1, N2>, dim3((unsigned)tiles16, nets), dim3(step16::kThreads),
+               sizeof(float) * step16::lds_floats<DP, N0, N1, N2>(), s, fa);
+  });
+  assert(compiled);      // step16_applies said so
+  catppo_plan_note(ctx, "rollout forward, %lld rows: step16_fwd_kernel<%d, %d, %d, %d> + heads, %d tiles of 16 rows x %d networks, ONE "
+                   "launch [<= %d rows, fp32, a compiled shape]", (long long)N, L.obs_pad, shape->hidden[0], shape->hidden[1],
+                   shape->hidden[2], tiles16, nets, sw.step16_fwd_max_rows);
+  return true;
+}
+
+// Optimiser step of a small minibatch (an env-sharded rank's 2048 rows, cfg1): forward, heads, loss, head backward and the
+// data gradients of the hidden layers in ONE launch of 16-row workgroups, then every layer's weight gradient in one grouped
+// launch (dw_multi_kernel) and the fold: 3 launches instead of 10.  CATPPO_STEP16=0 keeps the layer-wise launches (A/B),
+// CATPPO_STEP16_MAX_ROWS moves the upper bound of the window.
+void launch_step16(catppo_ctx* ctx, const catppo_mlp_shape* shape, const catppo_mlp_layout& L, const MlpWs& w,
+                  const float* params, const HeadArgs& g, hipStream_t s) {
+  const int nl = shape->n_hidden;
+  const int64_t M = g.M;
+  step16::Args sa{};
+  sa.x = w.xmb, sa.params = params, sa.M = M, sa.n_flat = L.n_flat;
+  for (int net = 0; net < 2; ++net) {
+    for (int l = 0; l <= nl; ++l) sa.off_w[net][l] = L.off_w[net][l], sa.off_b[net][l] = L.off_b[net][l];
+    for (int l = 0; l < nl; ++l) sa.H[net][l] = l + 1 < nl ? w.H[net][l] : nullptr, sa.dZ[net][l] = w.dZ[net][l];
+  }
+  sa.g = g;
+  const int tiles16 = (int)cdiv64(M, step16::kR);
+  [[maybe_unused]] const bool compiled = step16_dispatch(L.obs_pad, shape->hidden, [&](auto dp, auto n0, auto n1, auto n2) {
+    constexpr int DP = decltype(dp)::value, N0 = decltype(n0)::value, N1 = decltype(n1)::value, N2 = decltype(n2)::value;
+    launch_lds(step16_kernel<DP, N0, N1, N2>, dim3((unsigned)tiles16, 2), dim3(step16::kThreads),
+               sizeof(float) * step16::lds_floats<DP, N0, N1, N2>(), s, sa);
+  });
+  assert(compiled);      // step16_applies said so
+  catppo_plan_note(ctx, "minibatch %lld rows: step16_kernel<%d, %d, %d, %d> - forward, heads, PPO loss, head backward and the "
+                   "hidden layers' data gradients in ONE launch, %d tiles of 16 rows x 2 networks [<= %d rows, fp32, "
+                   "a compiled shape]", (long long)M, L.obs_pad, shape->hidden[0], shape->hidden[1], shape->hidden[2], tiles16,
+                   switches().step16_max_rows);
+}

@@ -69,6 +69,20 @@ def test_small_minibatch_step_against_the_default_small_path(tmp_path):
     np.testing.assert_allclose(new["diag"], old["diag"], rtol=3e-6, atol=1e-7)
 
 
+def test_step16_window_override_is_clamped_to_the_workspace_bound(tmp_path):
+    """CATPPO_STEP16_MAX_ROWS above kStep16MaxRows = 8192 (mlp_common.h): the workspace holds head partial rows for 16-row
+    tiles x 2 networks up to there, so the override gets the 8192-row window - 8192 rows take step16_kernel, 8208 rows take
+    exactly what they take with the switch off."""
+    spec = (45, 12, (512, 256, 128))
+    _, plan_at = _grad_of(tmp_path, "at", *spec, 8192, 8192, CATPPO_STEP16_MAX_ROWS="16384")
+    over, plan_over = _grad_of(tmp_path, "over", *spec, 8208, 8208, CATPPO_STEP16_MAX_ROWS="16384")
+    off, plan_off = _grad_of(tmp_path, "off", *spec, 8208, 8208, CATPPO_STEP16="0")
+    assert "step16_kernel" in plan_at and "[<= 8192 rows" in plan_at
+    assert "step16_kernel" not in plan_over and plan_over == plan_off
+    np.testing.assert_array_equal(over["grad"], off["grad"])
+    np.testing.assert_array_equal(over["diag"], off["diag"])
+
+
 def test_16_row_rollout_forward_equals_the_layerwise_path(tmp_path):
     """step16_fwd_kernel (16-row tiles, three layers + rollout heads in one launch; cleanrl/ppo.py:104-119) against the
     layer-wise rollout forward at the batch sizes below the 32-row kernels' window: hidden layers bit-identical by
