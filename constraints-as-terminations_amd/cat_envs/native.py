@@ -90,6 +90,27 @@ class RolloutStep(C.Structure):
         ("sim_src", C.c_void_p), ("sim_state", C.c_void_p), ("sim_row_bytes", C.c_int64)]
 
 
+SERVO_OFFSETS = ("joint_pos", "joint_vel", "joint_acc", "applied_torque", "projected_gravity", "root_pos", "command",
+                 "last_air_time", "first_contact", "forces", "reward", "hard_reset", "obs", "servo")
+SERVO_CONSTANTS = ("dt", "kp", "kd", "inertia", "tau_max", "action_scale", "vel_alpha", "tilt_beta", "tilt_max",
+                   "reward_scale", "foot_clearance", "contact_threshold", "stand_height", "height_drop", "floor_height",
+                   "min_height", "base_stiffness", "weight", "impact_gain", "init_noise", "standing_fraction",
+                   "command_deadzone")
+
+
+class ServoSim(C.Structure):
+    """catppo_servo_sim: argument block of the Solo12 servo surrogate step (field order = include/catppo.h)"""
+    _fields_ = ([("N", C.c_int64), ("env_offset", C.c_int64), ("state_in", C.c_void_p), ("state_out", C.c_void_p),
+                 ("row_stride", C.c_int64), ("row_floats", C.c_int32), ("obs_dim", C.c_int32), ("H", C.c_int32),
+                 ("B", C.c_int32)]
+                + [("off_" + n, C.c_int32) for n in SERVO_OFFSETS]
+                + [("action", C.c_void_p), ("reset", C.c_void_p), ("episode_length", C.c_void_p),
+                   ("max_episode_length", C.c_int64), ("decimation", C.c_int32), ("resample_steps", C.c_int32),
+                   ("init", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64),
+                   ("default_joint_pos", C.c_float * 12)]
+                + [(n, C.c_float) for n in SERVO_CONSTANTS])
+
+
 F32, F16, F64 = 0, 1, 2                 # CATPPO_F32 / _F16 / _F64
 SUM, MAX = 0, 1                         # CATPPO_SUM / _MAX
 LR_FIXED, LR_LINEAR, LR_KEEP = 0, 1, 2
@@ -178,6 +199,8 @@ _SIGNATURES = {
     "catppo_adv_moments_keyed": (C.c_int, [_vp, _vp, C.c_int, _vp, _i32, _i64, _i64, _vp, _vp, _vp]),
     # ---- ABI 0.4
     "catppo_set_grad_overlap": (C.c_int, [_vp, C.c_int]),
+    # ---- closed-loop Solo12 servo surrogate (one launch per env step)
+    "catppo_servo_sim_step": (C.c_int, [_vp, C.POINTER(ServoSim), _vp]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
@@ -680,6 +703,12 @@ class Native:
 
     def rollout_flush(self):
         self._ok(self.lib.catppo_rollout_defer_tail(self.h, -1, self._stream()))      # -1: flush, the mode stays
+
+    def servo_sim_step(self, desc: ServoSim):
+        """one control step (or, with ``desc.init``, the first state) of the Solo12 servo surrogate"""
+        rc = self.lib.catppo_servo_sim_step(self.h, C.byref(desc), self._stream())
+        if rc:
+            self._ok(rc)
 
     # ------------------------------------------------------------------ hipGraphs
     def debug_clip_branches(self, buf):

@@ -22,3 +22,18 @@ register(
     disable_env_checker=True,
     kwargs={"env_cfg_entry_point": f"{__name__}.cat_flat_env_cfg:Solo12FlatEnvCfg_PLAY", **_KW},
 )
+
+# the same task with the closed-loop servo surrogate as simulator (SyntheticCfg.kind = "servo")
+register(
+    id="Isaac-Velocity-CaT-Flat-Solo12-Servo-v0",
+    entry_point=CaTEnv,
+    disable_env_checker=True,
+    kwargs={"env_cfg_entry_point": f"{__name__}.cat_flat_env_cfg:Solo12ServoFlatEnvCfg", **_KW},
+)
+
+register(
+    id="Isaac-Velocity-CaT-Flat-Solo12-Servo-Play-v0",
+    entry_point=CaTEnv,
+    disable_env_checker=True,
+    kwargs={"env_cfg_entry_point": f"{__name__}.cat_flat_env_cfg:Solo12ServoFlatEnvCfg_PLAY", **_KW},
+)

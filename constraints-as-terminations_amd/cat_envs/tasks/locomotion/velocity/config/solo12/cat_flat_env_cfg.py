@@ -74,6 +74,15 @@ class TwoConstraintsCfg:
     contact = ConstraintsCfg.__dataclass_fields__["contact"].default_factory()
 
 
+@configclass
+class ThreeConstraintsCfg:
+    """the servo learning experiment: one soft safety, one hard safety and one style term.  (With all 13 terms and the
+    initial action noise of 1 some term is violated in 99.8 % of the env steps, the action-rate term alone in about 97 %.)"""
+    joint_torque = ConstraintsCfg.__dataclass_fields__["joint_torque"].default_factory()
+    foot_contact_force = ConstraintsCfg.__dataclass_fields__["foot_contact_force"].default_factory()
+    base_orientation = ConstraintsCfg.__dataclass_fields__["base_orientation"].default_factory()
+
+
 MAX_CURRICULUM_ITERATIONS = 1000
 
 
@@ -110,9 +119,16 @@ class TwoCurriculumCfg:
 
 
 @configclass
+class ThreeCurriculumCfg:
+    joint_torque = _anneal("joint_torque")
+    base_orientation = _anneal("base_orientation")
+
+
+@configclass
 class SceneCfg:
     num_envs: int = 4096
     env_spacing: float = 3.0
+    env_offset: int = 0          # global id of this process's first env (env-sharded runs of the servo simulator)
 
 
 @configclass
@@ -128,6 +144,31 @@ class SyntheticCfg:
     stream_steps: int = 48       # stream length (cycled)
     seed_offset: int = 1234
     exact_reset_sync: bool = False
+    # "stream": the pre-generated open-loop streams above.  "servo": the closed-loop Solo12 servo surrogate
+    # (csrc/servo_sim.hip), whose state follows the actions; its constants are the servo_* fields.
+    kind: str = "stream"
+    servo_kp: float = 3.0                # joint servo: tau = clamp(kp (q_des - q) - kd qd, +-tau_max), qdd = tau / inertia
+    servo_kd: float = 0.2
+    servo_inertia: float = 0.004
+    servo_tau_max: float = 3.5
+    servo_action_scale: float = 0.5      # q_des = default_joint_pos + action_scale * action
+    servo_vel_alpha: float = 0.5         # base velocity lag per control step
+    servo_tilt_beta: float = 0.3         # roll / pitch lag per control step
+    servo_tilt_max: float = 0.35         # |(roll, pitch)| beyond which the robot has rolled over (hard reset)
+    servo_reward_scale: float = 0.25     # s of the rational tracking rewards
+    servo_foot_clearance: float = 0.1    # foot clearance [m] per rad of knee flexion
+    servo_contact_threshold: float = 0.02
+    servo_stand_height: float = 0.25     # hip height of a leg at the default pose
+    servo_height_drop: float = 0.2       # hip height lost per rad of HFE offset
+    servo_floor_height: float = 0.05     # base height with no stance leg
+    servo_min_height: float = 0.12       # below it the base body touches the ground
+    servo_base_stiffness: float = 200.0  # base contact force [N] per m below servo_min_height
+    servo_weight: float = 25.0           # shared between the stance feet
+    servo_impact_gain: float = 8.0       # touch-down impulse [N] per rad/s of knee velocity
+    servo_init_noise: float = 0.1        # width of the uniform joint noise of an episode's first pose
+    servo_resample_steps: int = 250      # a new command every so many control steps
+    servo_standing_fraction: float = 0.02
+    servo_command_deadzone: float = 0.1
 
 
 @configclass
@@ -140,6 +181,18 @@ class Solo12FlatEnvCfg:
     decimation: int = 4
     episode_length_s: float = 10.0
     seed: int = 42
+
+
+@configclass
+class Solo12ServoFlatEnvCfg(Solo12FlatEnvCfg):
+    """the same task on the closed-loop servo surrogate: rewards, observations and constraints follow the actions"""
+    synthetic: SyntheticCfg = SyntheticCfg(kind="servo")
+
+
+@configclass
+class Solo12ServoFlatEnvCfg_PLAY(Solo12ServoFlatEnvCfg):
+    scene: SceneCfg = SceneCfg(num_envs=50, env_spacing=3.0)
+    curriculum: object = None
 
 
 @configclass

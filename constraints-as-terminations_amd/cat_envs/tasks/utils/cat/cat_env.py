@@ -11,6 +11,8 @@ and observations.  Every step the current slab of the stream is moved into persi
 buffers (what a simulator's ``scene.update`` does) - by one ``copy_`` in ``step``, inside the
 first launch of the fused ``step_into`` (``catppo_rollout_step.sim_src``) - and every manager
 reads views of those buffers, exactly like IsaacLab's ``scene[...]`` data objects.
+``SyntheticCfg.kind = "servo"`` selects ``Solo12ServoSim`` instead: a closed-loop surrogate whose next state is computed
+from the state buffers and the action by one kernel launch per step.
 
 No host synchronisation happens inside ``step``: resets are handled with masks
 (``exact_reset_sync=True`` restores the reference's ``nonzero()``-based control flow).
@@ -136,14 +138,87 @@ class SyntheticSolo12Sim:
             first_contact_f32=fc, compute_first_contact=lambda dt: fc > 0.5)
         self.scene = {"robot": robot, "contact_forces": sensor}
 
-    def advance(self) -> torch.Tensor:
-        """move to the next step of the stream WITHOUT touching the state buffer: returns the slab that holds the new
+    def advance(self, action=None) -> torch.Tensor:
+        """(``action`` is ignored: the stream is open loop)  move to the next step of the stream WITHOUT touching the state buffer: returns the slab that holds the new
         state (the fused env step hands it to catppo_rollout_pre, which copies it into ``cur`` inside its own launch)"""
         self.cursor = (self.cursor + 1) % self.S
         return self._slabs[self.cursor]
 
-    def step(self):
+    def step(self, action=None):
         self.cur.copy_(self.advance())                         # "scene.update": one contiguous slab
+
+
+class Solo12ServoSim(SyntheticSolo12Sim):
+    """Closed-loop stand-in simulator: the Solo12 servo surrogate (csrc/servo_sim.hip).
+
+    Same surface and packed layout as ``SyntheticSolo12Sim`` (plus 14 floats of private state per env, field ``servo``),
+    but nothing is pre-generated: ``advance(action)`` launches one kernel that maps (state buffer, action) to the next
+    state in one of two slabs and returns that slab; ``step(action)`` also copies it into the state buffer ``cur``.
+    ``episode_length`` / ``reset`` are the env's own buffers (the kernel reads which envs ended their episode in the
+    previous step and how far the others are); ``env_offset`` is the global id of env 0 of an env-sharded run."""
+
+    NX = 14
+
+    def __init__(self, num_envs: int, obs_dim: int, device, seed: int, syn, dt: float, decimation: int,
+                 max_episode_length: int, episode_length: torch.Tensor, reset: torch.Tensor, env_offset: int = 0):
+        self.N, self.D, self.device = num_envs, obs_dim, torch.device(device)
+        J, B, H = len(SOLO12_JOINTS), len(SOLO12_BODIES), self.H
+        self.J, self.B = J, B
+        fields = [("joint_pos", J), ("joint_vel", J), ("joint_acc", J), ("applied_torque", J),
+                  ("projected_gravity_b", 3), ("root_pos_w", 3), ("command", 3), ("last_air_time", B),
+                  ("first_contact", B), ("forces", H * B * 3), ("reward", 1), ("hard_reset", 1), ("obs", obs_dim),
+                  ("servo", self.NX)]
+        self.off, o = {}, 0
+        for name, w in fields:
+            self.off[name] = (o, w)
+            o += w
+        self.F = (o + 3) // 4 * 4
+        self.cur = torch.zeros(num_envs, self.F, device=self.device)
+        self._slabs = [torch.zeros(num_envs, self.F, device=self.device) for _ in range(2)]
+        self.cursor = -1
+        self.default_joint_pos = torch.tensor(DEFAULT_JOINT_POS, device=self.device).repeat(num_envs, 1).contiguous()
+        self._episode_length, self._reset = episode_length, reset       # referenced by the descriptor: keep alive
+        self._nat = native.get(self.device)
+        d = self._desc = native.ServoSim()
+        d.N, d.env_offset, d.row_stride, d.row_floats = num_envs, int(env_offset), self.F, self.F
+        d.obs_dim, d.H, d.B = obs_dim, H, B
+        names = {"projected_gravity": "projected_gravity_b", "root_pos": "root_pos_w"}
+        for n in native.SERVO_OFFSETS:
+            setattr(d, "off_" + n, self.off[names.get(n, n)][0])
+        d.state_in, d.reset, d.episode_length = self.cur.data_ptr(), reset.data_ptr(), episode_length.data_ptr()
+        d.max_episode_length, d.decimation = int(max_episode_length), int(decimation)
+        d.resample_steps, d.seed = int(syn.servo_resample_steps), int(seed) & (2 ** 64 - 1)
+        for j, v in enumerate(DEFAULT_JOINT_POS):
+            d.default_joint_pos[j] = v
+        d.dt = dt
+        for n in native.SERVO_CONSTANTS[1:]:
+            setattr(d, n, float(getattr(syn, "servo_" + n)))
+        self._build_scene()
+
+    def reset(self):
+        """the first state of episode 0 in the state buffer"""
+        d = self._desc
+        d.init, d.state_out, d.action = 1, self.cur.data_ptr(), None
+        self._nat.servo_sim_step(d)
+        d.init = 0
+
+    def advance(self, action: torch.Tensor) -> torch.Tensor:
+        if action is None:
+            raise ValueError("Solo12ServoSim.advance needs the action: the simulator is closed loop")
+        if action.dtype != torch.float32 or not action.is_contiguous():
+            action = action.float().contiguous()
+        self.cursor = (self.cursor + 1) % 2
+        slab = self._slabs[self.cursor]
+        d = self._desc
+        d.state_out, d.action = slab.data_ptr(), action.data_ptr()
+        self._nat.servo_sim_step(d)
+        return slab
+
+    def step(self, action=None):
+        if action is None:
+            self.reset()
+        else:
+            self.cur.copy_(self.advance(action))
 
 
 class _ActionManager:
@@ -211,9 +286,13 @@ class CaTEnv:
         syn = cfg.synthetic
         self.obs_dim, self.act_dim = int(syn.obs_dim), len(SOLO12_JOINTS)
         seed = int(getattr(cfg, "seed", 0) or 0)
-        self.sim = SyntheticSolo12Sim(self.num_envs, self.obs_dim, self.device, seed + int(syn.seed_offset),
-                                      int(syn.stream_steps))
-        self.scene = self.sim.scene
+        kind = str(getattr(syn, "kind", "stream"))
+        if kind not in ("stream", "servo"):
+            raise ValueError(f"SyntheticCfg.kind must be 'stream' or 'servo', got {kind!r}")
+        if kind == "stream":
+            self.sim = SyntheticSolo12Sim(self.num_envs, self.obs_dim, self.device, seed + int(syn.seed_offset),
+                                          int(syn.stream_steps))
+            self.scene = self.sim.scene
         self.exact_reset_sync = bool(getattr(syn, "exact_reset_sync", False))
         g = torch.Generator(device=self.device)
         g.manual_seed(seed + 17)
@@ -229,6 +308,13 @@ class CaTEnv:
         self.reset_buf = torch.zeros(self.num_envs, dtype=torch.bool, device=self.device)
         self.reset_terminated = torch.zeros_like(self.reset_buf)
         self.reset_time_outs = torch.zeros_like(self.reset_buf)
+        if kind == "servo":
+            # the closed-loop simulator reads the env's own episode counters and reset mask; an env-sharded run names the
+            # global id of its first env (cfg.scene.env_offset), so that the shards reproduce the single-process envs
+            self.sim = Solo12ServoSim(self.num_envs, self.obs_dim, self.device, seed + int(syn.seed_offset), syn,
+                                      cfg.sim.dt, cfg.decimation, self.max_episode_length, self.episode_length_buf,
+                                      self.reset_buf, env_offset=int(getattr(cfg.scene, "env_offset", 0) or 0))
+            self.scene = self.sim.scene
         self.obs_buf = {"policy": self.sim.view("obs")}
         self._rstep = None
         self._nat = None
@@ -266,7 +352,7 @@ class CaTEnv:
     def step(self, action: torch.Tensor):
         """reference: cat_env.py:42-147 with the physics loop replaced by the synthetic stream."""
         self._sim_step_counter += self.cfg.decimation
-        self.sim.step()
+        self.sim.step(action)
         self.common_step_counter += 1
         # -- one launch: process_action, episode_length_buf += 1 (:92), terminations (:95-97: hard resets
         #    from the stream, time-outs from the counter), reward_manager output -> reward_buf
@@ -314,9 +400,9 @@ class CaTEnv:
         # 5 us copy kernel and a launch boundary less per env step; CATPPO_FUSED_SIM_COPY=0 keeps the separate copy.
         slab = None
         if _FUSED_SIM_COPY:
-            slab = self.sim.advance()
+            slab = self.sim.advance(action)
         else:
-            self.sim.step()
+            self.sim.step(action)
         self.common_step_counter += 1
         st = self._rstep
         if st is None:

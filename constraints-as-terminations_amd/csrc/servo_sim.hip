@@ -1,0 +1,266 @@
+// Solo12 servo surrogate: one control step of the closed-loop stand-in simulator in one launch (DESIGN section 9,
+// include/catppo.h catppo_servo_sim).  tests/servo_twin.py restates this file statement by statement in numpy; the two
+// agree bit for bit, so every expression here is part of the model: fp32, no fused multiply-add (the library is built
+// with -ffp-contract=off), only + - * / sqrt min max abs compares and selects, reductions in a fixed order.
+//
+// 16 lanes per env, four envs per wave, 16 envs per workgroup.  Lane j < 12 is joint j (leg j / 3 in the order FL FR HL
+// HR, part j % 3 in the order HAA HFE KFE) and integrates it in registers; every lane carries foot (lane & 3) and the
+// whole base state redundantly (the joint sums are butterflies, all lanes end up with the same bits), so no lane waits
+// for another except through the shuffles.  The next row is assembled in LDS and leaves as coalesced 16-byte stores.
+//   tree16: x += xor-shuffle 8, 4, 2, 1 (width 16)     tree4 (feet): x += xor-shuffle 1, 2
+#include "common.h"
+#include "rng.h"
+
+namespace {
+
+constexpr int kEnvsPerBlock = 16, kThreads = 256, kJoints = 12, kPrivate = 14;
+constexpr uint32_t kTagCommand = 0x434D4453u, kTagInit = 0x494E4954u;   // "CMDS", "INIT": fourth Philox counter word
+
+// G[k][lane]: the fixed 5 x 12 matrix of the base model (rows vx, vy, wz, roll, pitch)
+__device__ __forceinline__ float gain(int k, int lane) {
+  if (lane >= kJoints) return 0.f;
+  const int leg = lane / 3, part = lane - 3 * leg;
+  const bool left = (leg & 1) == 0, front = leg < 2;
+  switch (k) {
+    case 0: return part == 1 ? 0.5f : 0.f;                          // vx: the four HFE offsets
+    case 1: return part == 0 ? 0.5f : 0.f;                          // vy: the four HAA offsets
+    case 2: return part == 0 ? (front ? 0.5f : -0.5f) : 0.f;        // wz: front against hind HAA
+    case 3: return part == 1 ? (left ? 0.3f : -0.3f) : 0.f;         // roll: left against right HFE
+    default: return part == 2 ? (front ? 0.3f : -0.3f) : 0.f;       // pitch: front against hind KFE
+  }
+}
+
+__device__ __forceinline__ float tree16(float x) {
+  x = x + __shfl_xor(x, 8, 16);
+  x = x + __shfl_xor(x, 4, 16);
+  x = x + __shfl_xor(x, 2, 16);
+  x = x + __shfl_xor(x, 1, 16);
+  return x;
+}
+
+__device__ __forceinline__ float tree4(float x) {
+  x = x + __shfl_xor(x, 1, 16);
+  x = x + __shfl_xor(x, 2, 16);
+  return x;
+}
+
+__device__ __forceinline__ float pick(const rng::u32x4& r, int w) { return rng::uniform_open(w == 0 ? r.x : w == 1 ? r.y : w == 2 ? r.z : r.w); }
+
+// command of (env, episode, resample index): uniform in the reference ranges, dead zone, standing fraction
+__device__ __forceinline__ void command_of(const catppo_servo_sim& d, uint32_t gid, uint32_t ep, uint32_t k, float c[3]) {
+  const rng::u32x4 r = rng::philox4x32_10(rng::u32x4{gid, ep, k, kTagCommand}, (uint32_t)d.seed, (uint32_t)(d.seed >> 32));
+  c[0] = -0.3f + rng::uniform_open(r.x) * 1.3f;
+  c[1] = -0.7f + rng::uniform_open(r.y) * 1.4f;
+  c[2] = -0.78f + rng::uniform_open(r.z) * 1.56f;
+  const float n2 = (c[0] * c[0] + c[1] * c[1]) + c[2] * c[2];
+  const bool keep = n2 > d.command_deadzone * d.command_deadzone && !(rng::uniform_open(r.w) < d.standing_fraction);
+  if (!keep) c[0] = c[1] = c[2] = 0.f;
+}
+
+// joint `lane` of the first pose of (env, episode): default + uniform noise; Philox block lane / 4, word lane % 4
+__device__ __forceinline__ float init_q(const catppo_servo_sim& d, uint32_t gid, uint32_t ep, int lane, float def) {
+  const rng::u32x4 r = rng::philox4x32_10(rng::u32x4{gid, ep, (uint32_t)(lane >> 2), kTagInit}, (uint32_t)d.seed,
+                                          (uint32_t)(d.seed >> 32));
+  return def + (pick(r, lane & 3) - 0.5f) * d.init_noise;
+}
+
+__global__ __launch_bounds__(kThreads) void servo_sim_kernel(const catppo_servo_sim d) {
+  extern __shared__ float4 lds4[];
+  float* lds = reinterpret_cast<float*>(lds4);
+  const int tid = threadIdx.x, lane = tid & 15, grp = tid >> 4;
+  const int F = d.row_floats, D = d.obs_dim, B3 = d.B * 3;
+  const int64_t e0 = (int64_t)blockIdx.x * kEnvsPerBlock;
+  // rows past N recompute the last env and are dropped at the store: no divergence around the shuffles and barriers
+  const int64_t e = e0 + grp < d.N ? e0 + grp : d.N - 1;
+  float* row = lds + grp * F;
+  for (int i = lane; i < F; i += 16) row[i] = 0.f;
+  __syncthreads();
+
+  const float* in = d.state_in + e * d.row_stride;
+  const float* xin = in + d.off_servo;
+  const bool init = d.init != 0;
+  const bool rst = init || d.reset[e] != 0;
+  const int64_t t = d.episode_length[e];
+  const uint32_t gid = (uint32_t)(d.env_offset + e);
+  const uint32_t ep = init ? 0u : (uint32_t)xin[13];
+  const bool isj = lane < kJoints;
+  const int f = lane & 3, foot_body = 4 * f + 4;
+  const float def = isj ? d.default_joint_pos[lane] : 0.f;
+  float cmd[3];
+  command_of(d, gid, ep, (uint32_t)(t / d.resample_steps), cmd);
+  float* obs = row + d.off_obs;
+
+  if (init) {
+    // the first state of episode 0: default pose + noise, at rest, four feet on the ground
+    const float q0 = isj ? init_q(d, gid, 0u, lane, def) : 0.f;
+    if (isj) {
+      row[d.off_joint_pos + lane] = q0;
+      if (9 + lane < D) obs[9 + lane] = q0 - def;
+    } else {
+      row[d.off_servo + 9 + f] = 1.f;
+    }
+    if (lane == 12) {
+      row[d.off_projected_gravity + 2] = -1.f;
+      row[d.off_root_pos + 2] = d.stand_height;
+      if (5 < D) obs[5] = -1.f;
+    }
+    if (lane == 13) {
+      for (int k = 0; k < 3; ++k) {
+        row[d.off_command + k] = cmd[k];
+        if (6 + k < D) obs[6 + k] = cmd[k];
+      }
+    }
+  } else {
+    // ---- the state this step starts from: the row, or the first state of episode `ep` re-derived from the counter
+    float q = 0.f, qd = 0.f, a = 0.f;
+    if (isj) {
+      q = rst ? init_q(d, gid, ep, lane, def) : in[d.off_joint_pos + lane];
+      qd = rst ? 0.f : in[d.off_joint_vel + lane];
+      a = d.action[e * kJoints + lane];
+    }
+    // ---- joints: `decimation` substeps of the clamped PD servo, semi-implicit Euler; the substep of largest |tau| is reported
+    const float q_des = def + d.action_scale * a;
+    float tau_w = 0.f;
+    for (int s = 0; s < d.decimation; ++s) {
+      float tau = d.kp * (q_des - q) - d.kd * qd;
+      tau = fminf(fmaxf(tau, -d.tau_max), d.tau_max);
+      const float qdd = tau / d.inertia;
+      qd = qd + qdd * d.dt;
+      q = q + qd * d.dt;
+      if (fabsf(tau) > fabsf(tau_w)) tau_w = tau;
+    }
+    const float dq = q - def;
+    // ---- base: five joint reductions, first-order lags
+    float red[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) red[k] = tree16(gain(k, lane) * dq);
+    const float step_dt = d.dt * (float)d.decimation;
+    float v[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const float v0 = rst ? 0.f : xin[k];
+      v[k] = v0 + d.vel_alpha * (red[k] - v0);
+    }
+    const float roll0 = rst ? 0.f : xin[3], pitch0 = rst ? 0.f : xin[4];
+    const float roll = roll0 + d.tilt_beta * (red[3] - roll0);
+    const float pitch = pitch0 + d.tilt_beta * (red[4] - pitch0);
+    const float ang[3] = {(roll - roll0) / step_dt, (pitch - pitch0) / step_dt, v[2]};
+    const float tilt2 = roll * roll + pitch * pitch;
+    const bool fallen = tilt2 > d.tilt_max * d.tilt_max;
+    const float nrm = sqrtf(tilt2 + 1.f);
+    float grav[3] = {(0.f - pitch) / nrm, roll / nrm, -1.f / nrm};
+    if (fallen) grav[0] = 0.f, grav[1] = 0.f, grav[2] = 1.f;
+    // ---- feet (every lane: foot lane & 3), base height, contact forces, air times
+    const float knee = __shfl(dq, 3 * f + 2, 16), knee_v = __shfl(qd, 3 * f + 2, 16), hfe = __shfl(dq, 3 * f + 1, 16);
+    const float con = (0.f - d.foot_clearance * knee) < d.contact_threshold ? 1.f : 0.f;
+    const float ncon = tree4(con);
+    const float zleg = d.stand_height - d.height_drop * fabsf(hfe);
+    const float nsafe = fmaxf(ncon, 1.f);
+    const float zsum = tree4(con * zleg);
+    const float z = ncon > 0.f ? zsum / nsafe : d.floor_height;
+    const float con_prev = rst ? 1.f : xin[9 + f];
+    const float air0 = rst ? 0.f : xin[5 + f];
+    const float last_air0 = rst ? 0.f : in[d.off_last_air_time + foot_body];
+    const bool touch = con > 0.f && !(con_prev > 0.f);
+    const float fz = con > 0.f ? d.weight / nsafe + (touch ? d.impact_gain * fabsf(knee_v) : 0.f) : 0.f;
+    const float last_air = touch ? air0 : last_air0;
+    const float air = con > 0.f ? 0.f : air0 + step_dt;
+    const float fbase = z < d.min_height ? d.base_stiffness * (d.min_height - z) : 0.f;
+    const float x0 = rst ? 0.f : in[d.off_root_pos], y0 = rst ? 0.f : in[d.off_root_pos + 1];
+    // ---- reward: rational stand-ins for the two exp tracking rewards
+    const float ex = cmd[0] - v[0], ey = cmd[1] - v[1], ew = cmd[2] - v[2];
+    const float reward = 1.f / (1.f + (ex * ex + ey * ey) / d.reward_scale) + 0.5f / (1.f + (ew * ew) / d.reward_scale);
+    // ---- does this step end the episode?  Then `obs` already shows the first state of the next one.
+    const bool ends = t + 1 >= d.max_episode_length || fallen;
+    const uint32_t ep_out = ep + (ends ? 1u : 0u);
+
+    // ---- assemble the next row
+    if (isj) {
+      row[d.off_joint_pos + lane] = q;
+      row[d.off_joint_vel + lane] = qd;
+      row[d.off_joint_acc + lane] = tau_w / d.inertia;
+      row[d.off_applied_torque + lane] = tau_w;
+      float o_q = dq, o_v = qd, o_a = a;
+      if (ends) o_q = init_q(d, gid, ep_out, lane, def) - def, o_v = 0.f, o_a = 0.f;
+      if (9 + lane < D) obs[9 + lane] = o_q;
+      if (21 + lane < D) obs[21 + lane] = o_v;
+      if (33 + lane < D) obs[33 + lane] = o_a;
+    } else {
+      row[d.off_last_air_time + foot_body] = last_air;
+      row[d.off_first_contact + foot_body] = touch ? 1.f : 0.f;
+      row[d.off_forces + foot_body * 3 + 2] = fz;
+      row[d.off_servo + 5 + f] = air;
+      row[d.off_servo + 9 + f] = con;
+    }
+    if (lane == 12) {
+      for (int k = 0; k < 3; ++k) row[d.off_projected_gravity + k] = grav[k];
+      row[d.off_root_pos] = x0 + v[0] * step_dt;
+      row[d.off_root_pos + 1] = y0 + v[1] * step_dt;
+      row[d.off_root_pos + 2] = z;
+      row[d.off_forces + 2] = fbase;                    // base_link is body 0
+    }
+    if (lane == 13) {
+      for (int k = 0; k < 3; ++k) row[d.off_command + k] = cmd[k];
+      row[d.off_reward] = reward;
+      row[d.off_hard_reset] = fallen ? 1.f : 0.f;
+    }
+    if (lane == 14) {
+      for (int k = 0; k < 3; ++k) row[d.off_servo + k] = v[k];
+      row[d.off_servo + 3] = roll;
+      row[d.off_servo + 4] = pitch;
+      row[d.off_servo + 13] = (float)ep_out;
+    }
+    if (lane == 15) {
+      float head[9] = {ang[0], ang[1], ang[2], grav[0], grav[1], grav[2], cmd[0], cmd[1], cmd[2]};
+      if (ends) {
+        float cn[3];
+        command_of(d, gid, ep_out, 0u, cn);
+        head[0] = head[1] = head[2] = head[3] = head[4] = 0.f;
+        head[5] = -1.f, head[6] = cn[0], head[7] = cn[1], head[8] = cn[2];
+      }
+      for (int k = 0; k < 9; ++k)
+        if (k < D) obs[k] = head[k];
+    }
+    // the force history moves one slot back (slot 0 is this step)
+    if (!rst)
+      for (int i = lane; i < (d.H - 1) * B3; i += 16) row[d.off_forces + B3 + i] = in[d.off_forces + i];
+  }
+  __syncthreads();
+
+  const int F4 = F >> 2;
+  const int64_t stride4 = d.row_stride >> 2;
+  float4* out4 = reinterpret_cast<float4*>(d.state_out);
+  for (int idx = tid; idx < kEnvsPerBlock * F4; idx += kThreads) {
+    const int r = idx / F4, c = idx - r * F4;
+    if (e0 + r < d.N) out4[(e0 + r) * stride4 + c] = lds4[idx];
+  }
+}
+
+}  // namespace
+
+extern "C" int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* desc, void* stream) {
+  CATPPO_CHECK_ARG(ctx, ctx != nullptr);
+  CATPPO_CHECK_ARG(ctx, desc != nullptr);
+  const catppo_servo_sim& d = *desc;
+  CATPPO_CHECK_ARG(ctx, d.N >= 1 && d.N < (int64_t(1) << 31) && d.env_offset >= 0 && d.env_offset + d.N < (int64_t(1) << 32));
+  CATPPO_CHECK_ARG(ctx, d.state_in && d.state_out && d.episode_length);
+  CATPPO_CHECK_ARG(ctx, d.init || (d.action && d.reset && d.state_in != d.state_out));
+  CATPPO_CHECK_ARG(ctx, d.row_floats >= 4 && d.row_floats % 4 == 0 && d.row_stride >= d.row_floats && d.row_stride % 4 == 0);
+  CATPPO_CHECK_ARG(ctx, ((uintptr_t)d.state_in % 16) == 0 && ((uintptr_t)d.state_out % 16) == 0);
+  CATPPO_CHECK_ARG(ctx, (size_t)d.row_floats * kEnvsPerBlock * sizeof(float) <= 64 * 1024);
+  CATPPO_CHECK_ARG(ctx, d.H >= 1 && d.B == 17 && d.obs_dim >= 0);
+  CATPPO_CHECK_ARG(ctx, d.decimation >= 1 && d.resample_steps >= 1 && d.max_episode_length >= 1);
+  CATPPO_CHECK_ARG(ctx, d.inertia > 0.f && d.dt > 0.f && d.reward_scale > 0.f);
+  // every field the kernel writes lies inside the row
+  const struct { int32_t off, width; } fields[] = {
+      {d.off_joint_pos, kJoints}, {d.off_joint_vel, kJoints}, {d.off_joint_acc, kJoints}, {d.off_applied_torque, kJoints},
+      {d.off_projected_gravity, 3}, {d.off_root_pos, 3}, {d.off_command, 3}, {d.off_last_air_time, d.B},
+      {d.off_first_contact, d.B}, {d.off_forces, d.H * d.B * 3}, {d.off_reward, 1}, {d.off_hard_reset, 1},
+      {d.off_obs, d.obs_dim}, {d.off_servo, kPrivate}};
+  for (const auto& fl : fields) CATPPO_CHECK_ARG(ctx, fl.off >= 0 && (int64_t)fl.off + fl.width <= d.row_floats);
+  const unsigned nblk = (unsigned)cdiv64(d.N, kEnvsPerBlock);
+  const size_t lds_bytes = (size_t)d.row_floats * kEnvsPerBlock * sizeof(float);
+  hipLaunchKernelGGL(servo_sim_kernel, dim3(nblk), dim3(kThreads), lds_bytes, static_cast<hipStream_t>(stream), d);
+  CATPPO_CHECK_LAUNCH(ctx);
+  return CATPPO_OK;
+}

@@ -626,6 +626,42 @@ int catppo_allgather(catppo_ctx* ctx, const void* send, void* recv, int64_t byte
  * one: see profiles/r5_grad_overlap_tail_world1.txt. */
 int catppo_set_grad_overlap(catppo_ctx* ctx, int on);      /* on: 0 | 1 | 2 set (CATPPO_OK), -1 query (0 / 1) */
 
+/* ---- Solo12 servo surrogate: a closed-loop stand-in simulator on the device -----------------------
+ * One control step of N envs in one launch: (state row, action, command) -> next state row, for the packed sim-state
+ * block the CaT env reads (cat_envs/tasks/utils/cat/cat_env.py, Solo12ServoSim).  Not physics: 12 clamped PD servo
+ * joints integrated over `decimation` substeps, base velocity / roll / pitch as first-order lags of fixed joint
+ * combinations, feet, contact forces and air times from the knee offsets, commands and first poses from Philox4x32-10
+ * keyed on (seed; global env id, episode, resample index).  fp32, unfused, only + - * / sqrt min max abs compares and
+ * selects, every reduction in a fixed order: tests/servo_twin.py restates it bit for bit in numpy.
+ * A row is `row_floats` floats (multiple of 4; rows 16-byte aligned, `row_stride` floats apart); off_* are float
+ * offsets into it.  off_servo names 14 floats of private state: v[3] | roll pitch | air[4] | contact[4] | episode.
+ * reset[i] != 0: env i ended its episode in the previous step; the kernel then starts from the first state of the
+ * episode in its row (re-derived from the counter) instead of the row.  A step that ends an episode (episode_length + 1
+ * >= max_episode_length, or the model's own hard_reset) writes the terminal state, but its `obs` already shows the
+ * first state of the next episode.  init != 0: write the first state of episode 0 (no integration; action and reset
+ * are not read).  state_in and state_out are different buffers unless init.  Enqueues on `stream`, never allocates,
+ * never synchronises. */
+typedef struct catppo_servo_sim {
+  int64_t N, env_offset;                 /* env_offset: global env id of row 0 (env-sharded runs) */
+  const float* state_in;
+  float* state_out;
+  int64_t row_stride;
+  int32_t row_floats, obs_dim, H, B;     /* force history depth, bodies (17: base + 4 x {shoulder, upper, lower, foot}) */
+  int32_t off_joint_pos, off_joint_vel, off_joint_acc, off_applied_torque, off_projected_gravity, off_root_pos,
+      off_command, off_last_air_time, off_first_contact, off_forces, off_reward, off_hard_reset, off_obs, off_servo;
+  const float* action;                   /* [N, 12] */
+  const uint8_t* reset;                  /* [N] */
+  const int64_t* episode_length;         /* [N], before this step's increment */
+  int64_t max_episode_length;
+  int32_t decimation, resample_steps, init, reserved;
+  uint64_t seed;
+  float default_joint_pos[12];
+  float dt, kp, kd, inertia, tau_max, action_scale, vel_alpha, tilt_beta, tilt_max, reward_scale, foot_clearance,
+      contact_threshold, stand_height, height_drop, floor_height, min_height, base_stiffness, weight, impact_gain,
+      init_noise, standing_fraction, command_deadzone;
+} catppo_servo_sim;
+int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* desc, void* stream);
+
 /* ---- test hook (ABI 0.6) ------------------------------------------------------------------------------------------
  * buf != NULL ([2][M] int32, device): the head / loss kernel of every following catppo_ppo_minibatch_* call writes the clip
  * branch each sample of the minibatch took - surrogate codes in [0, M) (ratio against 1 +- clip_coef), value-loss codes in

@@ -111,6 +111,11 @@ def _main(args_cli):
         # all-reduces combine distinct shards; rank 0 alone writes the run directory
         rank = int(os.environ.get("RANK", "0")) if int(os.environ.get("WORLD_SIZE", "1")) > 1 else 0
         env_cfg.seed = agent_cfg.seed + rank
+        if getattr(env_cfg.synthetic, "kind", "stream") == "servo":
+            # the servo simulator is keyed on (seed, global env id): one seed, and every rank names its first global env,
+            # so the shards are the rows of the single-process run
+            env_cfg.seed = agent_cfg.seed
+            env_cfg.scene.env_offset = rank * env_cfg.scene.num_envs
         env_cfg.sim.device = args_cli.device if args_cli.device is not None else env_cfg.sim.device
 
         log_root_path = os.path.abspath(os.path.join("logs", "clean_rl", agent_cfg.experiment_name))
