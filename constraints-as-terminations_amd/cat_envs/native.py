@@ -178,6 +178,8 @@ _SIGNATURES = {
                                      C.c_int, _vp]),
     "catppo_rollout_pre": (C.c_int, [_vp, C.POINTER(RolloutStep), _vp]),
     "catppo_rollout_post": (C.c_int, [_vp, C.POINTER(RolloutStep), _vp]),
+    # mode: 1 defer the post launch's tail | 2 = 1 + catppo_rollout_post only RECORDS the step and the next
+    # catppo_policy_step on the same rows carries it in one launch (anything else flushes) | 0 off + flush | -1 flush
     "catppo_rollout_defer_tail": (C.c_int, [_vp, C.c_int, _vp]),
     "catppo_graph_begin": (C.c_int, [_vp, _vp]),
     "catppo_graph_end": (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -696,10 +698,13 @@ class Native:
     def rollout_post(self, step: RolloutStep):
         self._ok(self.lib.catppo_rollout_post(self.h, C.byref(step), self._stream()))
 
-    def rollout_defer_tail(self, on: bool):
+    def rollout_defer_tail(self, on: bool, merge: bool = False):
         """ABI 0.5: while on, catppo_rollout_post leaves its one-workgroup tail (running maxima / normaliser state /
-        episode log) to the next catppo_rollout_pre launch; ``False`` switches it off AND runs a tail still pending"""
-        self._ok(self.lib.catppo_rollout_defer_tail(self.h, int(bool(on)), self._stream()))
+        episode log) to the next catppo_rollout_pre launch; ``False`` switches it off AND runs a tail still pending.
+        ``merge`` (mode 2): catppo_rollout_post also launches nothing itself - the next catppo_policy_step on the rows it
+        writes carries the step in its own launch; any other call of the family, ``rollout_flush`` and ``False`` run a step
+        still recorded as the launch it would have been.  Until then NO output of that step is current."""
+        self._ok(self.lib.catppo_rollout_defer_tail(self.h, (2 if merge else 1) if on else 0, self._stream()))
 
     def rollout_flush(self):
         self._ok(self.lib.catppo_rollout_defer_tail(self.h, -1, self._stream()))      # -1: flush, the mode stays

@@ -450,6 +450,12 @@ class PPOTrainer:
             dt = os.environ["CATPPO_ROLLOUT_DEFER_TAIL"] != "0"
         #: catppo_rollout_defer_tail around the env steps of a rollout (fused path only)
         self.defer_tail = True if dt is None else bool(dt)
+        #: the env step's post launch rides in the next policy forward (catppo_rollout_defer_tail mode 2; needs defer_tail;
+        #: cfg ``merge_rollout_step`` / CATPPO_STEP_MERGE=0: the separate launches, for A/B)
+        sm = getattr(c, "merge_rollout_step", None)
+        if os.environ.get("CATPPO_STEP_MERGE") is not None:
+            sm = os.environ["CATPPO_STEP_MERGE"] != "0"
+        self.step_merge = True if sm is None else bool(sm)
         # hipGraph replay of the update phase
         g = getattr(c, "graph_update", None)
         env_g = os.environ.get("CATPPO_GRAPH_UPDATE")
@@ -554,8 +560,11 @@ class PPOTrainer:
         # env step and by the logging below, not by the policy forward) rides in the next step's first launch instead of
         # standing between catppo_rollout_post and the forward (catppo_rollout_defer_tail; CATPPO_ROLLOUT_DEFER_TAIL=0: A/B)
         defer = self.sink is not None and self.defer_tail
+        # ... and the post launch itself rides in the next step's policy forward: catppo_rollout_post records the step,
+        # the catppo_policy_step below carries it (nothing of this loop reads a step's outputs in between); the last
+        # step of the rollout has no forward behind it and runs as its own launch from the flush in `finally`
         if defer:
-            nat.rollout_defer_tail(True)
+            nat.rollout_defer_tail(True, merge=self.step_merge)
         try:
             for step in range(T):
                 self.global_step += N * self.world

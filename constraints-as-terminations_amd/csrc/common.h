@@ -48,6 +48,17 @@ struct catppo_ctx {
   alignas(16) unsigned char post_tail_args[512] = {0};  // that launch's PostArgs
   double* post_rpart = nullptr;                         // its reset-statistics rows: owned (the workspace is reused by
   uint64_t post_rpart_bytes = 0;                        // whatever runs between the two launches), grown on demand
+  // catppo_rollout_defer_tail(ctx, 2): while step_merge is on, catppo_rollout_post launches nothing - it leaves its
+  // argument block here - and the next catppo_policy_step on the same rows takes ONE launch that normalises the
+  // observation tile on its way into the forward and does the post step's bookkeeping behind the value head
+  // (step_merge.h).  Whatever else comes first flushes: catppo_internal_flush_step launches rollout_post_kernel as before.
+  bool step_merge = false;
+  bool step_pending = false;
+  int step_nblk = 0;                                    // 32-env tiles of the recorded step
+  uint64_t step_lds = 0;                                // rollout_post_kernel's dynamic LDS for it (the flush)
+  void* step_stream = nullptr;
+  alignas(16) unsigned char step_args[512] = {0};       // PostArgs
+  alignas(16) unsigned char step_meta[192] = {0};       // TermMetaS
   // catppo_debug_clip_branches: when set, the head / loss kernels of the next gradient calls write the clip branch every
   // sample took ([2][M] int32: surrogate codes, then value-loss codes; 0 inside, 1 below, 2 above the clip range)
   int32_t* branch_out = nullptr;
@@ -129,6 +140,10 @@ int catppo_internal_launch_terms(catppo_ctx* ctx, const catppo_term_desc* desc, 
                                  const float* forces, int64_t forces_env_stride, int H, int B, const float* command,
                                  int command_ld, float* cstr, int K, float* colmax_partial, int* nblk_out,
                                  hipStream_t stream);
+
+// rollout.hip: a post step recorded under catppo_rollout_defer_tail(ctx, 2) that no merged forward picked up runs as
+// rollout_post_kernel on the stream it was recorded for; `stream` (the caller's) is ordered behind it
+int catppo_internal_flush_step(catppo_ctx* ctx, hipStream_t stream);
 
 // comm.hip: SUM all-reduce of n ranges [off[i], off[i] + cnt[i]) of one fp32 buffer as ONE grouped RCCL operation on `stream`
 int catppo_internal_allreduce_ranges(catppo_ctx* ctx, float* base, const int64_t* off, const int64_t* cnt, int n,

@@ -19,6 +19,7 @@
 #include "common.h"
 #include "gemm_f32.h"
 #include "rng.h"
+#include "rollout_post.h"
 
 #include <cassert>
 #include <cmath>
@@ -31,6 +32,7 @@ namespace {
 #include "mlp_loss.h"
 #include "mlp_wide.h"
 #include "step16.h"
+#include "step_merge.h"
 #include "mlp_step.h"
 #include "mlp_backward.h"
 #include "mlp_optim.h"
@@ -105,6 +107,15 @@ int policy_core(catppo_ctx* ctx, const catppo_mlp_shape* shape, const float* par
   call.action = action, call.logprob = logprob, call.value_out = value, call.value_f16 = (int)(value_dtype == CATPPO_F16);
   call.rng_state = rng_state, call.rng_step = rng_step, call.eps_out = eps_out, call.do_head = 1;
   const int nets = critic_only ? 1 : 2;
+  // a post step recorded by catppo_rollout_post (catppo_rollout_defer_tail mode 2): this forward carries it when it
+  // continues that step; otherwise the step runs as its own launch first, and the forward goes on as without it
+  if (ctx->step_pending) {
+    if (try_step_merge(ctx, shape, L, call, nets, s)) {
+      CATPPO_CHECK_LAUNCH(ctx);
+      return CATPPO_OK;
+    }
+    if (int rc = catppo_internal_flush_step(ctx, s)) return rc;
+  }
   // the one-launch forms in the order they are preferred; the first that applies launches
   if (!(rollout_step16(ctx, shape, L, call, nets, s) || rollout_rows_fwd(ctx, shape, L, call, nets, s) ||
         rollout_rows_wide(ctx, shape, L, call, nets, s) || rollout_fused_fwd(ctx, shape, L, call, nets, s)))

@@ -1,5 +1,6 @@
 // Fused rollout step: everything between the simulator's state update and the next policy forward in THREE launches
-// (two in rounds 2-3: the fold behind rollout_pre was a "last workgroup to arrive" tree inside that launch).
+// (two in rounds 2-3: the fold behind rollout_pre was a "last workgroup to arrive" tree inside that launch) - or in TWO
+// plus a share of the forward's launch, see the bracket below rollout_post.
 //
 // The reference spends, per env step, ~15 eager launches + one host sync PER constraint term
 // (cat/constraint_manager.py:39-82,213-229), six launches + a nonzero() sync in CaTEnv.step (cat/cat_env.py:92-121),
@@ -24,15 +25,23 @@
 //                 rollout-buffer rows and the normalised next-observation rows.  The last workgroup to finish writes
 //                 the new state back (nobody reads it any more in this launch) and folds the reset statistics.
 //
+//   [env step in three launches, catppo_rollout_defer_tail mode 2: catppo_rollout_post only records the step; the next
+//    catppo_policy_step carries it - step_fwd_kernel (step_merge.h, in mlp.hip) is rows_fwd_kernel<32> whose workgroups
+//    normalise their observation tile themselves (the derivation below, shared through rollout_post.h) and whose critic
+//    workgroup does rollout_post's per-tile work behind its value head.  rollout_post_kernel stays the form every other
+//    caller gets, and the launch a recorded step falls back to (catppo_internal_flush_step).]
+//
 // Arithmetic: identical statements in identical order to cat_step.hip / rms.hip / env_step.hip (this file is
 // compiled with -ffp-contract=off as well), so the termination masks stay bit-exact.
 #include "terms_eval.h"
 #include <cstdlib>
 #include "xwg.h"
+#include "rollout_post.h"
 
 namespace {
 
 using namespace terms;
+using namespace rpost;
 // -DROLLOUT_TL (tools/rollout_timeline.py): thread 0 of every workgroup stamps the wall clock (100 MHz) at the phase
 // boundaries of the two kernels into a buffer set through catppo_debug_rollout_tl().  Compiles away otherwise.
 #ifdef ROLLOUT_TL
@@ -43,8 +52,6 @@ __device__ unsigned long long* g_rtl;     // [2 kernels][1024 workgroups][16 sta
 #endif
 
 constexpr int kThreads = 256;
-constexpr int kPostRows = 32;
-constexpr int kMaxObsPerThread = 2;     // D <= 512
 
 struct PreArgs {
   int64_t N;
@@ -153,115 +160,6 @@ __device__ __forceinline__ void block_fold(const T* __restrict__ partial, int nr
   }
 }
 
-struct TermMetaS {
-  int32_t off[kMaxTerms + 1];
-  float dp[kMaxTerms];
-};
-
-struct PostArgs {
-  int64_t N;
-  int A, D, K, n_terms;
-  const float* cstr;
-  float min_p, tau, one_minus_tau;
-  int first_call;
-  float* rm;
-  float* reward;
-  const uint8_t* reset;
-  const uint8_t* time_outs;
-  float* cstr_prob;
-  float* dones;
-  float* ep_viol;
-  float* ep_prob;
-  float* probs;
-  int64_t* ep_len;
-  float* action;
-  float* prev_action;
-  int zero_action;
-  const float* log_prev;
-  float* log_out;
-  void* rewards_t;
-  void* dones_t1;
-  void* true_dones_t1;
-  int planes_f16;
-  const float* obs_raw;
-  int64_t obs_ld;
-  float* obs_mean;
-  float* obs_var;
-  float* obs_count;
-  float obs_eps;
-  double obs_n;
-  float* obs_out;
-  int64_t obs_out_ld;
-  const float* x_colmax;
-  const double* x_sums;
-  int x_records;          // > 1: x_colmax / x_sums point at record 0 of `x_records` gathered records, x_stride bytes apart
-  int64_t x_stride;
-  double* reset_part;     // [grid][2 n_terms + 1]: per term {sum violation, sum probability}, then the reset count
-  unsigned int* ticket;
-  int defer;              // 1: no tail in this launch (post_tail_deferred runs it from a later launch)
-  uint32_t d_magic, k_magic;   // catppo_div_magic(D), (K)
-};
-static_assert(sizeof(PostArgs) <= sizeof(catppo_ctx::post_tail_args), "catppo_ctx::post_tail_args too small");
-
-__device__ __forceinline__ void store_plane(void* p, int64_t i, float v, int f16) {
-  if (f16) reinterpret_cast<_Float16*>(p)[i] = (_Float16)v;
-  else reinterpret_cast<float*>(p)[i] = v;
-}
-
-// new running maximum of column c (constraint_manager.py:58-61) from the exchange record(s) and the state of the previous
-// step (every workgroup of rollout_post_kernel, into LDS; the last one to arrive - or the deferred tail - writes it back).
-// Split into the loads and the arithmetic so that rollout_post_kernel can request the operands up front.
-__device__ __forceinline__ float load_colmax(const PostArgs& a, int c) {
-  float m = a.x_colmax[c];
-  for (int w = 1; w < a.x_records; ++w)     // gathered records of the other ranks: MAX is exact and order independent
-    m = nanmax(m, reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.x_colmax) + w * a.x_stride)[c]);
-  return m;
-}
-__device__ __forceinline__ float running_max_from(const PostArgs& a, float m, float rm_c) {
-  if (a.first_call) return m;
-  const float x = rm_c * a.tau;              // rm.mul_(tau)
-  const float y = a.one_minus_tau * m;       // (1-tau) * cmax
-  return x + y;                              // .add_()
-}
-__device__ __forceinline__ float derive_running_max(const PostArgs& a, int c) {
-  return running_max_from(a, load_colmax(a, c), a.first_call ? 0.0f : a.rm[c]);
-}
-// merged observation normaliser of column c (cleanrl/ppo.py:48-62, the op order of rms.hip): new mean / variance
-__device__ __forceinline__ void load_sums(const PostArgs& a, int c, double* sx_out, double* sxx_out) {
-  const int D = a.D;
-  double sx = a.x_sums[c], sxx = a.x_sums[D + c];
-  for (int w = 1; w < a.x_records; ++w) {   // rank order: the same sums on every rank
-    const double* xs = reinterpret_cast<const double*>(reinterpret_cast<const char*>(a.x_sums) + w * a.x_stride);
-    sx += xs[c], sxx += xs[D + c];
-  }
-  *sx_out = sx, *sxx_out = sxx;
-}
-__device__ __forceinline__ void normaliser_from(const PostArgs& a, double sx, double sxx, float mean, float var, float cnt,
-                                                float nf, float tot, float* new_mean, float* new_var) {
-  const double m = sx / a.obs_n;
-  double v = sxx / a.obs_n - m * m;
-  if (v < 0.0) v = 0.0;
-  const float bm = (float)m, bv = (float)v;
-  const float delta = bm - mean;
-  float t = delta * nf;
-  t = t / tot;
-  *new_mean = mean + t;
-  const float m_a = var * cnt;
-  const float m_b = bv * nf;
-  float d2 = delta * delta;
-  d2 = d2 * cnt;
-  d2 = d2 * nf;
-  d2 = d2 / tot;
-  float M2 = m_a + m_b;
-  M2 = M2 + d2;
-  *new_var = M2 / tot;
-}
-__device__ __forceinline__ void derive_normaliser(const PostArgs& a, int c, float cnt, float nf, float tot, float* new_mean,
-                                                  float* new_var) {
-  double sx, sxx;
-  load_sums(a, c, &sx, &sxx);
-  normaliser_from(a, sx, sxx, a.obs_mean[c], a.obs_var[c], cnt, nf, tot, new_mean, new_var);
-}
 
 // Reset statistics of a post launch: its `nblk` partial rows {sum violation, sum probability per term | number of envs
 // that reset} folded in ONE pass (the rows come from the coherence point, ~3.5 us per round trip - the count used to be
@@ -834,6 +732,7 @@ extern "C" int catppo_debug_rollout_tl(void* buf) {     // timeline builds only:
 
 inline uint64_t xchg_sum_offset(int K) { return ((uint64_t)K * sizeof(float) + 15) / 16 * 16; }
 
+int order_behind(catppo_ctx* ctx, hipStream_t stream, hipStream_t ts, const char* what);
 // a deferred post tail that no rollout_pre launch picked up: one small launch of its own
 int flush_post_tail(catppo_ctx* ctx, hipStream_t stream) {
   if (!ctx->post_tail_pending) return CATPPO_OK;
@@ -846,11 +745,31 @@ int flush_post_tail(catppo_ctx* ctx, hipStream_t stream) {
   CATPPO_CHECK_LAUNCH(ctx);
   //  a caller on ANOTHER stream is about to enqueue work that reads what the tail publishes (running maxima,
   // normaliser state): order that stream behind the tail instead of leaving it to the caller
-  if (stream != ts) {
-    if (ctx->ev_tail == nullptr && hipEventCreateWithFlags(&ctx->ev_tail, hipEventDisableTiming) != hipSuccess)
-      return catppo_fail(ctx, CATPPO_E_HIP, "flush_post_tail: hipEventCreate failed");
-    if (hipEventRecord(ctx->ev_tail, ts) != hipSuccess || hipStreamWaitEvent(stream, ctx->ev_tail, 0) != hipSuccess)
-      return catppo_fail(ctx, CATPPO_E_HIP, "flush_post_tail: cannot order the calling stream behind the deferred tail");
+  return order_behind(ctx, stream, ts, "flush_post_tail");
+}
+
+// order `stream` behind whatever was last enqueued on `ts` (another stream of the same context)
+int order_behind(catppo_ctx* ctx, hipStream_t stream, hipStream_t ts, const char* what) {
+  if (stream == ts) return CATPPO_OK;
+  if (ctx->ev_tail == nullptr && hipEventCreateWithFlags(&ctx->ev_tail, hipEventDisableTiming) != hipSuccess)
+    return catppo_fail(ctx, CATPPO_E_HIP, "%s: hipEventCreate failed", what);
+  if (hipEventRecord(ctx->ev_tail, ts) != hipSuccess || hipStreamWaitEvent(stream, ctx->ev_tail, 0) != hipSuccess)
+    return catppo_fail(ctx, CATPPO_E_HIP, "%s: cannot order the calling stream behind the pending launch", what);
+  return CATPPO_OK;
+}
+
+// the post launch of a step, and the registration of its deferred tail
+int launch_post(catppo_ctx* ctx, const PostArgs& p, const TermMetaS& meta, int nblk, size_t lds, hipStream_t stream) {
+  if (lds > 64 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(rollout_post_kernel),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(rollout_post_kernel, dim3(nblk), dim3(kThreads), lds, stream, p, meta);
+  CATPPO_CHECK_LAUNCH(ctx);
+  if (p.defer) {
+    memcpy(ctx->post_tail_args, &p, sizeof(p));
+    ctx->post_tail_nblk = nblk;
+    ctx->post_tail_stream = stream;
+    ctx->post_tail_pending = true;
   }
   return CATPPO_OK;
 }
@@ -867,6 +786,20 @@ int check_step(catppo_ctx* ctx, const catppo_rollout_step* a, const char* fn) {
 
 }  // namespace
 
+int catppo_internal_flush_step(catppo_ctx* ctx, hipStream_t stream) {
+  if (!ctx->step_pending) return CATPPO_OK;
+  PostArgs p;
+  TermMetaS meta;
+  memcpy(&p, ctx->step_args, sizeof(p));
+  memcpy(&meta, ctx->step_meta, sizeof(meta));
+  ctx->step_pending = false;
+  hipStream_t ts = static_cast<hipStream_t>(ctx->step_stream);
+  if (int rc = launch_post(ctx, p, meta, ctx->step_nblk, (size_t)ctx->step_lds, ts)) return rc;
+  catppo_plan_note(ctx, "env step, %lld rows: rollout_post_kernel as a launch of its own [the recorded post step was not "
+                   "followed by a policy step the merged launch takes]", (long long)p.N);
+  return order_behind(ctx, stream, ts, "catppo_internal_flush_step");
+}
+
 extern "C" uint64_t catppo_rollout_step_sizeof(void) { return sizeof(catppo_rollout_step); }
 // size of one exchange record and the offset of its fp64 sums (ABI 0.6: one call for the two of ABI 0.5)
 extern "C" int catppo_rollout_xchg_layout(int K, int D, uint64_t* bytes, uint64_t* sum_offset) {
@@ -878,6 +811,7 @@ extern "C" int catppo_rollout_xchg_layout(int K, int D, uint64_t* bytes, uint64_
 
 extern "C" int catppo_rollout_pre(catppo_ctx* ctx, const catppo_rollout_step* a, void* stream) {
   if (int rc = check_step(ctx, a, __func__)) return rc;
+  if (int rc = catppo_internal_flush_step(ctx, static_cast<hipStream_t>(stream))) return rc;
   CATPPO_CHECK_ARG(ctx, a->action_in && a->action && a->prev_action && a->episode_length && a->hard_reset &&
                             a->reward_src && a->time_outs && a->terminated && a->reset && a->reward && a->desc && a->cstr);
   CATPPO_CHECK_ARG(ctx, a->obs_raw == nullptr || (a->D >= 1 && a->obs_ld >= a->D));
@@ -1002,6 +936,7 @@ extern "C" int catppo_rollout_pre(catppo_ctx* ctx, const catppo_rollout_step* a,
 
 extern "C" int catppo_rollout_post(catppo_ctx* ctx, const catppo_rollout_step* a, void* stream) {
   if (int rc = check_step(ctx, a, __func__)) return rc;
+  if (int rc = catppo_internal_flush_step(ctx, static_cast<hipStream_t>(stream))) return rc;
   CATPPO_CHECK_ARG(ctx, a->cstr && a->term_off && a->term_dp && a->rm && a->cstr_prob && a->ep_viol && a->ep_prob &&
                             a->reward && a->reset && a->time_outs && a->episode_length);
   CATPPO_CHECK_ARG(ctx, a->rewards_t == nullptr || (a->dones_t1 && a->true_dones_t1));
@@ -1065,24 +1000,27 @@ extern "C" int catppo_rollout_post(catppo_ctx* ctx, const catppo_rollout_step* a
   p.ticket = ctx->tickets + catppo_ctx::kTicketPost;
   p.defer = defer ? 1 : 0;
   p.d_magic = catppo_div_magic((uint32_t)(D > 0 ? D : 1)), p.k_magic = catppo_div_magic((uint32_t)K);
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(rollout_post_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(rollout_post_kernel, dim3(nblk), dim3(kThreads), lds, static_cast<hipStream_t>(stream), p, meta);
-  CATPPO_CHECK_LAUNCH(ctx);
-  if (defer) {
-    memcpy(ctx->post_tail_args, &p, sizeof(p));
-    ctx->post_tail_nblk = nblk;
-    ctx->post_tail_stream = stream;
-    ctx->post_tail_pending = true;
+  // merge mode: nothing is launched here.  The next catppo_policy_step on these rows carries the step (step_merge.h);
+  // anything else that comes first launches it through catppo_internal_flush_step
+  if (defer && ctx->step_merge && a->obs_raw != nullptr) {
+    memcpy(ctx->step_args, &p, sizeof(p));
+    memcpy(ctx->step_meta, &meta, sizeof(meta));
+    ctx->step_nblk = nblk;
+    ctx->step_lds = lds;
+    ctx->step_stream = stream;
+    ctx->step_pending = true;
+    return CATPPO_OK;
   }
-  return CATPPO_OK;
+  return launch_post(ctx, p, meta, nblk, lds, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int catppo_rollout_defer_tail(catppo_ctx* ctx, int on, void* stream) {
   if (!ctx) return CATPPO_E_ARG;
-  CATPPO_CHECK_ARG(ctx, on == 0 || on == 1 || on == -1);
+  CATPPO_CHECK_ARG(ctx, on == 0 || on == 1 || on == 2 || on == -1);
+  // a recorded post step comes first, whatever the call asks for: the tail it leaves is then flushed like any other
+  if (int rc = catppo_internal_flush_step(ctx, static_cast<hipStream_t>(stream))) return rc;
   if (on == -1) return flush_post_tail(ctx, static_cast<hipStream_t>(stream));      // flush only, the mode stays (ABI 0.5: catppo_rollout_flush)
   ctx->rollout_defer = on != 0;
+  ctx->step_merge = on == 2;
   return on ? CATPPO_OK : flush_post_tail(ctx, static_cast<hipStream_t>(stream));
 }

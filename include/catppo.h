@@ -550,8 +550,24 @@ int catppo_rollout_post(catppo_ctx* ctx, const catppo_rollout_step* a, void* str
  * tail and its reset-statistics rows belong to the context; a call that flushes the tail from ANOTHER stream is ordered
  * behind the tail's launch by an event (round 6).  Reference: the statistics concerned are
  * ConstraintManager's running maxima (cat/constraint_manager.py:58-61), RunningMeanStd's state (cleanrl/ppo.py:48-62)
- * and the episode log of ConstraintManager.reset (cat/constraint_manager.py:190-211). */
-int catppo_rollout_defer_tail(catppo_ctx* ctx, int on, void* stream);    /* on: 1 | 0 (= off + flush) | -1 (flush only) */
+ * and the episode log of ConstraintManager.reset (cat/constraint_manager.py:190-211).
+ *
+ * on = 2 (env step in three launches): deferred tail as with 1, and catppo_rollout_post itself launches NOTHING - it
+ * records its argument block in the context (a step with obs_raw; the caller's all-reduce / all-gather of the exchange
+ * record has been enqueued by then, as before).  The next catppo_policy_step of that context carries the step in its
+ * own launch (step_fwd_kernel: every workgroup of the 32-row forward normalises its observation rows from the raw rows
+ * straight into its LDS tile, the critic workgroup of a tile does the step's bookkeeping behind its value head) when it
+ * continues the step: same stream, same N, x == obs_out with obs_out_ld == the padded observation width, a shape and a
+ * row count the 32-row forward rows_fwd_kernel<32> takes (fp32, every hidden layer 256 wide, act_dim < 16, 2049..4096
+ * rows unless the window is overridden), eps / state noise or the critic-only form (no given_action), K <= 64 constraint
+ * columns, D <= 128, and head outputs that are none of the step's buffers.  Anything else - another size or shape,
+ * bf16 or wide heads, given_action, another catppo_rollout_pre / _post, any catppo_rollout_defer_tail call (-1 included)
+ * - first launches the recorded step as the rollout_post_kernel launch it would have been, on the stream it was recorded
+ * for, and then proceeds as without it.  CONTRACT while on = 2: NO output of a step (obs_out, reward, dones, the
+ * rollout-buffer planes, episode statistics; and, as with 1, rm / normaliser state / log_out) is valid before the next
+ * catppo_policy_step or one of those calls; nothing the step reads may be written in between.  Results are bit-identical
+ * in every mode.  PPOTrainer.rollout arms it beside the tail deferral and flushes in its `finally`. */
+int catppo_rollout_defer_tail(catppo_ctx* ctx, int on, void* stream);    /* on: 1 | 2 | 0 (= off + flush) | -1 (flush only) */
 
 /* ---- rl_games front end: episode bookkeeping with float dones ---------------------------------------
  * One env step of CaTA2CAgent.play_steps' bookkeeping (rl_games/cat_common.py:71-92), one launch, no host sync:
