@@ -67,30 +67,84 @@ def _q(t: torch.Tensor) -> torch.Tensor:
     return t.to(torch.bfloat16).to(torch.float32)
 
 
+def _mm(a: torch.Tensor, b: torch.Tensor, accumulate) -> torch.Tensor:
+    """a @ b with products and sums in ``accumulate``, rounded once to fp32"""
+    if accumulate == torch.float32:
+        return a @ b
+    return (a.to(accumulate) @ b.to(accumulate)).float()
+
+
 class _BF16OperandLinear(torch.autograd.Function):
     """Restatement of the build's bf16 mode (catppo_mlp_shape.mfma_bf16, BASELINE config 5 - NOT a reference
     code path): every hidden-layer GEMM rounds both operands to bf16 (RNE) and accumulates in fp32, in the
-    forward (x.w^T), the data gradient (gy.w) and the weight gradient (gy^T.x); bias and its gradient fp32."""
+    forward (x.w^T), the data gradient (gy.w) and the weight gradient (gy^T.x); bias and its gradient fp32.
+
+    ``accumulate=torch.float64``: the same bf16 operands, products and sums (bias, and the bias gradient's column sum,
+    included) in fp64, the result rounded ONCE to fp32 - the order-free value every fp32 summation order of the device
+    or of this oracle is a realisation of.  The operand rounding is unchanged: a bf16 x bf16 product is exact in fp32
+    and in fp64 alike."""
 
     @staticmethod
-    def forward(ctx, x, w, b):
+    def forward(ctx, x, w, b, accumulate=torch.float32):
         ctx.save_for_backward(x, w)
-        return _q(x) @ _q(w).t() + b
+        ctx.accumulate = accumulate
+        if accumulate == torch.float32:
+            return _q(x) @ _q(w).t() + b
+        return (_q(x).to(accumulate) @ _q(w).to(accumulate).t() + b.to(accumulate)).float()
 
     @staticmethod
     def backward(ctx, gy):
         x, w = ctx.saved_tensors
-        return _q(gy) @ _q(w), _q(gy).t() @ _q(x), gy.sum(0)
+        acc = ctx.accumulate
+        gb = gy.sum(0) if acc == torch.float32 else gy.to(acc).sum(0).float()
+        return _mm(_q(gy), _q(w), acc), _mm(_q(gy).t(), _q(x), acc), gb, None
 
 
-def mlp_forward(x: torch.Tensor, layers, bf16_hidden: bool = False) -> torch.Tensor:
-    """layers = [(W(out,in), b), ...]; ELU(alpha=1) between, none after the last."""
+class _StoredELU(torch.autograd.Function):
+    """ELU of a hidden layer of the bf16-STORED form of the bf16 mode (csrc/gemm_f32.h, comment block "bf16-STORED
+    operands"): activations and dZ are rounded to bf16 where they are PRODUCED instead of where a GEMM consumes them.
+      forward:  H = elu(z), stored as bf16 - except the last hidden layer, whose activations stay fp32 (the head reads
+                fp32; in the optimiser step they never leave the CU);
+      backward: dZ = dH * elu'(H) with elu'(H) = 1 (H > 0) | H + 1 taken from the activation AS STORED (rounded, but for
+                the last hidden layer), and dZ itself stored as bf16 for every layer - so the bias gradient that
+                _BF16OperandLinear.backward takes from it is the column sum of the ROUNDED dZ.
+    The GEMM operands are the same bf16 values as in the rounded-at-use form (rounding is idempotent): the forward is
+    unchanged, the backward differs through elu' and the bias sums."""
+
+    @staticmethod
+    def forward(ctx, z, round_out):
+        h = F.elu(z)
+        if round_out:
+            h = _q(h)
+        ctx.save_for_backward(h)
+        return h
+
+    @staticmethod
+    def backward(ctx, gh):
+        (h,) = ctx.saved_tensors
+        return _q(gh * torch.where(h > 0, torch.ones_like(h), h + 1.0)), None
+
+
+def mlp_forward(x: torch.Tensor, layers, bf16_hidden: bool = False, accumulate=torch.float32,
+                bf16_stored: bool = False) -> torch.Tensor:
+    """layers = [(W(out,in), b), ...]; ELU(alpha=1) between, none after the last.
+
+    ``accumulate`` and ``bf16_stored`` restate the bf16 mode further (see _BF16OperandLinear, _StoredELU) and change
+    nothing without ``bf16_hidden``.  With float64 accumulation the fp32-operand output layer sums in fp64 too."""
     h = x
+    wide = bf16_hidden and accumulate != torch.float32
+    n_hidden = len(layers) - 1
     for i, (w, b) in enumerate(layers):
         last = i + 1 == len(layers)
-        h = _BF16OperandLinear.apply(h, w, b) if (bf16_hidden and not last) else F.linear(h, w, b)
-        if not last:
-            h = F.elu(h)
+        if bf16_hidden and not last:
+            h = _BF16OperandLinear.apply(h, w, b, accumulate)
+            h = _StoredELU.apply(h, i + 1 < n_hidden) if bf16_stored else F.elu(h)
+        elif wide:
+            h = F.linear(h.to(accumulate), w.to(accumulate), b.to(accumulate)).float()
+        else:
+            h = F.linear(h, w, b)
+            if not last:
+                h = F.elu(h)
     return h
 
 
@@ -107,8 +161,10 @@ def gaussian_logp_entropy(mean, logstd, action):
 class AgentOracle:
     """Parameters as plain tensors under the reference's 23 state_dict keys."""
 
-    def __init__(self, obs_dim: int, act_dim: int, hidden=(512, 256, 128), seed: int = 0, bf16_hidden: bool = False):
+    def __init__(self, obs_dim: int, act_dim: int, hidden=(512, 256, 128), seed: int = 0, bf16_hidden: bool = False,
+                 accumulate=torch.float32, bf16_stored: bool = False):
         self.bf16_hidden = bool(bf16_hidden)
+        self.accumulate, self.bf16_stored = accumulate, bool(bf16_stored)     # of the bf16 mode only (mlp_forward)
         g = torch.Generator().manual_seed(seed)
         dims = [obs_dim, *hidden]
         self.p: dict[str, torch.Tensor] = {"actor_logstd": torch.zeros(1, act_dim)}
@@ -154,10 +210,10 @@ class AgentOracle:
         return sd
 
     def get_value(self, x):
-        return mlp_forward(x, self.layers("critic"), self.bf16_hidden)
+        return mlp_forward(x, self.layers("critic"), self.bf16_hidden, self.accumulate, self.bf16_stored)
 
     def get_action_and_value(self, x, action=None, eps=None, deterministic=False):
-        mean = mlp_forward(x, self.layers("actor_mean"), self.bf16_hidden)
+        mean = mlp_forward(x, self.layers("actor_mean"), self.bf16_hidden, self.accumulate, self.bf16_stored)
         if action is None:
             if deterministic:
                 action = mean
