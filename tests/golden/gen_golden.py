@@ -112,6 +112,28 @@ def gen_cat(tag, seed, n_envs, terms, max_ps, steps, sub=1, tau=0.95, min_p=0.0,
          **extras_rec)
 
 
+def gen_cat_nan_inf():
+    """the reference's own ``CaT`` on a step with one NaN and one +Inf constraint value (inputs: tests/stat_refs.cat_case):
+    what torch's max / clamp / masked assignment make of them, for tests/test_stat_refs.py to hold the oracle against"""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))      # stat_refs imports the oracle package
+    import stat_refs
+    cm, _, _, _ = R.load_ref_cat()
+    K, N, nt = 100, 33, 7
+    widths, max_p, steps = stat_refs.cat_case(K, N, nt, nan_inf=True)
+    off = np.concatenate([[0], np.cumsum(widths)])
+    cat = cm.CaT(tau=stat_refs.CAT_TAU, min_p=stat_refs.CAT_MIN_P)
+    rec = {"running_maxes": [], "cstr_prob": [], "probs": []}
+    for s in steps:
+        cat.reset()
+        for i in range(nt):
+            cat.add(f"t{i}", torch.from_numpy(s["cstr"][:, off[i]:off[i + 1]].copy()), max_p[i])
+        rec["running_maxes"].append(t2n(cat.get_running_maxes())[0].copy())
+        rec["cstr_prob"].append(t2n(cat.get_probs()).copy())
+        rec["probs"].append(np.concatenate([t2n(cat.probs[f"t{i}"]) for i in range(nt)], 1))
+    save("cat_nan_inf", K=K, N=N, n_terms=nt, widths=np.array(widths), max_p=np.array(max_p, np.float64),
+         cstr=np.stack([s["cstr"] for s in steps]), **{k: np.stack(v) for k, v in rec.items()})
+
+
 def gen_curriculum():
     _, _, _, cu = R.load_ref_cat()
     env = types.SimpleNamespace(common_step_counter=0)
@@ -661,12 +683,15 @@ def main():
         return gen_rlg_play_steps()
     if sys.argv[1:] == ["terms_scale"]:
         return gen_terms_scale()
+    if sys.argv[1:] == ["cat_nan_inf"]:
+        return gen_cat_nan_inf()
     print("CaT streams")
     gen_cat("small", 101, 7, S.CAT_TERMS_SMALL, [0.25, 1.0, 0.25, 1.0, 0.5], 16,
             curriculum_at=8, reset_at={5, 11})
     gen_cat("minp", 102, 33, S.CAT_TERMS_SMALL, [0.25, 1.0, 0.25, 1.0, 0.5], 6, min_p=0.05, tau=0.9)
     gen_cat("solo64", 103, 64, S.CAT_TERMS_SOLO12, S.CAT_MAXP_SOLO12, 16, curriculum_at=8, reset_at={7})
     gen_cat("solo4096", 104, 4096, S.CAT_TERMS_SOLO12, S.CAT_MAXP_SOLO12, 8, sub=16, curriculum_at=4)
+    gen_cat_nan_inf()
     gen_curriculum()
     print("terms / envfinish / rms / agent")
     gen_terms()
