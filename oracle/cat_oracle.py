@@ -122,10 +122,13 @@ def _torch_like_mean(x: np.ndarray):
 
 
 def env_finish(reward, cstr_prob, reset_mask):
-    """cat_env.py:102-107,118-121:  r = max(fl(r*fl(1-p)), 0);  dones = p;  dones[reset] = 1."""
+    """cat_env.py:102-107,118-121:  r = clip(fl(r*fl(1-p)), min=0);  dones = p;  dones[reset] = 1.
+    torch.clip keeps a negative zero (a negative raw reward times 1 - p = 0) and a NaN; np.maximum would turn the
+    former into +0."""
     reward = np.asarray(reward, F32)
     p = np.asarray(cstr_prob, F32)
-    r = np.maximum((reward * (F32(1.0) - p).astype(F32)).astype(F32), F32(0.0))
+    r = (reward * (F32(1.0) - p).astype(F32)).astype(F32)
+    r = np.where(r < F32(0.0), F32(0.0), r)
     dones = p.copy()
     dones[np.asarray(reset_mask, bool)] = F32(1.0)
     return r.astype(F32), dones.astype(F32)
