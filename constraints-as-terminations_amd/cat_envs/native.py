@@ -98,6 +98,10 @@ SERVO_CONSTANTS = ("dt", "kp", "kd", "inertia", "tau_max", "action_scale", "vel_
                    "command_deadzone")
 
 
+SERVO_EVAL_FIELDS = ("steps", "episodes", "falls", "reward", "err_lin2", "err_yaw2", "tilt2", "torque2", "feet",
+                     "ep_return", "done_return", "done_length")          # CATPPO_SERVO_EVAL_FLOATS = 12
+
+
 class ServoSim(C.Structure):
     """catppo_servo_sim: argument block of the Solo12 servo surrogate step (field order = include/catppo.h)"""
     _fields_ = ([("N", C.c_int64), ("env_offset", C.c_int64), ("state_in", C.c_void_p), ("state_out", C.c_void_p),
@@ -108,7 +112,8 @@ class ServoSim(C.Structure):
                    ("max_episode_length", C.c_int64), ("decimation", C.c_int32), ("resample_steps", C.c_int32),
                    ("init", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64),
                    ("default_joint_pos", C.c_float * 12)]
-                + [(n, C.c_float) for n in SERVO_CONSTANTS])
+                + [(n, C.c_float) for n in SERVO_CONSTANTS]
+                + [("fixed_command", C.c_void_p), ("eval", C.c_void_p)])
 
 
 F32, F16, F64 = 0, 1, 2                 # CATPPO_F32 / _F16 / _F64

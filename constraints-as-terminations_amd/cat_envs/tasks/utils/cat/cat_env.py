@@ -193,7 +193,28 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         d.dt = dt
         for n in native.SERVO_CONSTANTS[1:]:
             setattr(d, n, float(getattr(syn, "servo_" + n)))
+        self._fixed_command = self._eval_record = None                  # referenced by the descriptor: keep alive
         self._build_scene()
+
+    def _table(self, t, width, what):
+        if t is None:
+            return None
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_contiguous() and t.device == self.cur.device
+                and tuple(t.shape) == (self.N, width)):
+            raise ValueError(f"{what} must be a contiguous fp32 tensor of shape ({self.N}, {width}) on {self.cur.device}")
+        return t
+
+    def set_fixed_command(self, t: torch.Tensor | None):
+        """``t`` [N, 3]: env i's command is row i in every step and every episode, as it stands (no dead zone, no standing
+        fraction); None: the simulator draws the commands itself again.  The kernel reads the tensor at every launch."""
+        self._fixed_command = self._table(t, 3, "fixed commands")
+        self._desc.fixed_command = None if t is None else t.data_ptr()
+
+    def set_eval_record(self, t: torch.Tensor | None):
+        """``t`` [N, 12] (``native.SERVO_EVAL_FIELDS``): every following step adds its terms to row i of the record inside
+        the simulator's own launch, ``reset()`` zeroes it; None: detach."""
+        self._eval_record = self._table(t, len(native.SERVO_EVAL_FIELDS), "the evaluation record")
+        self._desc.eval = None if t is None else t.data_ptr()
 
     def reset(self):
         """the first state of episode 0 in the state buffer"""
@@ -342,6 +363,21 @@ class CaTEnv:
         if hasattr(self.cfg, "constraints"):
             self.constraint_manager = ConstraintManager(self.cfg.constraints, self)
             print("[INFO] Constraint Manager: ", self.constraint_manager)
+
+    # evaluation ------------------------------------------------------------------------------
+    def _servo_sim(self) -> Solo12ServoSim:
+        if not isinstance(self.sim, Solo12ServoSim):
+            raise TypeError("fixed commands and the evaluation record need the closed-loop simulator "
+                            "(SyntheticCfg.kind = 'servo'); the stream simulator is open loop")
+        return self.sim
+
+    def set_fixed_commands(self, commands: torch.Tensor | None):
+        """per-env commands [N, 3] that replace the simulator's own draws (None: back to the draws)"""
+        self._servo_sim().set_fixed_command(commands)
+
+    def set_eval_record(self, record: torch.Tensor | None):
+        """attach (or, with None, detach) the simulator's per-env evaluation record [N, 12]"""
+        self._servo_sim().set_eval_record(record)
 
     # episode control -------------------------------------------------------------------------
     def reset(self, seed: int | None = None, options=None):

@@ -46,8 +46,17 @@ __device__ __forceinline__ float tree4(float x) {
 
 __device__ __forceinline__ float pick(const rng::u32x4& r, int w) { return rng::uniform_open(w == 0 ? r.x : w == 1 ? r.y : w == 2 ? r.z : r.w); }
 
-// command of (env, episode, resample index): uniform in the reference ranges, dead zone, standing fraction
-__device__ __forceinline__ void command_of(const catppo_servo_sim& d, uint32_t gid, uint32_t ep, uint32_t k, float c[3]) {
+// command of (env, episode, resample index): uniform in the reference ranges, dead zone, standing fraction; with a
+// fixed-command table the caller's row `e` as it stands, for every episode and resample index (kEval: see the kernel)
+template <bool kEval>
+__device__ __forceinline__ void command_of(const catppo_servo_sim& d, int64_t e, uint32_t gid, uint32_t ep, uint32_t k,
+                                           float c[3]) {
+  if constexpr (kEval) {
+    if (d.fixed_command) {
+      for (int i = 0; i < 3; ++i) c[i] = d.fixed_command[e * 3 + i];
+      return;
+    }
+  }
   const rng::u32x4 r = rng::philox4x32_10(rng::u32x4{gid, ep, k, kTagCommand}, (uint32_t)d.seed, (uint32_t)(d.seed >> 32));
   c[0] = -0.3f + rng::uniform_open(r.x) * 1.3f;
   c[1] = -0.7f + rng::uniform_open(r.y) * 1.4f;
@@ -64,6 +73,9 @@ __device__ __forceinline__ float init_q(const catppo_servo_sim& d, uint32_t gid,
   return def + (pick(r, lane & 3) - 0.5f) * d.init_noise;
 }
 
+// kEval = false is the launch with both evaluation pointers NULL: everything they add is compiled out of it, so that a
+// training step runs the code it ran before the two fields existed
+template <bool kEval>
 __global__ __launch_bounds__(kThreads) void servo_sim_kernel(const catppo_servo_sim d) {
   extern __shared__ float4 lds4[];
   float* lds = reinterpret_cast<float*>(lds4);
@@ -87,8 +99,15 @@ __global__ __launch_bounds__(kThreads) void servo_sim_kernel(const catppo_servo_
   const int f = lane & 3, foot_body = 4 * f + 4;
   const float def = isj ? d.default_joint_pos[lane] : 0.f;
   float cmd[3];
-  command_of(d, gid, ep, (uint32_t)(t / d.resample_steps), cmd);
+  command_of<kEval>(d, e, gid, ep, (uint32_t)(t / d.resample_steps), cmd);
   float* obs = row + d.off_obs;
+  // evaluation record: lane k < 12 of a live lane group owns field k of its env (one 48-byte access per env); the spare
+  // groups past N, which recompute env N - 1, neither read nor write it
+  const bool rec = kEval && d.eval != nullptr && e0 + grp < d.N && isj;
+  const int64_t rec_at = e * CATPPO_SERVO_EVAL_FLOATS + lane;
+  float rec0 = 0.f;
+  if constexpr (kEval)
+    if (rec && !init) rec0 = d.eval[rec_at];
 
   if (init) {
     // the first state of episode 0: default pose + noise, at rest, four feet on the ground
@@ -110,6 +129,8 @@ __global__ __launch_bounds__(kThreads) void servo_sim_kernel(const catppo_servo_
         if (6 + k < D) obs[6 + k] = cmd[k];
       }
     }
+    if constexpr (kEval)
+      if (rec) d.eval[rec_at] = 0.f;
   } else {
     // ---- the state this step starts from: the row, or the first state of episode `ep` re-derived from the counter
     float q = 0.f, qd = 0.f, a = 0.f;
@@ -214,12 +235,35 @@ __global__ __launch_bounds__(kThreads) void servo_sim_kernel(const catppo_servo_
       float head[9] = {ang[0], ang[1], ang[2], grav[0], grav[1], grav[2], cmd[0], cmd[1], cmd[2]};
       if (ends) {
         float cn[3];
-        command_of(d, gid, ep_out, 0u, cn);
+        command_of<kEval>(d, e, gid, ep_out, 0u, cn);
         head[0] = head[1] = head[2] = head[3] = head[4] = 0.f;
         head[5] = -1.f, head[6] = cn[0], head[7] = cn[1], head[8] = cn[2];
       }
       for (int k = 0; k < 9; ++k)
         if (k < D) obs[k] = head[k];
+    }
+    // ---- evaluation record: every lane holds all twelve terms of this step, lane k adds term k to field k
+    if (kEval && d.eval != nullptr) {
+      const float torque2 = tree16(tau_w * tau_w);
+      const float ret = __shfl(rec0, 9, 16) + reward;      // this episode's return so far (field 9 + this step)
+      float term = 1.f, acc = rec0;
+      switch (lane) {
+        case 1: term = ends ? 1.f : 0.f; break;
+        case 2: term = fallen ? 1.f : 0.f; break;
+        case 3: term = reward; break;
+        case 4: term = ex * ex + ey * ey; break;
+        case 5: term = ew * ew; break;
+        case 6: term = tilt2; break;
+        case 7: term = torque2; break;
+        case 8: term = ncon; break;
+        case 9: term = reward; break;
+        case 10: term = ends ? ret : 0.f; break;
+        case 11: term = ends ? (float)(t + 1) : 0.f; break;
+        default: break;
+      }
+      acc = acc + term;
+      if (lane == 9 && ends) acc = 0.f;
+      if (rec) d.eval[rec_at] = acc;
     }
     // the force history moves one slot back (slot 0 is this step)
     if (!rst)
@@ -251,6 +295,9 @@ extern "C" int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* de
   CATPPO_CHECK_ARG(ctx, d.H >= 1 && d.B == 17 && d.obs_dim >= 0);
   CATPPO_CHECK_ARG(ctx, d.decimation >= 1 && d.resample_steps >= 1 && d.max_episode_length >= 1);
   CATPPO_CHECK_ARG(ctx, d.inertia > 0.f && d.dt > 0.f && d.reward_scale > 0.f);
+  CATPPO_CHECK_ARG(ctx, ((uintptr_t)d.eval % 16) == 0);
+  CATPPO_CHECK_ARG(ctx, d.fixed_command == nullptr || (d.fixed_command != d.state_in && d.fixed_command != d.state_out));
+  CATPPO_CHECK_ARG(ctx, d.eval == nullptr || (d.eval != d.state_in && d.eval != d.state_out));
   // every field the kernel writes lies inside the row
   const struct { int32_t off, width; } fields[] = {
       {d.off_joint_pos, kJoints}, {d.off_joint_vel, kJoints}, {d.off_joint_acc, kJoints}, {d.off_applied_torque, kJoints},
@@ -260,7 +307,8 @@ extern "C" int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* de
   for (const auto& fl : fields) CATPPO_CHECK_ARG(ctx, fl.off >= 0 && (int64_t)fl.off + fl.width <= d.row_floats);
   const unsigned nblk = (unsigned)cdiv64(d.N, kEnvsPerBlock);
   const size_t lds_bytes = (size_t)d.row_floats * kEnvsPerBlock * sizeof(float);
-  hipLaunchKernelGGL(servo_sim_kernel, dim3(nblk), dim3(kThreads), lds_bytes, static_cast<hipStream_t>(stream), d);
+  const auto kernel = (d.fixed_command || d.eval) ? servo_sim_kernel<true> : servo_sim_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(nblk), dim3(kThreads), lds_bytes, static_cast<hipStream_t>(stream), d);
   CATPPO_CHECK_LAUNCH(ctx);
   return CATPPO_OK;
 }

@@ -656,7 +656,17 @@ int catppo_set_grad_overlap(catppo_ctx* ctx, int on);      /* on: 0 | 1 | 2 set 
  * >= max_episode_length, or the model's own hard_reset) writes the terminal state, but its `obs` already shows the
  * first state of the next episode.  init != 0: write the first state of episode 0 (no integration; action and reset
  * are not read).  state_in and state_out are different buffers unless init.  Enqueues on `stream`, never allocates,
- * never synchronises. */
+ * never synchronises.
+ * fixed_command != NULL: env i's command is fixed_command[3 i .. 3 i + 2] in every step and every episode (the step's
+ * command, the init row, the post-reset observation); no dead zone, no standing fraction - the table is the command.
+ * eval != NULL: a per-env evaluation record of CATPPO_SERVO_EVAL_FLOATS fp32 sums, read, updated and written back by
+ * the launch of every step (one unfused add per field and step, the kernel's own values of that step) and set to zero
+ * by an init launch:  0 steps | 1 episodes ended | 2 falls (hard_reset) | 3 reward (raw) | 4 (cx - vx)^2 + (cy - vy)^2 |
+ * 5 (cw - wz)^2 | 6 roll^2 + pitch^2 | 7 tree16 of applied_torque^2 | 8 feet in contact | 9 return of the running
+ * episode (zero after the step that ends it) | 10 returns of the ended episodes | 11 lengths of the ended episodes.
+ * Both NULL: the launch computes what it did before the two fields existed, bit for bit.  Neither may alias a state
+ * buffer; the record never changes a float of the state row. */
+#define CATPPO_SERVO_EVAL_FLOATS 12
 typedef struct catppo_servo_sim {
   int64_t N, env_offset;                 /* env_offset: global env id of row 0 (env-sharded runs) */
   const float* state_in;
@@ -675,6 +685,8 @@ typedef struct catppo_servo_sim {
   float dt, kp, kd, inertia, tau_max, action_scale, vel_alpha, tilt_beta, tilt_max, reward_scale, foot_clearance,
       contact_threshold, stand_height, height_drop, floor_height, min_height, base_stiffness, weight, impact_gain,
       init_noise, standing_fraction, command_deadzone;
+  const float* fixed_command;            /* [N, 3] or NULL */
+  float* eval;                           /* [N, CATPPO_SERVO_EVAL_FLOATS] or NULL; 16-byte aligned */
 } catppo_servo_sim;
 int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* desc, void* stream);
 

@@ -4,6 +4,11 @@ Checkpoints written by ``PPO()`` (``model_<it>.pt``, the reference's 23-key ``st
 here and in the reference's play.py alike.  Like the reference (play.py:107-135) the script writes
 ``<run>/exported/model.onnx`` and ``<run>/exported/model.pt`` (deterministic policy with the frozen
 observation normaliser) before rolling the policy out on the device kernels.
+
+``--eval_steps K`` (closed-loop servo tasks) then evaluates the deterministic policy for K control steps on a fresh env
+(``cat_envs.tasks.utils.cleanrl.evaluate``): one line ``[EVAL] <json>`` and ``<run>/eval/<checkpoint name>.json``.
+``--eval_grid NX NY NW`` fixes the commands to a grid over the task's command ranges (env i gets point i % (NX NY NW));
+without it the simulator draws them.  ``--stochastic`` samples the actions instead of taking the mean.
 """
 import argparse
 import os
@@ -41,6 +46,10 @@ def main(argv=None):
     parser.add_argument("--seed", type=int, default=None)
     parser.add_argument("--device", type=str, default=None)
     parser.add_argument("--headless", action="store_true", default=False)
+    parser.add_argument("--eval_steps", type=int, default=0, help="Evaluate the policy for this many control steps (0: off).")
+    parser.add_argument("--eval_grid", type=int, nargs=3, default=None, metavar=("NX", "NY", "NW"),
+                        help="Fixed commands: a grid of NX x NY x NW points over the command ranges (default: sampled).")
+    parser.add_argument("--stochastic", action="store_true", default=False, help="Evaluate with sampled actions.")
     cli_args.add_clean_rl_args(parser)
     args_cli = parser.parse_args(argv)
     import torch
@@ -80,6 +89,25 @@ def main(argv=None):
         ret += float(rewards.mean())
     print(f"[INFO] mean reward per step over {args_cli.video_length} steps: {ret / args_cli.video_length:.4f}")
     env.close()
+
+    if args_cli.eval_steps > 0:
+        from cat_envs.tasks.utils.cleanrl.evaluate import COMMAND_RANGES, command_grid, evaluate_policy
+        eval_env = make(args_cli.task, cfg=env_cfg)               # a fresh env: the evaluator leaves it in the evaluated state
+        commands = None
+        if args_cli.eval_grid is not None:
+            axes = [(lo, hi, n) for (lo, hi), n in zip(COMMAND_RANGES, args_cli.eval_grid)]
+            commands = command_grid(*axes, num_envs=eval_env.unwrapped.num_envs)[0]
+        result = evaluate_policy(eval_env, actor, args_cli.eval_steps, commands=commands,
+                                 deterministic=not args_cli.stochastic)
+        text = result.to_json()
+        print(f"[EVAL] {text}")
+        out_dir = os.path.join(os.path.dirname(resume_path), "eval")
+        os.makedirs(out_dir, exist_ok=True)
+        out_path = os.path.join(out_dir, os.path.splitext(os.path.basename(resume_path))[0] + ".json")
+        with open(out_path, "w") as f:
+            f.write(text + "\n")
+        print(f"[INFO] Wrote evaluation to {out_path}")
+        eval_env.close()
 
 
 if __name__ == "__main__":

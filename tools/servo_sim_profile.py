@@ -3,6 +3,10 @@
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/servo_sim_profile.py --num_envs 4096
     python tools/rocpd_stats.py DIR/.../*.db          ->  rows of profiles/servo_sim_kernel_stats.csv
 
+--eval attaches the evaluation record and a fixed command table to the simulator (both descriptor pointers non-NULL), for the
+three-arm comparison of profiles/servo_eval_kernel_stats.csv: CATPPO_LIB=<library of the parent commit>, this library without
+--eval (both pointers NULL), this library with --eval.
+
 Per env step the trace shows servo_sim_kernel (the simulator), the two launches of catppo_rollout_pre, the one of
 catppo_rollout_post and the policy forward."""
 import argparse
@@ -20,6 +24,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--num_envs", type=int, default=4096)
     ap.add_argument("--rollouts", type=int, default=10)
+    ap.add_argument("--eval", action="store_true", help="attach the evaluation record and fixed commands")
     a = ap.parse_args()
     import cat_envs.tasks  # noqa: F401
     from cat_envs.shim import load_cfg_from_registry, make
@@ -31,12 +36,24 @@ def main():
     agent_cfg.minibatch_size = min(agent_cfg.minibatch_size, a.num_envs * agent_cfg.num_steps)
     trainer = PPOTrainer(make(task, cfg=env_cfg), agent_cfg)
     assert trainer.sink is not None
+    if a.eval:
+        from cat_envs.tasks.utils.cleanrl.evaluate import COMMAND_RANGES, command_grid
+        env_u = trainer.envs.unwrapped
+        record = torch.zeros(a.num_envs, 12, device=env_u.device)
+        axes = [(lo, hi, 4) for lo, hi in COMMAND_RANGES]
+        commands = torch.from_numpy(command_grid(*axes, num_envs=a.num_envs)[0]).to(env_u.device)
+        env_u.set_eval_record(record)
+        env_u.set_fixed_commands(commands)
     for _ in range(a.rollouts):
         trainer.rollout()
         trainer.obs[0].copy_(trainer.obs[trainer.T])
     torch.cuda.synchronize()
     print(f"{a.rollouts} rollouts of {trainer.T} steps x {a.num_envs} envs; mean reward/step "
           f"{float(trainer.rewards.float().mean()):.4f}")
+    if a.eval:
+        steps = record[:, 0].cpu()
+        assert float(steps.min()) == float(steps.max()) == a.rollouts * trainer.T, (float(steps.min()), float(steps.max()))
+        print(f"evaluation record: {int(steps[0])} steps per env, raw reward/step {float(record[:, 3].sum() / steps.sum()):.4f}")
 
 
 if __name__ == "__main__":
