@@ -147,6 +147,28 @@ class SyntheticSolo12Sim:
     def step(self, action=None):
         self.cur.copy_(self.advance())                         # "scene.update": one contiguous slab
 
+    # run state: the state buffer and the position in the stream; the stream itself is a pure
+    # function of (seed, N, obs_dim, stream_steps) - those are part of the fingerprint and construction regenerates it
+    def fingerprint(self) -> dict:
+        return {"stream_steps": int(self.S)}
+
+    def state_dict(self) -> dict:
+        return {"cur": self.cur, "cursor": int(self.cursor)}
+
+    def check_state_dict(self, sd: dict):
+        s = sd["cur"]
+        if tuple(s.shape) != tuple(self.cur.shape) or s.dtype != self.cur.dtype:
+            raise ValueError(f"run state: simulator state is {tuple(s.shape)} {s.dtype}, this simulator's is "
+                             f"{tuple(self.cur.shape)} {self.cur.dtype}")
+        if not -1 <= int(sd["cursor"]) < len(self._slabs):
+            raise ValueError(f"run state: simulator cursor {sd['cursor']} outside this simulator's {len(self._slabs)} slabs")
+
+    def load_state_dict(self, sd: dict):
+        """in place: term descriptors, the fused step and the servo kernel's argument block hold the address of ``cur``"""
+        self.check_state_dict(sd)
+        self.cur.copy_(sd["cur"])
+        self.cursor = int(sd["cursor"])
+
 
 class Solo12ServoSim(SyntheticSolo12Sim):
     """Closed-loop stand-in simulator: the Solo12 servo surrogate (csrc/servo_sim.hip).
@@ -241,6 +263,20 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         else:
             self.cur.copy_(self.advance(action))
 
+    # run state: the state buffer (the 14 private floats per env included) and which slab is written next; the slabs are
+    # scratch - the kernel reads ``cur`` and writes the other slab
+    def fingerprint(self) -> dict:
+        d = self._desc
+        fp = {n: float(getattr(d, n)) for n in native.SERVO_CONSTANTS}
+        fp["resample_steps"], fp["decimation"] = int(d.resample_steps), int(d.decimation)
+        return {"servo": fp}
+
+    def state_dict(self) -> dict:
+        if self._fixed_command is not None or self._eval_record is not None:
+            raise RuntimeError("run state: a fixed-command table or an evaluation record is attached to the simulator; "
+                               "an evaluation is not a resumable state (detach them before saving)")
+        return super().state_dict()
+
 
 class _ActionManager:
     def __init__(self, n, a, device):
@@ -283,6 +319,22 @@ class _CurriculumManager:
 
     def reset(self, env_ids=None):
         return {k: v for k, v in self._state.items() if isinstance(v, (int, float))}
+
+    # run state: the logged scalars and, for every constraint term, the ``max_p`` the curriculum has reached (a Python
+    # double on the term cfg; it reaches the device as a launch argument of the next step)
+    def state_dict(self) -> dict:
+        cm = getattr(self._env, "constraint_manager", None)
+        max_p = {n: float(cm.get_term_cfg(n).max_p) for n in cm.active_terms} if cm is not None else {}
+        return {"state": {k: float(v) for k, v in self._state.items() if isinstance(v, (int, float))}, "max_p": max_p}
+
+    def load_state_dict(self, sd: dict):
+        cm = getattr(self._env, "constraint_manager", None)
+        for name, p in sd["max_p"].items():
+            cfg = cm.get_term_cfg(name)
+            cfg.max_p = float(p)
+            cm.set_term_cfg(name, cfg)
+        self._state.clear()
+        self._state.update(sd["state"])
 
 
 class CaTEnv:
@@ -378,6 +430,74 @@ class CaTEnv:
     def set_eval_record(self, record: torch.Tensor | None):
         """attach (or, with None, detach) the simulator's per-env evaluation record [N, 12]"""
         self._servo_sim().set_eval_record(record)
+
+    # run state (DESIGN section 10) ----------------------------------------------------------------
+    def _state_tensors(self) -> dict:
+        am = self.action_manager
+        return {"episode_length_buf": self.episode_length_buf, "reset_buf": self.reset_buf,
+                "reset_terminated": self.reset_terminated, "reset_time_outs": self.reset_time_outs,
+                "reward_buf": self.reward_buf, "dones": self._dones, "action": am._action, "prev_action": am._prev_action}
+
+    def state_fingerprint(self) -> dict:
+        """what has to be equal between the env that saved a state and the env that loads it"""
+        syn, cm = self.cfg.synthetic, getattr(self, "constraint_manager", None)
+        if cm is not None and cm._term_names and not cm._bound:
+            cm._bind(native.get(self.device))
+        fp = {"task_kind": "servo" if isinstance(self.sim, Solo12ServoSim) else "stream",
+              "num_envs": self.num_envs, "obs_dim": self.obs_dim, "act_dim": self.act_dim,
+              "env_seed": int(getattr(self.cfg, "seed", 0) or 0), "seed_offset": int(syn.seed_offset),
+              "env_offset": int(getattr(self.cfg.scene, "env_offset", 0) or 0),
+              "max_episode_length": int(self.max_episode_length), "decimation": int(self.cfg.decimation),
+              "exact_reset_sync": bool(self.exact_reset_sync),
+              "constraint_terms": [[n, int(w)] for n, w in zip(cm._term_names, cm._widths)] if cm is not None else []}
+        fp.update(self.sim.fingerprint())
+        return fp
+
+    def state_dict(self) -> dict:
+        """the env's part of a run state: counters, reset masks, action history, the curriculum's scalars and the
+        ``max_p`` values it has reached, the constraint manager's and the simulator's own parts.  Legal between two steps.
+        The tensors are the live ones: the caller copies them (``checkpoint.to_plain``)."""
+        sd = {"common_step_counter": int(self.common_step_counter), "sim_step_counter": int(self._sim_step_counter),
+              "curriculum": self.curriculum_manager.state_dict(), "sim": self.sim.state_dict()}
+        sd.update(self._state_tensors())
+        if hasattr(self, "constraint_manager"):
+            sd["constraints"] = self.constraint_manager.state_dict()
+        return sd
+
+    def check_state_dict(self, sd: dict):
+        """``ValueError`` unless every part of ``sd`` fits this env; loads nothing"""
+        keys = ["common_step_counter", "sim_step_counter", "curriculum", "sim", *self._state_tensors()]
+        if hasattr(self, "constraint_manager"):
+            keys.append("constraints")
+        missing = [k for k in keys if k not in sd]
+        if missing:
+            raise ValueError(f"run state: the env's part lacks {missing}")
+        for k, t in self._state_tensors().items():
+            s = sd[k]
+            if tuple(s.shape) != tuple(t.shape) or s.dtype != t.dtype:
+                raise ValueError(f"run state: env tensor '{k}' is {tuple(s.shape)} {s.dtype}, this env's is "
+                                 f"{tuple(t.shape)} {t.dtype}")
+        self.sim.check_state_dict(sd["sim"])
+        if hasattr(self, "constraint_manager"):
+            cm = self.constraint_manager
+            cm.check_state_dict(sd["constraints"])
+            unknown = [n for n in sd["curriculum"]["max_p"] if n not in cm.active_terms]
+            if unknown:
+                raise ValueError(f"run state: max_p of constraint terms {unknown} that this env does not have")
+
+    def load_state_dict(self, sd: dict):
+        """IN PLACE (``copy_`` into the existing tensors, never a rebound attribute): the fused step's argument block, the
+        servo simulator's, the constraint manager's descriptor table and a trainer's ``RolloutSink`` hold raw device
+        addresses of these tensors, and captured graphs bake them in.  Everything is checked before anything is written."""
+        self.check_state_dict(sd)
+        for k, t in self._state_tensors().items():
+            t.copy_(sd[k])
+        self.common_step_counter = int(sd["common_step_counter"])
+        self._sim_step_counter = int(sd["sim_step_counter"])
+        self.sim.load_state_dict(sd["sim"])
+        if hasattr(self, "constraint_manager"):
+            self.constraint_manager.load_state_dict(sd["constraints"])
+        self.curriculum_manager.load_state_dict(sd["curriculum"])      # through set_term_cfg: the next launch carries it
 
     # episode control -------------------------------------------------------------------------
     def reset(self, seed: int | None = None, options=None):

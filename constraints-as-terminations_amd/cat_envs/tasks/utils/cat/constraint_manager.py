@@ -445,6 +445,59 @@ class ConstraintManager(ManagerBase):
                 self._log_views.append(d)
         return dict(self._log_views[self._log_pos]) if copy else self._log_views[self._log_pos]
 
+    # ------------------------------------------------------------------ run state
+    def _state_tensors(self) -> Dict[str, torch.Tensor]:
+        cat = self.cat
+        return {"p_rm": cat._p_rm, "p_cstr": cat._p_cstr, "p_probs": cat._p_probs, "ep_viol": self._ep_viol,
+                "ep_prob": self._ep_prob, "cstr_prob_buf": self._cstr_prob_buf, "log_ring": self._log_ring}
+
+    def state_dict(self) -> dict:
+        """everything a later step reads that an earlier step wrote: running maxima and the first-call flag, the packed
+        constraint / probability tiles, the per-episode sums, the log ring with its position.  ``max_p`` belongs to the
+        curriculum and travels with the env's part.  Tensors are the live ones (the caller copies them)."""
+        if self._class_term_cfgs:
+            raise NotImplementedError("run state: class-based constraint terms keep state of their own that is not saved")
+        if self._term_names and not self._bound:
+            self._bind(native.get(self._device))
+        sd = {"terms": [[n, int(w)] for n, w in zip(self._term_names, self._widths)],
+              "p_first": bool(self.cat._p_first) if self._term_names else True,
+              "log_pos": int(self._log_pos), "log_ring_slots": int(self.LOG_RING)}
+        if self._term_names:
+            sd.update(self._state_tensors())
+        return sd
+
+    def check_state_dict(self, sd: dict):
+        """``ValueError`` unless ``sd`` fits this manager; changes nothing but the size of the log ring (grown, never shrunk,
+        the way a trainer's ``ensure_log_ring`` does)"""
+        if self._class_term_cfgs:
+            raise NotImplementedError("run state: class-based constraint terms keep state of their own that is not saved")
+        if self._term_names and not self._bound:
+            self._bind(native.get(self._device))
+        terms = [[n, int(w)] for n, w in zip(self._term_names, self._widths)]
+        if [list(t) for t in sd["terms"]] != terms:
+            raise ValueError(f"run state: constraint terms {sd['terms']} do not match this env's {terms}")
+        if not self._term_names:
+            return
+        self.ensure_log_ring(int(sd["log_ring_slots"]))
+        if int(sd["log_ring_slots"]) != self.LOG_RING:
+            raise ValueError(f"run state: log ring of {sd['log_ring_slots']} slots, this manager's has {self.LOG_RING}")
+        for k, t in self._state_tensors().items():
+            s = sd[k]
+            if tuple(s.shape) != tuple(t.shape) or s.dtype != t.dtype:
+                raise ValueError(f"run state: constraint manager tensor '{k}' is {tuple(s.shape)} {s.dtype}, "
+                                 f"this manager's is {tuple(t.shape)} {t.dtype}")
+
+    def load_state_dict(self, sd: dict):
+        """in place (``copy_``): the fused step's argument block and captured graphs hold the addresses of these tensors"""
+        self.check_state_dict(sd)
+        if not self._term_names:
+            return
+        for k, t in self._state_tensors().items():
+            t.copy_(sd[k])
+        self.cat._p_first = bool(sd["p_first"])
+        self._log_pos = int(sd["log_pos"])
+        self._desc_dirty = True              # the next step re-checks the descriptor table against the restored term cfgs
+
     @property
     def max_p(self) -> Dict[str, torch.Tensor]:
         return {n: torch.full((w,), c.max_p, dtype=torch.float, device=self._device)

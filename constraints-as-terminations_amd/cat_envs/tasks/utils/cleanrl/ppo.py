@@ -816,6 +816,126 @@ class PPOTrainer:
                 return
         self.adam_step += self._update_body(perms)
 
+    # ------------------------------------------------------------------ run state
+    _SHARDED_STATE = ("run states of env-sharded runs (world > 1) are not implemented: every rank owns its own env shard, "
+                      "which would need a file of its own, and nothing here can test more than two ranks on one device")
+
+    def state_fingerprint(self) -> dict:
+        """everything that must be equal for a saved state to continue THIS run (checkpoint.check_fingerprint)"""
+        env_u = self.envs.unwrapped
+        if not hasattr(env_u, "state_fingerprint"):
+            raise NotImplementedError(f"run state: {type(env_u).__name__} has no state_fingerprint() / state_dict()")
+        c, a = self.cfg, self.agent
+        fp = dict(env_u.state_fingerprint())
+        fp.update({"hidden": [int(h) for h in a.hidden], "num_steps": self.T, "minibatch_size": self.mb,
+                   "updates_epochs": int(c.updates_epochs), "mlp_precision": a.mlp_precision,
+                   "rollout_dtype": "fp16" if self.plane_dtype == torch.float16 else "fp32", "rng": self.rng,
+                   "lr_schedule": self.lr_schedule, "world": int(self.world),
+                   "sizeof_iter_state": int(C.sizeof(native.IterState)),
+                   "catppo_version": int(self.nat.lib.catppo_version())})
+        return fp
+
+    def _schedule_fields(self) -> dict:
+        """recorded, not compared: a user may extend a run or change a coefficient"""
+        c = self.cfg
+        out = {k: float(getattr(c, k)) for k in ("learning_rate", "gamma", "gae_lambda", "clip_coef", "ent_coef", "vf_coef",
+                                                  "max_grad_norm", "kl_threshold") if hasattr(c, k)}
+        out.update(num_iterations=int(c.num_iterations), anneal_lr=bool(c.anneal_lr), norm_adv=bool(c.norm_adv),
+                   clip_vloss=bool(c.clip_vloss), seed=int(getattr(c, "seed", 0)))
+        return out
+
+    def save_state(self, path: str) -> str:
+        """Write the whole run state to ``path`` (atomically).  Only legal at an iteration boundary - after
+        ``run_iteration`` has returned, or straight after construction.  One device synchronisation; the copies to the host
+        that follow find the device idle."""
+        from . import checkpoint
+        if self.world > 1:
+            raise NotImplementedError(self._SHARDED_STATE)
+        fp = self.state_fingerprint()
+        env_sd = self.envs.unwrapped.state_dict()             # raises while an evaluation is attached
+        torch.cuda.synchronize()
+        st = self.nat.iter_state_read(self.state)
+        if int(st.iteration) != self.iteration or int(st.adam_step) != self.adam_step:
+            raise RuntimeError(f"run state: the device iteration state (iteration {int(st.iteration)}, {int(st.adam_step)} "
+                               f"optimiser steps) and the trainer ({self.iteration}, {self.adam_step}) disagree: not at an "
+                               "iteration boundary")
+        tr = {"agent": dict(self.agent.state_dict()), "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq,
+              "iter_state": self.state, "sizeof_iter_state": int(self.state.numel()),
+              "iter_state_fields": {"iteration": int(st.iteration), "adam_step": int(st.adam_step), "lr": float(st.lr),
+                                    "seed": int(st.seed)},
+              "adam_step": int(self.adam_step), "iteration": int(self.iteration), "global_step": int(self.global_step),
+              "obs0": self.obs[0], "dones0": self.dones[0], "true_dones0": self.true_dones[0], "kl_buf": self.kl_buf,
+              "eager_updates_left": int(self._eager_updates_left), "schedule": self._schedule_fields()}
+        if self.rng == "torch":
+            tr["torch_rng"] = {"cpu": torch.get_rng_state(), "device": torch.cuda.get_rng_state(self.device)}
+        return checkpoint.write_state(path, {"format": checkpoint.FORMAT, "fingerprint": fp, "trainer": tr, "env": env_sd})
+
+    _STATE_KEYS = ("agent", "exp_avg", "exp_avg_sq", "iter_state", "sizeof_iter_state", "iter_state_fields", "adam_step",
+                   "iteration", "global_step", "obs0", "dones0", "true_dones0", "kl_buf", "eager_updates_left", "schedule")
+
+    def load_state(self, path: str) -> dict:
+        """Continue from the run state in ``path``: afterwards the next ``run_iteration`` is iteration ``saved + 1`` of the
+        run that wrote it, bit for bit.  The fingerprint and every shape are checked BEFORE anything is written - a refused
+        load leaves trainer and env as they were.  Loads in place (``copy_``); a captured update graph is dropped and
+        captured again; the launch-time switches (graph_update, one_call_step, defer_tail, ...) stay as this process chose
+        them.  Returns the file's ``trainer`` section."""
+        from . import checkpoint
+        if self.world > 1:
+            raise NotImplementedError(self._SHARDED_STATE)
+        payload = checkpoint.read_state(path)
+        checkpoint.check_fingerprint(payload["fingerprint"], self.state_fingerprint(), path)
+        tr, env_u = payload["trainer"], self.envs.unwrapped
+        checkpoint.require(tr, self._STATE_KEYS + (("torch_rng",) if self.rng == "torch" else ()), path, "trainer")
+        own = self.agent.state_dict()
+        pairs = [(f"agent.{k}", own[k], tr["agent"].get(k)) for k in own]
+        pairs += [("exp_avg", self.exp_avg, tr["exp_avg"]), ("exp_avg_sq", self.exp_avg_sq, tr["exp_avg_sq"]),
+                  ("iter_state", self.state, tr["iter_state"]), ("obs0", self.obs[0], tr["obs0"]),
+                  ("dones0", self.dones[0], tr["dones0"]), ("true_dones0", self.true_dones[0], tr["true_dones0"]),
+                  ("kl_buf", self.kl_buf, tr["kl_buf"])]
+        extra = [k for k in tr["agent"] if k not in own]
+        bad = [f"{n}: saved {None if s is None else (tuple(s.shape), s.dtype)}, this run {(tuple(t.shape), t.dtype)}"
+               for n, t, s in pairs if s is None or tuple(s.shape) != tuple(t.shape) or s.dtype != t.dtype]
+        if bad or extra:
+            raise ValueError(f"{path}: trainer tensors do not fit: {'; '.join(bad + ['unexpected agent.' + k for k in extra])}")
+        try:
+            env_u.check_state_dict(payload["env"])
+        except (ValueError, KeyError) as e:
+            raise ValueError(f"{path}: {e}") from e
+        # -- nothing was written up to here ---------------------------------------------------------------------------
+        torch.cuda.synchronize()
+        if self._graph_id is not None:                           # captured again by the next update phase
+            self.nat.graph_destroy(self._graph_id)
+            self._graph_id = None
+        with torch.no_grad():
+            for _, t, s in pairs:
+                t.copy_(s)
+        env_u.load_state_dict(payload["env"])
+        self.adam_step, self.iteration = int(tr["adam_step"]), int(tr["iteration"])
+        self.global_step = int(tr["global_step"])
+        self._eager_updates_left = int(tr["eager_updates_left"])
+        if self.rng == "torch":
+            torch.set_rng_state(tr["torch_rng"]["cpu"])
+            torch.cuda.set_rng_state(tr["torch_rng"]["device"], self.device)
+        torch.cuda.synchronize()
+        sched = tr["schedule"]
+        if self.lr_schedule == "linear" and int(sched.get("num_iterations", self.cfg.num_iterations)) != int(self.cfg.num_iterations):
+            print(f"[catppo] resumed at iteration {self.iteration}: the linear learning-rate anneal now follows "
+                  f"num_iterations={int(self.cfg.num_iterations)} (the saved run had {int(sched['num_iterations'])})")
+        return tr
+
+    def _save_run_state(self, it: int):
+        """``state_<it>.pt`` beside ``model_<it>.pt`` (rank 0, cfg ``save_state``), older ones pruned (``keep_states``)"""
+        from . import checkpoint
+        if not bool(getattr(self.cfg, "save_state", True)):
+            return
+        if self.world > 1:
+            if not getattr(self, "_sharded_note", False):
+                self._sharded_note = True
+                print(f"[catppo] no run state is written: {self._SHARDED_STATE}")
+            return
+        self.save_state(f"{self.run_path}/state_{it}.pt")
+        checkpoint.prune_states(self.run_path, int(getattr(self.cfg, "keep_states", 2)))
+
     # ------------------------------------------------------------------ one iteration
     def run_iteration(self, eps_fn=None, perm_fn=None, log: bool = True):
         if self.stream is None:
@@ -878,6 +998,7 @@ class PPOTrainer:
         if self.run_path is not None and self.rank == 0 and (it + 1) % c.save_interval == 0:
             torch.save(self.agent.state_dict(), f"{self.run_path}/model_{it}.pt")     # same off-by-one naming
             print("Saved model")
+            self._save_run_state(it)                             # (only where a model is written: no further sync elsewhere)
         return stats
 
     def _log_episode_infos(self, ep_infos, it):
@@ -907,17 +1028,32 @@ class PPOTrainer:
             self.writer.add_scalar(key if "/" in key else "Episode/" + key, value, it)
 
 
-def PPO(envs, ppo_cfg, run_path):
-    """Train with CleanRL-style PPO on CaT float dones (reference ppo.py:126-372)."""
+def PPO(envs, ppo_cfg, run_path, resume_state=None, stop_after=None):
+    """Train with CleanRL-style PPO on CaT float dones (reference ppo.py:126-372).
+
+    ``resume_state``: path of a run state (``state_<it>.pt``, written beside every ``model_<it>.pt``): the run continues
+    with iteration ``it + 1`` exactly as the run that wrote it would have.  ``stop_after``: leave after that iteration
+    (what a killed run looks like; the schedules still follow ``num_iterations``)."""
     writer = _make_writer(ppo_cfg, run_path)
     if not os.path.exists(run_path):
         os.makedirs(run_path)
     trainer = PPOTrainer(envs, ppo_cfg, run_path, writer)
+    total = int(ppo_cfg.num_iterations)
+    first = 1
+    if resume_state is not None:
+        trainer.load_state(resume_state)
+        if trainer.iteration >= total:
+            raise ValueError(f"{resume_state} was saved after iteration {trainer.iteration}: nothing is left of a run of "
+                             f"num_iterations={total} (raise --num_iterations to extend the run)")
+        first = trainer.iteration + 1
+        print(f"Resuming from {resume_state} at iteration {first}")
+    last = total if stop_after is None else min(total, int(stop_after))
     print(f"Starting training for {ppo_cfg.num_iterations} steps")
-    t0 = time.time()
-    for _ in range(1, int(ppo_cfg.num_iterations) + 1):
+    t0, steps0 = time.time(), trainer.global_step
+    for _ in range(first, last + 1):
         trainer.run_iteration()
     torch.cuda.synchronize()
     dt = time.time() - t0
-    print(f"[PPO] {trainer.global_step} env steps in {dt:.2f} s ({trainer.global_step / max(dt, 1e-9):,.0f} env-steps/s)")
+    steps = trainer.global_step - steps0
+    print(f"[PPO] {steps} env steps in {dt:.2f} s ({steps / max(dt, 1e-9):,.0f} env-steps/s)")
     return trainer

@@ -60,3 +60,9 @@ class CleanRlPpoActorCriticCfg:
     #: replay the update phase of an iteration from a hipGraph (needs rng="device"); None = automatic: on for
     #: minibatches <= 4096 samples, where the optimiser step is launch bound
     graph_update: object = None
+    #: write ``state_<it>.pt`` - the whole run state: optimiser, iteration state, rollout carry-over, env - beside every
+    #: ``model_<it>.pt`` (cleanrl/checkpoint.py); ``keep_states`` newest ones are kept (0 = all)
+    save_state: bool = True
+    keep_states: int = 2
+    #: continue the latest run (``load_run`` / ``load_checkpoint``) from its run state in a new run directory (--resume)
+    resume: bool = False

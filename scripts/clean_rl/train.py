@@ -11,6 +11,13 @@ only AppLauncher's argument definitions are picked up when IsaacLab happens to b
 like there (train.py:57-61,92) they are moved to ``sys.argv`` after argparse and applied by the ``hydra_task_config``
 decorator BEFORE ``main``'s body, so the explicit flags (--num_envs, --seed, --num_iterations, --device) win over them.
 ``cat_envs.shim.hydra_task_config`` resolves them without hydra; IsaacLab's own decorator is used when it is importable.
+
+``--resume True`` continues a run that was stopped or killed: the latest run directory under the task's log root that
+matches ``--load_run`` (default: any) and in it the highest-numbered ``state_<it>.pt`` (``--checkpoint model_N.pt`` selects
+``state_N.pt``).  The run state holds the optimiser, the iteration state, the rollout carry-over and the env, so the
+continuation computes what the uninterrupted run would have, bit for bit, given the same command line.  It writes to a NEW
+time-stamped run directory, whose ``params/resumed_from.txt`` names the state file.  ``--stop_after K`` leaves after
+iteration K while the schedules keep following ``--num_iterations``.
 """
 import argparse
 import os
@@ -36,6 +43,8 @@ def build_parser():
     parser.add_argument("--task", type=str, default=None, help="Name of the task.")
     parser.add_argument("--seed", type=int, default=None, help="Seed used for the environment")
     parser.add_argument("--num_iterations", type=int, default=None, help="RL Policy training iterations.")
+    parser.add_argument("--stop_after", type=int, default=None,
+                        help="Leave after this iteration (schedules still follow --num_iterations); go on with --resume True.")
     cli_args.add_clean_rl_args(parser)
     try:  # AppLauncher contributes --headless / --device / ... when Isaac Sim exists
         from isaaclab.app import AppLauncher
@@ -120,8 +129,23 @@ def _main(args_cli):
 
         log_root_path = os.path.abspath(os.path.join("logs", "clean_rl", agent_cfg.experiment_name))
         print(f"[INFO] Logging experiment in directory: {log_root_path}")
+        resume_state = None
+        if bool(getattr(agent_cfg, "resume", False)):
+            if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+                raise NotImplementedError("--resume: run states of env-sharded runs (torchrun, world > 1) are not implemented: "
+                                          "every rank's env shard would need a file of its own")
+            from cat_envs.tasks.utils.cleanrl.checkpoint import find_state
+            # resolved BEFORE this run's own directory exists (it would be the latest, and empty)
+            resume_state = os.path.abspath(find_state(log_root_path, agent_cfg.load_run, agent_cfg.load_checkpoint))
+            print(f"[INFO] Resuming from run state: {resume_state}")
         log_dir = os.path.join(log_root_path, datetime.now().strftime("%Y-%m-%d_%H-%M-%S"))
+        if resume_state is not None and os.path.dirname(resume_state) == log_dir:
+            raise RuntimeError(f"the resumed run would write into the run it resumes ({log_dir}): started within the same second")
         if rank == 0:
+            if resume_state is not None:
+                os.makedirs(os.path.join(log_dir, "params"), exist_ok=True)
+                with open(os.path.join(log_dir, "params", "resumed_from.txt"), "w") as f:
+                    f.write(resume_state + "\n")
             dump_cfg(os.path.join(log_dir, "params", "env.yaml"), env_cfg)
             dump_cfg(os.path.join(log_dir, "params", "agent.yaml"), agent_cfg)
             dump_cfg(os.path.join(log_dir, "params", "env.pkl"), env_cfg)
@@ -130,7 +154,11 @@ def _main(args_cli):
         env = make(args_cli.task, cfg=env_cfg, render_mode="rgb_array" if args_cli.video else None)
         if args_cli.video:
             print("[WARN] video recording needs Isaac Sim rendering; ignored with the synthetic simulator")
-        PPO(env, agent_cfg, log_dir)
+        # IsaacLab's env constructor seeds the global generators with env_cfg.seed; CaTEnv draws from generators of its own,
+        # so it is done here: the Agent's orthogonal initialisation (and rng="torch") then follow --seed, and two runs of
+        # one command line - or a stopped, resumed run and the uninterrupted one - compute the same
+        torch.manual_seed(int(env_cfg.seed))
+        PPO(env, agent_cfg, log_dir, resume_state=resume_state, stop_after=args_cli.stop_after)
         env.close()
 
     run()
