@@ -19,6 +19,7 @@ No host synchronisation happens inside ``step``: resets are handled with masks
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 import os
@@ -320,6 +321,15 @@ class _CurriculumManager:
     def reset(self, env_ids=None):
         return {k: v for k, v in self._state.items() if isinstance(v, (int, float))}
 
+    @contextlib.contextmanager
+    def frozen(self):
+        """no term runs inside the block: ``max_p`` of every constraint term stays what it is"""
+        keyed, self._keyed = self._keyed, []
+        try:
+            yield
+        finally:
+            self._keyed = keyed
+
     # run state: the logged scalars and, for every constraint term, the ``max_p`` the curriculum has reached (a Python
     # double on the term cfg; it reaches the device as a launch argument of the next step)
     def state_dict(self) -> dict:
@@ -430,6 +440,23 @@ class CaTEnv:
     def set_eval_record(self, record: torch.Tensor | None):
         """attach (or, with None, detach) the simulator's per-env evaluation record [N, 12]"""
         self._servo_sim().set_eval_record(record)
+
+    def fresh_cat_state(self):
+        """the constraint manager's state as at construction, in place (``ConstraintManager.fresh_state``); ``max_p`` of the
+        terms is left alone: it belongs to whoever drives the curriculum"""
+        if hasattr(self, "constraint_manager"):
+            self.constraint_manager.fresh_state()
+
+    @contextlib.contextmanager
+    def curriculum_frozen(self):
+        """inside the block the curriculum does not run and afterwards its step counter stands where it stood: stepping
+        the env in here moves no ``max_p``, now or later"""
+        counter = self.common_step_counter
+        try:
+            with self.curriculum_manager.frozen():
+                yield
+        finally:
+            self.common_step_counter = counter
 
     # run state (DESIGN section 10) ----------------------------------------------------------------
     def _state_tensors(self) -> dict:

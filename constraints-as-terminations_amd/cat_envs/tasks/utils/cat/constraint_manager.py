@@ -498,6 +498,23 @@ class ConstraintManager(ManagerBase):
         self._log_pos = int(sd["log_pos"])
         self._desc_dirty = True              # the next step re-checks the descriptor table against the restored term cfgs
 
+    def fresh_state(self):
+        """Everything a step reads that an earlier step wrote, as at construction: running maxima zero with the
+        first-call flag set (the next step takes the column maxima as they are), constraint / probability tiles, episode
+        sums and the log ring zero, the ring at slot 0.  In place (``zero_``): the descriptor table, the fused step's
+        argument block and captured graphs hold the addresses of these tensors.  ``max_p`` and the term parameters are not
+        state of this kind and stay."""
+        if self._class_term_cfgs:
+            raise NotImplementedError("fresh_state: class-based constraint terms keep state of their own")
+        if not self._term_names:
+            return
+        if not self._bound:
+            self._bind(native.get(self._device))
+        for t in self._state_tensors().values():
+            t.zero_()
+        self.cat._p_first = True
+        self._log_pos = 0
+
     @property
     def max_p(self) -> Dict[str, torch.Tensor]:
         return {n: torch.full((w,), c.max_p, dtype=torch.float, device=self._device)

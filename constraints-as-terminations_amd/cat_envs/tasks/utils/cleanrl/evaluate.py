@@ -106,7 +106,8 @@ class EvalResult:
         return json.dumps(d)
 
 
-def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool = True) -> EvalResult:
+def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool = True,
+                    fresh_cat_state: bool = False) -> EvalResult:
     """Roll ``policy`` out for ``steps`` control steps from a fresh reset and measure it.
 
     ``policy`` is an ``Agent`` - its observations are normalised by the frozen ``obs_rms`` and the action is the mean
@@ -116,7 +117,15 @@ def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool 
 
     Use a dedicated env: its episode counters, reset masks, action history and constraint episode sums are zeroed, the
     simulator is reset, and the env is LEFT IN THE EVALUATED STATE (the record and the command table are detached again,
-    also when the roll-out raises).  The loop never synchronises the host."""
+    also when the roll-out raises).  The loop never synchronises the host.
+
+    ``fresh_cat_state=True`` also starts the env's CaT state as at construction (``CaTEnv.fresh_cat_state``: running maxima
+    and their first-call flag, probability buffers, episode sums, log ring - all in place) and keeps the curriculum from
+    running for the length of the evaluation, so every term's ``max_p`` is what the caller set through ``set_term_cfg``.  The
+    result is then a function of the parameters, the observation normaliser, the ``max_p`` vector, the env cfg and seed,
+    ``steps`` and ``commands`` alone: two such evaluations agree bit for bit whatever the env did in between (DESIGN
+    section 11).  The default leaves the CaT state as the env's last step left it."""
+    import contextlib
     import torch
     from cat_envs.tasks.utils.cleanrl.ppo import Agent
     steps = int(steps)
@@ -128,7 +137,9 @@ def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool 
     n, dev = u.num_envs, u.device
     record = torch.zeros(n, len(FIELDS), device=dev)
     table = None
-    if commands is not None:
+    if isinstance(commands, torch.Tensor) and commands.device == dev and commands.dtype == torch.float32:
+        table = commands.detach().reshape(n, 3).contiguous().clone()       # a table of its own, without a host round trip
+    elif commands is not None:
         table = torch.as_tensor(np.asarray(commands.detach().cpu() if isinstance(commands, torch.Tensor) else commands,
                                            np.float32)).reshape(n, 3).contiguous().to(dev)
     if isinstance(policy, Agent):
@@ -149,6 +160,10 @@ def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool 
         cm._ep_viol.zero_()
         cm._ep_prob.zero_()
     u.set_eval_record(record)                                         # TypeError on the stream simulator
+    frozen = contextlib.ExitStack()
+    if fresh_cat_state:
+        u.fresh_cat_state()
+        frozen.enter_context(u.curriculum_frozen())
     try:
         u.set_fixed_commands(table)
         obs = env.reset()[0]["policy"]
@@ -168,6 +183,7 @@ def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool 
                     viol[:, :-1].add_(hit)
                     viol[:, -1].add_(hit.any(1))
     finally:
+        frozen.close()
         u.set_eval_record(None)
         u.set_fixed_commands(None)
     res = EvalResult(per_env=record.cpu().numpy(), commands=None if table is None else table.cpu().numpy(),

@@ -354,9 +354,13 @@ class RolloutSink:
 class PPOTrainer:
     """State of one ``PPO()`` run; ``run_iteration`` is one pass of the hot path."""
 
-    def __init__(self, envs, ppo_cfg, run_path=None, writer=None, agent: Agent | None = None):
+    def __init__(self, envs, ppo_cfg, run_path=None, writer=None, agent: Agent | None = None, eval_env=None):
+        from . import periodic_eval
         c = ppo_cfg
         self.cfg, self.envs, self.run_path, self.writer = c, envs, run_path, writer
+        # periodic evaluation (cfg eval_interval > 0, DESIGN section 11): refused here, before anything is built
+        eval_settings = periodic_eval.EvalSettings.from_cfg(c)
+        evaluating = periodic_eval.check_setup(eval_settings, eval_env, envs, parallel.world_size())
         if not torch.cuda.is_available():
             raise RuntimeError("PPO needs a HIP device (MI355X): every step of the update runs in libcatppo.so; "
                                "there is no CPU fallback")
@@ -436,7 +440,8 @@ class PPOTrainer:
         self.adv_stats = z(2)
         self.hp = native.PpoHparams(float(c.clip_coef), float(c.ent_coef), float(c.vf_coef), int(bool(c.norm_adv)),
                                     int(bool(c.clip_vloss)), 1.0 / self._mb_rows_global[0], 0)
-        self.nat.mlp_reserve(a.shape, max(self.M, N))
+        # (an evaluation forwards its eval env's rows: reserved NOW - a workspace that grows later drops the captured graph)
+        self.nat.mlp_reserve(a.shape, max(self.M, N, int(eval_env.unwrapped.num_envs) if evaluating else 0))
         self.iteration = 0
         self.global_step = 0
         # fused env step (two launches) when the env offers it
@@ -518,6 +523,8 @@ class PPOTrainer:
             self.stream.wait_stream(torch.cuda.current_stream(dev))
         self.time_phases = False
         self._phase_events = []
+        #: None unless cfg eval_interval > 0: then the iterations it names gain one evaluation each, the others nothing
+        self.evaluator = periodic_eval.PeriodicEvaluator(self, eval_env, eval_settings, run_path, writer) if evaluating else None
 
     def phase_summary(self, reset: bool = True):
         """mean device milliseconds per iteration of the three phases (needs ``time_phases = True``); synchronises"""
@@ -949,6 +956,9 @@ class PPOTrainer:
 
     def _run_iteration(self, eps_fn=None, perm_fn=None, log: bool = True):
         c = self.cfg
+        ev_run = self.evaluator
+        if ev_run is not None and self.iteration == 0:            # a fresh run: the untrained policy, recorded as iteration 0
+            ev_run.evaluate(0)
         self.iteration += 1
         it = self.iteration
         self.lr = float(c.learning_rate)
@@ -975,6 +985,8 @@ class PPOTrainer:
         self.obs[0].copy_(self.obs[self.T])
         self.dones[0].copy_(self.dones[self.T])
         self.true_dones[0].copy_(self.true_dones[self.T])
+        if ev_run is not None and it % ev_run.interval == 0:      # absolute iterations: a resumed run keeps the grid
+            ev_run.evaluate(it)
         if not log:
             return None
         if self.world > 1:
@@ -1028,16 +1040,18 @@ class PPOTrainer:
             self.writer.add_scalar(key if "/" in key else "Episode/" + key, value, it)
 
 
-def PPO(envs, ppo_cfg, run_path, resume_state=None, stop_after=None):
+def PPO(envs, ppo_cfg, run_path, resume_state=None, stop_after=None, eval_env=None):
     """Train with CleanRL-style PPO on CaT float dones (reference ppo.py:126-372).
 
     ``resume_state``: path of a run state (``state_<it>.pt``, written beside every ``model_<it>.pt``): the run continues
     with iteration ``it + 1`` exactly as the run that wrote it would have.  ``stop_after``: leave after that iteration
-    (what a killed run looks like; the schedules still follow ``num_iterations``)."""
+    (what a killed run looks like; the schedules still follow ``num_iterations``).  ``eval_env``: the dedicated env of the
+    periodic evaluation (cfg ``eval_interval > 0``; ``periodic_eval.make_eval_env``); a resumed run starts from the
+    ``model_best.pt`` / ``eval/best.json`` of the run it continues."""
     writer = _make_writer(ppo_cfg, run_path)
     if not os.path.exists(run_path):
         os.makedirs(run_path)
-    trainer = PPOTrainer(envs, ppo_cfg, run_path, writer)
+    trainer = PPOTrainer(envs, ppo_cfg, run_path, writer, eval_env=eval_env)
     total = int(ppo_cfg.num_iterations)
     first = 1
     if resume_state is not None:
@@ -1047,6 +1061,10 @@ def PPO(envs, ppo_cfg, run_path, resume_state=None, stop_after=None):
                              f"num_iterations={total} (raise --num_iterations to extend the run)")
         first = trainer.iteration + 1
         print(f"Resuming from {resume_state} at iteration {first}")
+        if trainer.evaluator is not None:
+            best = trainer.evaluator.carry_over_from(os.path.dirname(os.path.abspath(resume_state)))
+            if best is not None:
+                print(f"[INFO] Carried over the best evaluation so far: {best['metric']} {best['value']:.6g} at iteration {best['iteration']}")
     last = total if stop_after is None else min(total, int(stop_after))
     print(f"Starting training for {ppo_cfg.num_iterations} steps")
     t0, steps0 = time.time(), trainer.global_step
@@ -1056,4 +1074,6 @@ def PPO(envs, ppo_cfg, run_path, resume_state=None, stop_after=None):
     dt = time.time() - t0
     steps = trainer.global_step - steps0
     print(f"[PPO] {steps} env steps in {dt:.2f} s ({steps / max(dt, 1e-9):,.0f} env-steps/s)")
+    if trainer.evaluator is not None and trainer.evaluator.tracker.summary() is not None:
+        print(trainer.evaluator.tracker.summary())
     return trainer

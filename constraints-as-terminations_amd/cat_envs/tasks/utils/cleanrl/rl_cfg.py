@@ -66,3 +66,13 @@ class CleanRlPpoActorCriticCfg:
     keep_states: int = 2
     #: continue the latest run (``load_run`` / ``load_checkpoint``) from its run state in a new run directory (--resume)
     resume: bool = False
+    #: evaluate the deterministic policy on a dedicated env every ``eval_interval`` iterations (0 = never) and before the
+    #: first one: ``eval_envs`` envs for ``eval_steps`` control steps on the fixed command grid ``eval_grid`` (points per
+    #: axis vx, vy, wz); ``Eval/*`` scalars, ``<run>/eval/history.jsonl`` and - ``save_best`` - ``model_best.pt`` for the
+    #: highest ``eval_metric`` (cleanrl/periodic_eval.py; closed-loop servo tasks, single process)
+    eval_interval: int = 0
+    eval_envs: int = 256
+    eval_steps: int = 200
+    eval_grid: tuple = (4, 4, 2)
+    eval_metric: str = "reward_per_step"
+    save_best: bool = True

@@ -17,6 +17,19 @@ def add_clean_rl_args(parser: argparse.ArgumentParser):
                        help="Name of the logging project when using wandb")
 
 
+def add_eval_args(parser: argparse.ArgumentParser):
+    """evaluation inside the run (train.py; play.py has --eval_steps / --eval_grid of its own for one checkpoint)"""
+    group = parser.add_argument_group("periodic evaluation", description="Evaluate the policy while training (servo tasks).")
+    group.add_argument("--eval_interval", type=int, default=None, metavar="K",
+                       help="Evaluate before the first iteration and after every K-th (0: never).")
+    group.add_argument("--eval_envs", type=int, default=None, metavar="N", help="Envs of the dedicated eval env.")
+    group.add_argument("--eval_steps", type=int, default=None, metavar="S", help="Control steps of one evaluation.")
+    group.add_argument("--eval_grid", type=int, nargs=3, default=None, metavar=("NX", "NY", "NW"),
+                       help="Fixed commands: a grid of NX x NY x NW points over the command ranges.")
+    group.add_argument("--eval_metric", type=str, default=None, metavar="NAME",
+                       help="The metric whose highest value selects model_best.pt.")
+
+
 def parse_clean_rl_cfg(task_name: str, args_cli: argparse.Namespace):
     from cat_envs.shim import load_cfg_from_registry
     return update_clean_rl_cfg(load_cfg_from_registry(task_name, "clean_rl_cfg_entry_point"), args_cli)
@@ -36,4 +49,14 @@ def update_clean_rl_cfg(agent_cfg, args_cli: argparse.Namespace):
         agent_cfg.logger = args_cli.logger
     if agent_cfg.logger in {"wandb"} and args_cli.log_project_name:
         agent_cfg.wandb_project = args_cli.log_project_name
+    return agent_cfg
+
+
+def update_eval_cfg(agent_cfg, args_cli: argparse.Namespace):
+    """the flags of ``add_eval_args`` over the task's runner configuration (all of which default to "off")"""
+    for name in ("eval_interval", "eval_envs", "eval_steps", "eval_metric"):
+        if getattr(args_cli, name, None) is not None:
+            setattr(agent_cfg, name, getattr(args_cli, name))
+    if getattr(args_cli, "eval_grid", None) is not None:
+        agent_cfg.eval_grid = tuple(args_cli.eval_grid)
     return agent_cfg

@@ -18,6 +18,12 @@ matches ``--load_run`` (default: any) and in it the highest-numbered ``state_<it
 continuation computes what the uninterrupted run would have, bit for bit, given the same command line.  It writes to a NEW
 time-stamped run directory, whose ``params/resumed_from.txt`` names the state file.  ``--stop_after K`` leaves after
 iteration K while the schedules keep following ``--num_iterations``.
+
+``--eval_interval K`` (closed-loop servo tasks, one process) evaluates the deterministic policy inside the run: before the
+first iteration and after every K-th, on a dedicated env of ``--eval_envs N`` envs for ``--eval_steps S`` control steps on the
+command grid ``--eval_grid NX NY NW``.  The run directory gains ``Eval/*`` scalars, ``eval/history.jsonl``, ``eval/best.json``
+and ``model_best.pt`` - the policy with the highest ``--eval_metric NAME`` - and the run ends with one line
+``[EVAL] best <metric> <value> at iteration <it>``.  A resumed run starts from the best of the run it continues.
 """
 import argparse
 import os
@@ -46,6 +52,7 @@ def build_parser():
     parser.add_argument("--stop_after", type=int, default=None,
                         help="Leave after this iteration (schedules still follow --num_iterations); go on with --resume True.")
     cli_args.add_clean_rl_args(parser)
+    cli_args.add_eval_args(parser)
     try:  # AppLauncher contributes --headless / --device / ... when Isaac Sim exists
         from isaaclab.app import AppLauncher
         AppLauncher.add_app_launcher_args(parser)
@@ -112,6 +119,7 @@ def _main(args_cli):
     def run(env_cfg, agent_cfg):
         # override configurations with the non-hydra CLI arguments (reference train.py:98-107)
         agent_cfg = cli_args.update_clean_rl_cfg(agent_cfg, args_cli)
+        agent_cfg = cli_args.update_eval_cfg(agent_cfg, args_cli)
         env_cfg.scene.num_envs = args_cli.num_envs if args_cli.num_envs is not None else env_cfg.scene.num_envs
         agent_cfg.num_iterations = (args_cli.num_iterations if args_cli.num_iterations is not None
                                     else agent_cfg.num_iterations)
@@ -157,9 +165,17 @@ def _main(args_cli):
         # IsaacLab's env constructor seeds the global generators with env_cfg.seed; CaTEnv draws from generators of its own,
         # so it is done here: the Agent's orthogonal initialisation (and rng="torch") then follow --seed, and two runs of
         # one command line - or a stopped, resumed run and the uninterrupted one - compute the same
+        eval_env = None
+        if int(getattr(agent_cfg, "eval_interval", 0) or 0) > 0:
+            # the dedicated env of the periodic evaluation: the training env's cfg with eval_envs envs, no curriculum and a
+            # seed derived from the training seed (periodic_eval.make_eval_env_cfg)
+            from cat_envs.tasks.utils.cleanrl.periodic_eval import make_eval_env
+            eval_env = make_eval_env(args_cli.task, env_cfg, int(agent_cfg.eval_envs))
         torch.manual_seed(int(env_cfg.seed))
-        PPO(env, agent_cfg, log_dir, resume_state=resume_state, stop_after=args_cli.stop_after)
+        PPO(env, agent_cfg, log_dir, resume_state=resume_state, stop_after=args_cli.stop_after, eval_env=eval_env)
         env.close()
+        if eval_env is not None:
+            eval_env.close()
 
     run()
 
