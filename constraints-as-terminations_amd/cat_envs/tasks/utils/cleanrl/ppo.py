@@ -370,6 +370,9 @@ class PPOTrainer:
         self.batch = self.T * self.N
         self.mb = int(c.minibatch_size)
         self.world, self.rank = parallel.world_size(), parallel.rank()
+        #: (run directory of the run states, cfg save_state, cfg keep_states); env-sharded runs take rank 0's (below)
+        self._state_plan = (None if run_path is None else os.path.abspath(run_path), bool(getattr(c, "save_state", True)),
+                            int(getattr(c, "keep_states", 2)))
         hidden = tuple(getattr(c, "hidden", None) or DEFAULT_HIDDEN)
         self.agent = agent if agent is not None else Agent(
             envs, hidden=hidden, mlp_precision=str(getattr(c, "mlp_precision", "fp32"))).to(self.device)
@@ -394,6 +397,12 @@ class PPOTrainer:
         if parallel.active():
             parallel.init_native_comm(self.nat)                 # RCCL under the C ABI (catppo_comm_init)
             parallel.broadcast_(a.flat, src=0)                  # replicas start identical (cf. skrl ppo.py:126-131)
+            if self.world > 1:
+                # run states (section 10): the files of ALL ranks go into rank 0's run directory, and whether and how many
+                # are kept is rank 0's cfg - so that no rank enters a save vote its peers do not (once, at construction)
+                plan = [self._state_plan]
+                torch.distributed.broadcast_object_list(plan, src=0)
+                self._state_plan = plan[0]
             a.obs_rms.dist_group = a.value_rms.dist_group = torch.distributed.group.WORLD
             cm = getattr(envs.unwrapped, "constraint_manager", None)
             if cm is not None and getattr(c, "dist_exact", True):
@@ -824,11 +833,10 @@ class PPOTrainer:
         self.adam_step += self._update_body(perms)
 
     # ------------------------------------------------------------------ run state
-    _SHARDED_STATE = ("run states of env-sharded runs (world > 1) are not implemented: every rank owns its own env shard, "
-                      "which would need a file of its own, and nothing here can test more than two ranks on one device")
-
     def state_fingerprint(self) -> dict:
-        """everything that must be equal for a saved state to continue THIS run (checkpoint.check_fingerprint)"""
+        """everything that must be equal for a saved state to continue THIS run (checkpoint.check_fingerprint); an
+        env-sharded run adds its rank (env count, env seed and env offset already differ between the ranks)"""
+        from . import checkpoint
         env_u = self.envs.unwrapped
         if not hasattr(env_u, "state_fingerprint"):
             raise NotImplementedError(f"run state: {type(env_u).__name__} has no state_fingerprint() / state_dict()")
@@ -840,7 +848,7 @@ class PPOTrainer:
                    "lr_schedule": self.lr_schedule, "world": int(self.world),
                    "sizeof_iter_state": int(C.sizeof(native.IterState)),
                    "catppo_version": int(self.nat.lib.catppo_version())})
-        return fp
+        return checkpoint.rank_fingerprint(fp, self.world, self.rank)
 
     def _schedule_fields(self) -> dict:
         """recorded, not compared: a user may extend a run or change a coefficient"""
@@ -851,13 +859,10 @@ class PPOTrainer:
                    clip_vloss=bool(c.clip_vloss), seed=int(getattr(c, "seed", 0)))
         return out
 
-    def save_state(self, path: str) -> str:
-        """Write the whole run state to ``path`` (atomically).  Only legal at an iteration boundary - after
-        ``run_iteration`` has returned, or straight after construction.  One device synchronisation; the copies to the host
-        that follow find the device idle."""
+    def _state_payload(self) -> dict:
+        """this process's run state as ``checkpoint.write_state`` takes it (the tensors are the live ones: it copies them).
+        One device synchronisation; the copies to the host that follow find the device idle."""
         from . import checkpoint
-        if self.world > 1:
-            raise NotImplementedError(self._SHARDED_STATE)
         fp = self.state_fingerprint()
         env_sd = self.envs.unwrapped.state_dict()             # raises while an evaluation is attached
         torch.cuda.synchronize()
@@ -875,24 +880,79 @@ class PPOTrainer:
               "eager_updates_left": int(self._eager_updates_left), "schedule": self._schedule_fields()}
         if self.rng == "torch":
             tr["torch_rng"] = {"cpu": torch.get_rng_state(), "device": torch.cuda.get_rng_state(self.device)}
-        return checkpoint.write_state(path, {"format": checkpoint.FORMAT, "fingerprint": fp, "trainer": tr, "env": env_sd})
+        return {"format": checkpoint.FORMAT, "fingerprint": fp, "trainer": tr, "env": env_sd}
+
+    def save_state(self, path: str) -> str:
+        """Write the whole run state to ``path`` (atomically).  Only legal at an iteration boundary - after
+        ``run_iteration`` has returned, or straight after construction.
+
+        Env-sharded run (``world > 1``): COLLECTIVE - every rank calls it with the same ``path``, rank 0's
+        ``state_<it>.pt``.  Rank r >= 1 writes ``state_<it>.rank<r>.pt`` beside it, the ranks vote, and only when every
+        rank wrote its file does rank 0 write ``path``, which commits the set; otherwise this iteration's files are removed
+        and every rank raises ``RuntimeError`` naming the failing ranks.  Returns the path of this rank's file."""
+        from . import checkpoint
+        if self.world > 1:
+            return self._save_state_set(path)
+        return checkpoint.write_state(path, self._state_payload())
+
+    def _save_state_set(self, path: str) -> str:
+        import uuid
+        from . import checkpoint
+        dist = torch.distributed
+        mine, payload, err = None, None, None
+        try:
+            mine = checkpoint.sibling_path(path, self.rank)
+            payload = self._state_payload()
+        except Exception as e:                                   # said in the vote: the peers must not wait for this rank
+            err = f"{type(e).__name__}: {e}"
+        # one token per save (never from a torch generator: rng="torch" runs stay bit-identical): files of two saves of one
+        # iteration are told apart when they are loaded
+        token = [uuid.uuid4().hex if self.rank == 0 else None]
+        dist.broadcast_object_list(token, src=0)
+        if payload is not None:
+            payload["trainer"]["set"] = {"world": int(self.world), "rank": int(self.rank), "token": str(token[0])}
+        wrote = False
+        if err is None and self.rank > 0:
+            try:
+                checkpoint.write_state(mine, payload)
+                wrote = True
+            except Exception as e:
+                err = f"{type(e).__name__}: {e}"
+        votes = [None] * self.world
+        dist.all_gather_object(votes, err)
+        bad = [(r, v) for r, v in enumerate(votes) if v is not None]
+        it = checkpoint.state_iteration(path)
+        if bad:
+            if wrote:
+                try:
+                    os.remove(mine)
+                except FileNotFoundError:
+                    pass
+            if self.rank == 0 and it is not None:
+                checkpoint.remove_siblings(os.path.dirname(path) or ".", it)
+            raise RuntimeError(f"{path}: the run state of {self.world} ranks was not written ({len(bad)} rank(s) failed; this "
+                               "iteration's files are removed): " + "; ".join(f"rank {r}: {v}" for r, v in bad))
+        if self.rank == 0:
+            try:
+                checkpoint.write_state(mine, payload)            # the commit: from here on the set exists
+            except BaseException:
+                if it is not None:
+                    checkpoint.remove_siblings(os.path.dirname(path) or ".", it)
+                raise
+        return mine
 
     _STATE_KEYS = ("agent", "exp_avg", "exp_avg_sq", "iter_state", "sizeof_iter_state", "iter_state_fields", "adam_step",
                    "iteration", "global_step", "obs0", "dones0", "true_dones0", "kl_buf", "eager_updates_left", "schedule")
 
-    def load_state(self, path: str) -> dict:
-        """Continue from the run state in ``path``: afterwards the next ``run_iteration`` is iteration ``saved + 1`` of the
-        run that wrote it, bit for bit.  The fingerprint and every shape are checked BEFORE anything is written - a refused
-        load leaves trainer and env as they were.  Loads in place (``copy_``); a captured update graph is dropped and
-        captured again; the launch-time switches (graph_update, one_call_step, defer_tail, ...) stay as this process chose
-        them.  Returns the file's ``trainer`` section."""
+    def _read_checked(self, path: str):
+        """everything a load does BEFORE it writes: read ``path``, fingerprint, required keys, every tensor's shape and
+        dtype in trainer, env, manager and simulator.  Returns (payload, [(name, own tensor, saved tensor)])."""
         from . import checkpoint
-        if self.world > 1:
-            raise NotImplementedError(self._SHARDED_STATE)
         payload = checkpoint.read_state(path)
         checkpoint.check_fingerprint(payload["fingerprint"], self.state_fingerprint(), path)
         tr, env_u = payload["trainer"], self.envs.unwrapped
-        checkpoint.require(tr, self._STATE_KEYS + (("torch_rng",) if self.rng == "torch" else ()), path, "trainer")
+        checkpoint.require(tr, self._STATE_KEYS + (("torch_rng",) if self.rng == "torch" else ())
+                           + (("set",) if self.world > 1 else ()), path, "trainer")
         own = self.agent.state_dict()
         pairs = [(f"agent.{k}", own[k], tr["agent"].get(k)) for k in own]
         pairs += [("exp_avg", self.exp_avg, tr["exp_avg"]), ("exp_avg_sq", self.exp_avg_sq, tr["exp_avg_sq"]),
@@ -908,6 +968,47 @@ class PPOTrainer:
             env_u.check_state_dict(payload["env"])
         except (ValueError, KeyError) as e:
             raise ValueError(f"{path}: {e}") from e
+        return payload, pairs
+
+    def _read_checked_set(self, path: str):
+        """``_read_checked`` of this rank's file of the set that ``path`` (rank 0's file) names, then ONE vote: the load
+        goes on only if every rank's file passed and the files are one save of this world - same token, iteration and
+        optimiser step count, written by ``world`` ranks, each by the rank that reads it.  Otherwise every rank raises
+        ``ValueError`` naming each offending rank, and no rank has written a byte."""
+        from . import checkpoint
+        payload = pairs = err = None
+        rec = (None,) * 5
+        try:
+            mine = checkpoint.sibling_path(path, self.rank)
+            if not os.path.isfile(mine):
+                raise FileNotFoundError(f"{mine} does not exist: rank {self.rank}'s file of the set is missing")
+            payload, pairs = self._read_checked(mine)
+            tr = payload["trainer"]
+            checkpoint.require(tr["set"], ("world", "rank", "token"), mine, "trainer.set")
+            rec = (int(tr["set"]["world"]), int(tr["set"]["rank"]), str(tr["set"]["token"]), int(tr["iteration"]),
+                   int(tr["adam_step"]))
+        except Exception as e:                                   # said in the vote: the peers must not wait for this rank
+            err = f"{type(e).__name__}: {e}"
+        votes = [None] * self.world
+        torch.distributed.all_gather_object(votes, (err,) + rec)
+        bad = checkpoint.check_set_votes(votes)
+        if bad:
+            short = lambda r, m: m if r == self.rank or len(m) <= 600 else m[:600] + " ..."
+            raise ValueError(f"{path}: the run state of {self.world} ranks was refused by {len(bad)} rank(s) and nothing was "
+                             "loaded on any rank: " + "; ".join(f"rank {r}: {short(r, m)}" for r, m in bad))
+        return payload, pairs
+
+    def load_state(self, path: str) -> dict:
+        """Continue from the run state in ``path``: afterwards the next ``run_iteration`` is iteration ``saved + 1`` of the
+        run that wrote it, bit for bit.  The fingerprint and every shape are checked BEFORE anything is written - a refused
+        load leaves trainer and env as they were.  Loads in place (``copy_``); a captured update graph is dropped and
+        captured again; the launch-time switches (graph_update, one_call_step, defer_tail, ...) stay as this process chose
+        them.  Returns the file's ``trainer`` section.
+
+        Env-sharded run (``world > 1``): COLLECTIVE - every rank calls it with the same ``path``, rank 0's
+        ``state_<it>.pt``, and reads its own file of the set; all ranks load or none does (``_read_checked_set``)."""
+        payload, pairs = self._read_checked_set(path) if self.world > 1 else self._read_checked(path)
+        tr, env_u = payload["trainer"], self.envs.unwrapped
         # -- nothing was written up to here ---------------------------------------------------------------------------
         torch.cuda.synchronize()
         if self._graph_id is not None:                           # captured again by the next update phase
@@ -919,7 +1020,12 @@ class PPOTrainer:
         env_u.load_state_dict(payload["env"])
         self.adam_step, self.iteration = int(tr["adam_step"]), int(tr["iteration"])
         self.global_step = int(tr["global_step"])
-        self._eager_updates_left = int(tr["eager_updates_left"])
+        left = int(tr["eager_updates_left"])
+        if self.world > 1:
+            # the eager first update phase of an env-sharded run warms up the PROCESS's communicator outside a stream
+            # capture (see update()): a process that has not run one yet still owes it, whatever the saving process had done
+            left = max(left, self._eager_updates_left)
+        self._eager_updates_left = left
         if self.rng == "torch":
             torch.set_rng_state(tr["torch_rng"]["cpu"])
             torch.cuda.set_rng_state(tr["torch_rng"]["device"], self.device)
@@ -931,14 +1037,18 @@ class PPOTrainer:
         return tr
 
     def _save_run_state(self, it: int):
-        """``state_<it>.pt`` beside ``model_<it>.pt`` (rank 0, cfg ``save_state``), older ones pruned (``keep_states``)"""
+        """``state_<it>.pt`` beside ``model_<it>.pt`` (rank 0, cfg ``save_state``), older ones pruned (``keep_states``).
+        Env-sharded run: called on EVERY rank (``save_state`` is collective there); directory and switches are rank 0's."""
         from . import checkpoint
-        if not bool(getattr(self.cfg, "save_state", True)):
-            return
         if self.world > 1:
-            if not getattr(self, "_sharded_note", False):
-                self._sharded_note = True
-                print(f"[catppo] no run state is written: {self._SHARDED_STATE}")
+            run_dir, on, keep = self._state_plan
+            if run_dir is None or not on:
+                return
+            self.save_state(os.path.join(run_dir, f"state_{it}.pt"))
+            if self.rank == 0:
+                checkpoint.prune_states(run_dir, keep, siblings=True)
+            return
+        if not bool(getattr(self.cfg, "save_state", True)):
             return
         self.save_state(f"{self.run_path}/state_{it}.pt")
         checkpoint.prune_states(self.run_path, int(getattr(self.cfg, "keep_states", 2)))
@@ -1010,7 +1120,10 @@ class PPOTrainer:
         if self.run_path is not None and self.rank == 0 and (it + 1) % c.save_interval == 0:
             torch.save(self.agent.state_dict(), f"{self.run_path}/model_{it}.pt")     # same off-by-one naming
             print("Saved model")
-            self._save_run_state(it)                             # (only where a model is written: no further sync elsewhere)
+            if self.world == 1:
+                self._save_run_state(it)                         # (only where a model is written: no further sync elsewhere)
+        if self.world > 1 and (it + 1) % c.save_interval == 0:
+            self._save_run_state(it)                             # every rank: its own file, and the vote that commits the set
         return stats
 
     def _log_episode_infos(self, ep_infos, it):
@@ -1044,13 +1157,14 @@ def PPO(envs, ppo_cfg, run_path, resume_state=None, stop_after=None, eval_env=No
     """Train with CleanRL-style PPO on CaT float dones (reference ppo.py:126-372).
 
     ``resume_state``: path of a run state (``state_<it>.pt``, written beside every ``model_<it>.pt``): the run continues
-    with iteration ``it + 1`` exactly as the run that wrote it would have.  ``stop_after``: leave after that iteration
+    with iteration ``it + 1`` exactly as the run that wrote it would have (env-sharded runs: rank 0's ``state_<it>.pt`` and
+    the same ``run_path`` on every rank; every rank loads its own file of the set).  ``stop_after``: leave after that iteration
     (what a killed run looks like; the schedules still follow ``num_iterations``).  ``eval_env``: the dedicated env of the
     periodic evaluation (cfg ``eval_interval > 0``; ``periodic_eval.make_eval_env``); a resumed run starts from the
     ``model_best.pt`` / ``eval/best.json`` of the run it continues."""
-    writer = _make_writer(ppo_cfg, run_path)
-    if not os.path.exists(run_path):
-        os.makedirs(run_path)
+    # env-sharded runs: the ranks share rank 0's run directory (train.py), where rank 0 alone logs
+    writer = _make_writer(ppo_cfg, run_path) if parallel.rank() == 0 else None
+    os.makedirs(run_path, exist_ok=True)
     trainer = PPOTrainer(envs, ppo_cfg, run_path, writer, eval_env=eval_env)
     total = int(ppo_cfg.num_iterations)
     first = 1

@@ -19,6 +19,13 @@ continuation computes what the uninterrupted run would have, bit for bit, given 
 time-stamped run directory, whose ``params/resumed_from.txt`` names the state file.  ``--stop_after K`` leaves after
 iteration K while the schedules keep following ``--num_iterations``.
 
+Env-sharded runs (``torchrun``, one process per GPU) stop and go on the same way.  Rank 0 picks the run directory and all
+ranks use it: beside ``model_<it>.pt`` it holds ``state_<it>.pt`` (rank 0) and ``state_<it>.rank<r>.pt`` (the other ranks),
+one state that exists only as a whole.  ``--resume True`` under the same ``torchrun`` world size takes the newest
+``state_<it>.pt`` that has all its siblings beside it; rank 0 resolves it and hands the path (or its error) to the other
+ranks, every rank loads its own file, and either all ranks load or none does.  All ranks must see rank 0's directory (one
+node, or a shared file system); another world size is refused.
+
 ``--eval_interval K`` (closed-loop servo tasks, one process) evaluates the deterministic policy inside the run: before the
 first iteration and after every K-th, on a dedicated env of ``--eval_envs N`` envs for ``--eval_steps S`` control steps on the
 command grid ``--eval_grid NX NY NW``.  The run directory gains ``Eval/*`` scalars, ``eval/history.jsonl``, ``eval/best.json``
@@ -137,18 +144,37 @@ def _main(args_cli):
 
         log_root_path = os.path.abspath(os.path.join("logs", "clean_rl", agent_cfg.experiment_name))
         print(f"[INFO] Logging experiment in directory: {log_root_path}")
-        resume_state = None
-        if bool(getattr(agent_cfg, "resume", False)):
-            if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-                raise NotImplementedError("--resume: run states of env-sharded runs (torchrun, world > 1) are not implemented: "
-                                          "every rank's env shard would need a file of its own")
-            from cat_envs.tasks.utils.cleanrl.checkpoint import find_state
-            # resolved BEFORE this run's own directory exists (it would be the latest, and empty)
-            resume_state = os.path.abspath(find_state(log_root_path, agent_cfg.load_run, agent_cfg.load_checkpoint))
-            print(f"[INFO] Resuming from run state: {resume_state}")
-        log_dir = os.path.join(log_root_path, datetime.now().strftime("%Y-%m-%d_%H-%M-%S"))
-        if resume_state is not None and os.path.dirname(resume_state) == log_dir:
-            raise RuntimeError(f"the resumed run would write into the run it resumes ({log_dir}): started within the same second")
+        world = int(os.environ.get("WORLD_SIZE", "1"))
+
+        def resolve():
+            """(run state to resume from or None, this run's directory)"""
+            state = None
+            if bool(getattr(agent_cfg, "resume", False)):
+                from cat_envs.tasks.utils.cleanrl.checkpoint import find_state
+                # resolved BEFORE this run's own directory exists (it would be the latest, and empty); env-sharded runs:
+                # only a state_<it>.pt with the files of all ranks beside it counts
+                state = os.path.abspath(find_state(log_root_path, agent_cfg.load_run, agent_cfg.load_checkpoint, world=world))
+                print(f"[INFO] Resuming from run state: {state}")
+            run_dir = os.path.join(log_root_path, datetime.now().strftime("%Y-%m-%d_%H-%M-%S"))
+            if state is not None and os.path.dirname(state) == run_dir:
+                raise RuntimeError(f"the resumed run would write into the run it resumes ({run_dir}): started within the same second")
+            return state, run_dir
+
+        if world > 1:
+            # rank 0 decides for all ranks: two ranks can read the clock in different seconds, and they must load ONE state
+            # and write their run-state files into ONE directory.  An error of rank 0 is raised by every rank.
+            box = [None]
+            if rank == 0:
+                try:
+                    box = [(None,) + resolve()]
+                except Exception as e:
+                    box = [(f"{type(e).__name__}: {e}", None, None)]
+            torch.distributed.broadcast_object_list(box, src=0)
+            err, resume_state, log_dir = box[0]
+            if err is not None:
+                raise RuntimeError(f"rank 0 could not set the run up: {err}")
+        else:
+            resume_state, log_dir = resolve()
         if rank == 0:
             if resume_state is not None:
                 os.makedirs(os.path.join(log_dir, "params"), exist_ok=True)
