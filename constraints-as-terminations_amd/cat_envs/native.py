@@ -116,6 +116,20 @@ class ServoSim(C.Structure):
                 + [("fixed_command", C.c_void_p), ("eval", C.c_void_p)])
 
 
+#: one row of the step trace, CATPPO_SERVO_TRACE_FLOATS = 72 (288 bytes): (name, first float, width)
+SERVO_TRACE_FIELDS = (("t", 0, 1), ("ends", 1, 1), ("fallen", 2, 1), ("reward", 3, 1), ("command", 4, 3), ("v", 7, 3),
+                      ("roll", 10, 1), ("pitch", 11, 1), ("z", 12, 1), ("ncon", 13, 1), ("zero", 14, 2), ("contact", 16, 4),
+                      ("fz", 20, 4), ("q", 24, 12), ("qd", 36, 12), ("tau_w", 48, 12), ("action", 60, 12))
+SERVO_TRACE_FLOATS = 72
+
+
+class ServoSimStep(ServoSim):
+    """``ServoSim`` with the descriptor's step-response tail: the command schedule and the step trace.  This is the whole
+    catppo_servo_sim and what ``servo_sim_step`` takes; a zero-filled tail is the behaviour of the fields above alone."""
+    _fields_ = [("fixed_segments", C.c_int32), ("fixed_segment_steps", C.c_int32), ("trace", C.c_void_p),
+                ("trace_envs", C.c_int32), ("trace_capacity", C.c_int32)]
+
+
 F32, F16, F64 = 0, 1, 2                 # CATPPO_F32 / _F16 / _F64
 SUM, MAX = 0, 1                         # CATPPO_SUM / _MAX
 LR_FIXED, LR_LINEAR, LR_KEEP = 0, 1, 2
@@ -207,7 +221,7 @@ _SIGNATURES = {
     # ---- ABI 0.4
     "catppo_set_grad_overlap": (C.c_int, [_vp, C.c_int]),
     # ---- closed-loop Solo12 servo surrogate (one launch per env step)
-    "catppo_servo_sim_step": (C.c_int, [_vp, C.POINTER(ServoSim), _vp]),
+    "catppo_servo_sim_step": (C.c_int, [_vp, C.POINTER(ServoSimStep), _vp]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
@@ -714,8 +728,10 @@ class Native:
     def rollout_flush(self):
         self._ok(self.lib.catppo_rollout_defer_tail(self.h, -1, self._stream()))      # -1: flush, the mode stays
 
-    def servo_sim_step(self, desc: ServoSim):
+    def servo_sim_step(self, desc: ServoSimStep):
         """one control step (or, with ``desc.init``, the first state) of the Solo12 servo surrogate"""
+        if not isinstance(desc, ServoSimStep):              # the library reads the whole catppo_servo_sim, tail included
+            raise TypeError("servo_sim_step takes a native.ServoSimStep")
         rc = self.lib.catppo_servo_sim_step(self.h, C.byref(desc), self._stream())
         if rc:
             self._ok(rc)

@@ -202,7 +202,7 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         self.default_joint_pos = torch.tensor(DEFAULT_JOINT_POS, device=self.device).repeat(num_envs, 1).contiguous()
         self._episode_length, self._reset = episode_length, reset       # referenced by the descriptor: keep alive
         self._nat = native.get(self.device)
-        d = self._desc = native.ServoSim()
+        d = self._desc = native.ServoSimStep()
         d.N, d.env_offset, d.row_stride, d.row_floats = num_envs, int(env_offset), self.F, self.F
         d.obs_dim, d.H, d.B = obs_dim, H, B
         names = {"projected_gravity": "projected_gravity_b", "root_pos": "root_pos_w"}
@@ -216,28 +216,60 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         d.dt = dt
         for n in native.SERVO_CONSTANTS[1:]:
             setattr(d, n, float(getattr(syn, "servo_" + n)))
-        self._fixed_command = self._eval_record = None                  # referenced by the descriptor: keep alive
+        self._fixed_command = self._eval_record = self._trace = None    # referenced by the descriptor: keep alive
         self._build_scene()
 
-    def _table(self, t, width, what):
+    def _table(self, t, width, what, lead=()):
         if t is None:
             return None
+        shape = (*lead, self.N, width)
         if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_contiguous() and t.device == self.cur.device
-                and tuple(t.shape) == (self.N, width)):
-            raise ValueError(f"{what} must be a contiguous fp32 tensor of shape ({self.N}, {width}) on {self.cur.device}")
+                and tuple(t.shape) == shape):
+            raise ValueError(f"{what} must be a contiguous fp32 tensor of shape {shape} on {self.cur.device}")
         return t
 
-    def set_fixed_command(self, t: torch.Tensor | None):
+    def set_fixed_command(self, t: torch.Tensor | None, segment_steps: int | None = None):
         """``t`` [N, 3]: env i's command is row i in every step and every episode, as it stands (no dead zone, no standing
-        fraction); None: the simulator draws the commands itself again.  The kernel reads the tensor at every launch."""
-        self._fixed_command = self._table(t, 3, "fixed commands")
-        self._desc.fixed_command = None if t is None else t.data_ptr()
+        fraction); None: the simulator draws the commands itself again.  The kernel reads the tensor at every launch.
+
+        ``t`` [S, N, 3] with ``segment_steps`` = L >= 1 is a schedule: a step that starts at episode length ``k`` uses row
+        ``min(k // L, S - 1)`` of env i.  It is keyed on the episode length like command resampling, so an episode that
+        ends restarts its schedule at segment 0."""
+        if t is not None and isinstance(t, torch.Tensor) and t.dim() == 3:
+            if segment_steps is None or int(segment_steps) < 1:
+                raise ValueError("a command schedule [S, N, 3] needs segment_steps >= 1")
+            if t.shape[0] < 1:
+                raise ValueError("a command schedule needs at least one segment")
+            table, segments = self._table(t, 3, "a command schedule", lead=(int(t.shape[0]),)), int(t.shape[0])
+        else:
+            if segment_steps is not None:
+                raise ValueError("segment_steps goes with a command schedule [S, N, 3]")
+            table, segments = self._table(t, 3, "fixed commands"), 0
+        self._fixed_command = table
+        d = self._desc
+        d.fixed_command = None if table is None else table.data_ptr()
+        d.fixed_segments, d.fixed_segment_steps = segments, int(segment_steps) if segments else 0
 
     def set_eval_record(self, t: torch.Tensor | None):
         """``t`` [N, 12] (``native.SERVO_EVAL_FIELDS``): every following step adds its terms to row i of the record inside
         the simulator's own launch, ``reset()`` zeroes it; None: detach."""
         self._eval_record = self._table(t, len(native.SERVO_EVAL_FIELDS), "the evaluation record")
         self._desc.eval = None if t is None else t.data_ptr()
+
+    def set_trace(self, t: torch.Tensor | None):
+        """``t`` [T, K, 72] (``native.SERVO_TRACE_FIELDS``), zeroed by the caller: every following step writes one row per
+        env 0 .. K - 1 inside the simulator's own launch, at the slot the env's evaluation record has counted so far (so
+        an evaluation record must be attached while it steps); slots >= T are dropped.  None: detach."""
+        if t is not None:
+            ok = isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_contiguous() and t.device == self.cur.device
+            if not (ok and t.dim() == 3 and t.shape[0] >= 1 and 1 <= t.shape[1] <= self.N
+                    and t.shape[2] == native.SERVO_TRACE_FLOATS):
+                raise ValueError(f"the trace must be a contiguous fp32 tensor of shape (T >= 1, 1 <= K <= {self.N}, "
+                                 f"{native.SERVO_TRACE_FLOATS}) on {self.cur.device}")
+        self._trace = t
+        d = self._desc
+        d.trace = None if t is None else t.data_ptr()
+        d.trace_capacity, d.trace_envs = (0, 0) if t is None else (int(t.shape[0]), int(t.shape[1]))
 
     def reset(self):
         """the first state of episode 0 in the state buffer"""
@@ -273,8 +305,8 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         return {"servo": fp}
 
     def state_dict(self) -> dict:
-        if self._fixed_command is not None or self._eval_record is not None:
-            raise RuntimeError("run state: a fixed-command table or an evaluation record is attached to the simulator; "
+        if self._fixed_command is not None or self._eval_record is not None or self._trace is not None:
+            raise RuntimeError("run state: a fixed-command table, an evaluation record or a trace is attached to the simulator; "
                                "an evaluation is not a resumable state (detach them before saving)")
         return super().state_dict()
 
@@ -433,9 +465,14 @@ class CaTEnv:
                             "(SyntheticCfg.kind = 'servo'); the stream simulator is open loop")
         return self.sim
 
-    def set_fixed_commands(self, commands: torch.Tensor | None):
-        """per-env commands [N, 3] that replace the simulator's own draws (None: back to the draws)"""
-        self._servo_sim().set_fixed_command(commands)
+    def set_fixed_commands(self, commands: torch.Tensor | None, segment_steps: int | None = None):
+        """per-env commands [N, 3], or a schedule [S, N, 3] of ``segment_steps`` control steps per segment, that replace
+        the simulator's own draws (None: back to the draws)"""
+        self._servo_sim().set_fixed_command(commands, segment_steps)
+
+    def set_trace(self, trace: torch.Tensor | None):
+        """attach (or, with None, detach) the simulator's step trace [T, K, 72]"""
+        self._servo_sim().set_trace(trace)
 
     def set_eval_record(self, record: torch.Tensor | None):
         """attach (or, with None, detach) the simulator's per-env evaluation record [N, 12]"""

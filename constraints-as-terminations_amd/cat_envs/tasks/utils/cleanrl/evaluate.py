@@ -5,6 +5,11 @@
 per-env table of fixed commands (``catppo_servo_sim.fixed_command``).  Nothing inside the loop synchronises the host; the
 tables come back once, at the end, and ``aggregate`` - pure numpy, no device - turns them into metrics in fp64.
 DESIGN section 9, "Evaluation".
+
+Step responses ("Step responses"): ``commands`` may be a schedule ``[S, N, 3]`` of ``segment_steps``
+control steps per segment (``command_sequence``), and ``trace_envs = K`` has the simulator write one row of 72 floats per
+step for each of its first K envs (``catppo_servo_sim.trace``, inside the same launch).  ``step_response`` - pure numpy
+as well - reads rise time, settling time, overshoot and steady-state error of every command change off the trace.
 """
 from __future__ import annotations
 
@@ -15,6 +20,8 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from cat_envs.native import SERVO_EVAL_FIELDS as FIELDS
+from cat_envs.native import SERVO_TRACE_FIELDS as TRACE_FIELDS
+from cat_envs.native import SERVO_TRACE_FLOATS as TRACE_FLOATS
 
 #: the ranges the servo simulator draws its commands from (csrc/servo_sim.hip, command_of): vx, vy, wz
 COMMAND_RANGES = ((-0.3, 1.0), (-0.7, 0.7), (-0.78, 0.78))
@@ -34,6 +41,87 @@ def command_grid(vx=(-0.3, 1.0, 1), vy=(-0.7, 0.7, 1), wz=(-0.78, 0.78, 1), num_
     pts = np.stack([g.reshape(-1) for g in np.meshgrid(*axes, indexing="ij")], 1).astype(np.float32)
     idx = np.arange(int(num_envs), dtype=np.int64) % len(pts)
     return np.ascontiguousarray(pts[idx]), idx
+
+
+def command_sequence(points, num_envs: int):
+    """``[S, num_envs, 3]`` fp32 from ``points`` [S, 3]: every env follows the same sequence of commands"""
+    pts = np.asarray(points, np.float32)
+    if pts.ndim != 2 or pts.shape[1] != 3 or len(pts) < 1:
+        raise ValueError(f"a command sequence is [S, 3] with S >= 1, got {pts.shape}")
+    if int(num_envs) < 1:
+        raise ValueError("num_envs must be at least 1")
+    return np.ascontiguousarray(np.broadcast_to(pts[:, None, :], (len(pts), int(num_envs), 3)))
+
+
+AXES = ("vx", "vy", "wz")
+_COL = {name: (a, w) for name, a, w in TRACE_FIELDS}
+
+
+def step_response(trace, segment_steps: int, tolerance: float = 0.1) -> list:
+    """Rise, settling, overshoot and steady-state error of every command change in a trace ``[T, K, 72]``, in fp64.
+
+    For each traced env, within its first episode only (the rows before its first ``ends``, that row included: the step
+    that ends an episode is still a step of it), the rows are cut into segments of ``segment_steps`` by their ``t``.
+    For segment s >= 1 of length L and each axis a whose command changed (delta = c_s[a] - c_{s-1}[a] != 0), with
+    e_k = v_k[a] - c_s[a] for the k-th step of the segment, k = 1 .. L:
+      ``rise_steps``    first k with |e_k| <= tolerance |delta|, else None
+      ``settle_steps``  smallest k such that |e_j| <= tolerance |delta| for all j >= k, else None
+      ``overshoot``     max(0, max_k sign(delta) e_k) / |delta|
+      ``steady_error``  |mean of e_k over the last ceil(L / 4) steps|
+    One dict per (env, segment, axis): ``{"env", "segment", "axis", "from", "to", "complete", ...}``; a segment that the
+    end of the episode (or of the trace) cut short has ``complete: False`` and no figures."""
+    tr = np.asarray(trace, np.float64)
+    if tr.ndim != 3 or tr.shape[2] != TRACE_FLOATS:
+        raise ValueError(f"a trace is [T, K, {TRACE_FLOATS}], got {tr.shape}")
+    L = int(segment_steps)
+    if L < 1:
+        raise ValueError("segment_steps must be at least 1")
+    c0, v0 = _COL["command"][0], _COL["v"][0]
+    out = []
+    for i in range(tr.shape[1]):
+        rows = tr[:, i]
+        ended = np.nonzero(rows[:, _COL["ends"][0]] > 0.5)[0]
+        rows = rows[:int(ended[0]) + 1] if len(ended) else rows
+        seg = (rows[:, 0] // L).astype(np.int64)                       # by the row's own t: the run may start at t > 0
+        for s in np.unique(seg):
+            at = np.nonzero(seg == s)[0]
+            before = np.nonzero(seg == s - 1)[0]
+            if s < 1 or len(before) == 0:
+                continue
+            c_new, c_old = rows[at[0], c0:c0 + 3], rows[before[-1], c0:c0 + 3]
+            for a in range(3):
+                delta = c_new[a] - c_old[a]
+                if delta == 0:
+                    continue
+                r = {"env": i, "segment": int(s), "axis": AXES[a], "from": float(c_old[a]), "to": float(c_new[a]),
+                     "complete": len(at) == L}
+                if r["complete"]:
+                    e = rows[at, v0 + a] - c_new[a]
+                    inside = np.abs(e) <= tolerance * abs(delta)
+                    first = np.nonzero(inside)[0]
+                    outside = np.nonzero(~inside)[0]
+                    settle = 1 if len(outside) == 0 else int(outside[-1]) + 2
+                    tail = e[L - math.ceil(L / 4):]
+                    r.update(rise_steps=int(first[0]) + 1 if len(first) else None,
+                             settle_steps=settle if settle <= L else None,
+                             overshoot=float(max(0.0, float(np.max(np.sign(delta) * e))) / abs(delta)),
+                             steady_error=float(abs(tail.mean())))
+                out.append(r)
+    return out
+
+
+def summarise_step_response(responses) -> dict:
+    """per axis the medians of the figures over the complete responses (None where no response has the figure), and the
+    count of incomplete ones"""
+    summary = {"incomplete": sum(1 for r in responses if not r["complete"])}
+    for axis in AXES:
+        done = [r for r in responses if r["complete"] and r["axis"] == axis]
+        block = {"responses": len(done)}
+        for key in ("rise_steps", "settle_steps", "overshoot", "steady_error"):
+            vals = [r[key] for r in done if r[key] is not None]
+            block[key] = float(np.median(vals)) if vals else None
+        summary[axis] = block
+    return summary
 
 
 def aggregate(record, cat_reward=None, termination_prob=None, violations=None, term_names=()) -> dict:
@@ -73,12 +161,21 @@ def aggregate(record, cat_reward=None, termination_prob=None, violations=None, t
 class EvalResult:
     per_env: np.ndarray                           # [N, 12] fp32: the simulator's record
     fields: tuple = FIELDS
-    commands: np.ndarray | None = None            # [N, 3] fixed commands, or None (sampled by the simulator)
+    commands: np.ndarray | None = None            # [N, 3] fixed commands, [S, N, 3] schedule, or None (sampled)
     cat_reward: np.ndarray | None = None          # [N] fp32 sum of the CaT-scaled reward
     termination_prob: np.ndarray | None = None    # [N] fp32 sum of the CaT termination probability
     violations: np.ndarray | None = None          # [N, terms + 1] fp32 counts of steps with a violation (last: any term)
     term_names: tuple = ()
     metrics: dict = field(default_factory=dict)
+    trace: np.ndarray | None = None               # [steps, K, 72] fp32: the simulator's step trace of envs 0 .. K - 1
+    trace_fields: tuple = TRACE_FIELDS
+    segment_steps: int | None = None              # control steps per segment when ``commands`` is a schedule
+
+    def step_response(self, tolerance: float = 0.1) -> list:
+        """``step_response`` of this evaluation's trace (needs a schedule and a trace)"""
+        if self.trace is None or self.segment_steps is None:
+            raise ValueError("step responses need a command schedule and a trace (commands [S, N, 3], trace_envs > 0)")
+        return step_response(self.trace, self.segment_steps, tolerance)
 
     def _aggregate(self, rows=slice(None)):
         def pick(x):
@@ -88,7 +185,7 @@ class EvalResult:
 
     def by_command(self) -> list:
         """the metrics per distinct command row, in order of first appearance: ``{"command", "envs", "metrics"}``"""
-        if self.commands is None:
+        if self.commands is None or self.commands.ndim == 3:         # drawn, or a schedule: one group
             return [{"command": None, "envs": int(len(self.per_env)), "metrics": dict(self.metrics)}]
         _, first, inverse = np.unique(self.commands, axis=0, return_index=True, return_inverse=True)
         inverse = np.asarray(inverse).reshape(-1)
@@ -103,17 +200,24 @@ class EvalResult:
         d = {"metrics": self.metrics, "num_envs": int(len(self.per_env)), "fields": list(self.fields)}
         if by_command and self.commands is not None:
             d["by_command"] = self.by_command()
+        if self.trace is not None and self.segment_steps is not None:
+            responses = self.step_response()
+            d["segment_steps"] = int(self.segment_steps)
+            d["step_response"] = {"summary": summarise_step_response(responses), "responses": responses}
         return json.dumps(d)
 
 
 def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool = True,
-                    fresh_cat_state: bool = False) -> EvalResult:
+                    fresh_cat_state: bool = False, segment_steps: int | None = None, trace_envs: int = 0) -> EvalResult:
     """Roll ``policy`` out for ``steps`` control steps from a fresh reset and measure it.
 
     ``policy`` is an ``Agent`` - its observations are normalised by the frozen ``obs_rms`` and the action is the mean
     (``deterministic=False`` samples); neither its parameters nor its normaliser are modified - or any callable
     ``raw_obs [N, D] -> action [N, 12]``.  ``commands`` [N, 3] (tensor or array) fixes env i's command to row i for the
     whole evaluation; None leaves the draws to the simulator.  Needs the closed-loop simulator (``TypeError`` otherwise).
+    ``commands`` [S, N, 3] with ``segment_steps`` = L is a schedule: a step that starts at episode length t uses segment
+    ``min(t // L, S - 1)``, and an episode that ends restarts it.  ``trace_envs`` = K > 0 attaches a zeroed trace
+    ``[steps, K, 72]`` of the first K envs, written by the simulator's own launch: ``EvalResult.trace``.
 
     Use a dedicated env: its episode counters, reset masks, action history and constraint episode sums are zeroed, the
     simulator is reset, and the env is LEFT IN THE EVALUATED STATE (the record and the command table are detached again,
@@ -135,13 +239,24 @@ def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool 
     if not hasattr(u, "set_eval_record"):
         raise TypeError("evaluate_policy needs a CaTEnv")
     n, dev = u.num_envs, u.device
+    trace_envs = int(trace_envs)
+    if trace_envs < 0 or trace_envs > n:
+        raise ValueError(f"trace_envs must be in [0, {n}], got {trace_envs}")
+    lead = ()                                                        # (S,) when the commands are a schedule
+    if commands is not None and len(np.shape(commands)) == 3:                # np.shape reads a tensor's own .shape
+        if segment_steps is None or int(segment_steps) < 1:
+            raise ValueError("a command schedule [S, N, 3] needs segment_steps >= 1")
+        segment_steps = int(segment_steps)
+        lead = (int(np.shape(commands)[0]),)
+    elif segment_steps is not None:
+        raise ValueError("segment_steps goes with a command schedule [S, N, 3]")
     record = torch.zeros(n, len(FIELDS), device=dev)
     table = None
     if isinstance(commands, torch.Tensor) and commands.device == dev and commands.dtype == torch.float32:
-        table = commands.detach().reshape(n, 3).contiguous().clone()       # a table of its own, without a host round trip
+        table = commands.detach().reshape(*lead, n, 3).contiguous().clone()   # a table of its own, without a host round trip
     elif commands is not None:
         table = torch.as_tensor(np.asarray(commands.detach().cpu() if isinstance(commands, torch.Tensor) else commands,
-                                           np.float32)).reshape(n, 3).contiguous().to(dev)
+                                           np.float32)).reshape(*lead, n, 3).contiguous().to(dev)
     if isinstance(policy, Agent):
         agent = policy
 
@@ -160,12 +275,18 @@ def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool 
         cm._ep_viol.zero_()
         cm._ep_prob.zero_()
     u.set_eval_record(record)                                         # TypeError on the stream simulator
+    trace = torch.zeros(steps, trace_envs, TRACE_FLOATS, device=dev) if trace_envs else None
     frozen = contextlib.ExitStack()
     if fresh_cat_state:
         u.fresh_cat_state()
         frozen.enter_context(u.curriculum_frozen())
     try:
-        u.set_fixed_commands(table)
+        if lead:
+            u.set_fixed_commands(table, segment_steps)
+        else:
+            u.set_fixed_commands(table)
+        if trace is not None:
+            u.set_trace(trace)
         obs = env.reset()[0]["policy"]
         with torch.no_grad():
             for _ in range(steps):
@@ -184,10 +305,13 @@ def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool 
                     viol[:, -1].add_(hit.any(1))
     finally:
         frozen.close()
+        if trace is not None:
+            u.set_trace(None)
         u.set_eval_record(None)
         u.set_fixed_commands(None)
     res = EvalResult(per_env=record.cpu().numpy(), commands=None if table is None else table.cpu().numpy(),
                      cat_reward=cat_reward.cpu().numpy(), termination_prob=term_prob.cpu().numpy(),
-                     violations=viol.cpu().numpy(), term_names=names)
+                     violations=viol.cpu().numpy(), term_names=names, trace=None if trace is None else trace.cpu().numpy(),
+                     segment_steps=segment_steps if lead else None)
     res.metrics = res._aggregate()
     return res

@@ -46,14 +46,27 @@ __device__ __forceinline__ float tree4(float x) {
 
 __device__ __forceinline__ float pick(const rng::u32x4& r, int w) { return rng::uniform_open(w == 0 ? r.x : w == 1 ? r.y : w == 2 ? r.z : r.w); }
 
+// the three instances of the kernel (see the kernel): what the launch's descriptor asks for
+constexpr int kTrain = 0, kEvaluate = 1, kStepResponse = 2;
+
 // command of (env, episode, resample index): uniform in the reference ranges, dead zone, standing fraction; with a
-// fixed-command table the caller's row `e` as it stands, for every episode and resample index (kEval: see the kernel)
-template <bool kEval>
+// fixed-command table the caller's row `e` as it stands, for every episode and resample index - in the step-response
+// instance, of segment min(t / fixed_segment_steps, S - 1) when the table is a schedule of S > 1 segments, `t` being the
+// episode length the command is for (one wave-uniform compare; the divide runs only for a schedule).  kMode: see the kernel
+template <int kMode>
 __device__ __forceinline__ void command_of(const catppo_servo_sim& d, int64_t e, uint32_t gid, uint32_t ep, uint32_t k,
-                                           float c[3]) {
-  if constexpr (kEval) {
+                                           int64_t t, float c[3]) {
+  if constexpr (kMode != kTrain) {
     if (d.fixed_command) {
-      for (int i = 0; i < 3; ++i) c[i] = d.fixed_command[e * 3 + i];
+      int64_t at = e;
+      if constexpr (kMode == kStepResponse) {
+        if (d.fixed_segments > 1) {
+          int64_t seg = t / d.fixed_segment_steps;
+          seg = seg < 0 ? 0 : seg < d.fixed_segments ? seg : d.fixed_segments - 1;
+          at = seg * d.N + e;
+        }
+      }
+      for (int i = 0; i < 3; ++i) c[i] = d.fixed_command[at * 3 + i];
       return;
     }
   }
@@ -73,10 +86,14 @@ __device__ __forceinline__ float init_q(const catppo_servo_sim& d, uint32_t gid,
   return def + (pick(r, lane & 3) - 0.5f) * d.init_noise;
 }
 
-// kEval = false is the launch with both evaluation pointers NULL: everything they add is compiled out of it, so that a
-// training step runs the code it ran before the two fields existed
-template <bool kEval>
-__global__ __launch_bounds__(kThreads) void servo_sim_kernel(const catppo_servo_sim d) {
+// kMode = kTrain is the launch with all three evaluation pointers NULL: everything they add is compiled out of it, so
+// that a training step runs the code it ran before the fields existed.  kEvaluate: a fixed-command table [N, 3] or an
+// evaluation record, and nothing else - the evaluation that runs inside training keeps the code it had, too.
+// kStepResponse: a command schedule or a step trace (either may be absent: two wave-uniform branches).  It is held to
+// the 64 VGPRs the other two come out at: at 8 workgroups per CU 32768 envs are one resident round, at 7 they are two
+template <int kMode>
+__global__ __launch_bounds__(kThreads, kMode == kStepResponse ? 8 : 1) void servo_sim_kernel(const catppo_servo_sim d) {
+  constexpr bool kEval = kMode != kTrain;
   extern __shared__ float4 lds4[];
   float* lds = reinterpret_cast<float*>(lds4);
   const int tid = threadIdx.x, lane = tid & 15, grp = tid >> 4;
@@ -99,7 +116,7 @@ __global__ __launch_bounds__(kThreads) void servo_sim_kernel(const catppo_servo_
   const int f = lane & 3, foot_body = 4 * f + 4;
   const float def = isj ? d.default_joint_pos[lane] : 0.f;
   float cmd[3];
-  command_of<kEval>(d, e, gid, ep, (uint32_t)(t / d.resample_steps), cmd);
+  command_of<kMode>(d, e, gid, ep, (uint32_t)(t / d.resample_steps), t, cmd);
   float* obs = row + d.off_obs;
   // evaluation record: lane k < 12 of a live lane group owns field k of its env (one 48-byte access per env); the spare
   // groups past N, which recompute env N - 1, neither read nor write it
@@ -195,6 +212,42 @@ __global__ __launch_bounds__(kThreads) void servo_sim_kernel(const catppo_servo_
     const bool ends = t + 1 >= d.max_episode_length || fallen;
     const uint32_t ep_out = ep + (ends ? 1u : 0u);
 
+    // ---- step trace: one row of CATPPO_SERVO_TRACE_FLOATS per traced env, at the slot its record had counted before
+    // this step (field 0, held by lane 0); registers to memory, neighbouring lanes write neighbouring floats
+    if constexpr (kMode == kStepResponse) {
+      const float slot = __shfl(rec0, 0, 16);
+      // a float below (float)capacity is an integer below capacity: no float lies between an int and its rounding
+      if (d.trace != nullptr && e0 + grp < d.N && e < d.trace_envs && slot >= 0.f && slot < (float)d.trace_capacity) {
+        float* tr = d.trace + ((int64_t)slot * d.trace_envs + e) * CATPPO_SERVO_TRACE_FLOATS;
+        float head = 0.f;
+        switch (lane) {
+          case 0: head = (float)t; break;
+          case 1: head = ends ? 1.f : 0.f; break;
+          case 2: head = fallen ? 1.f : 0.f; break;
+          case 3: head = reward; break;
+          case 4: head = cmd[0]; break;
+          case 5: head = cmd[1]; break;
+          case 6: head = cmd[2]; break;
+          case 7: head = v[0]; break;
+          case 8: head = v[1]; break;
+          case 9: head = v[2]; break;
+          case 10: head = roll; break;
+          case 11: head = pitch; break;
+          case 12: head = z; break;
+          case 13: head = ncon; break;
+          default: break;
+        }
+        tr[lane] = head;
+        if (lane < 8) tr[16 + lane] = lane < 4 ? con : fz;      // lanes 0..3 and 4..7 both carry feet 0..3
+        if (isj) {
+          tr[24 + lane] = q;
+          tr[36 + lane] = qd;
+          tr[48 + lane] = tau_w;
+          tr[60 + lane] = a;
+        }
+      }
+    }
+
     // ---- assemble the next row
     if (isj) {
       row[d.off_joint_pos + lane] = q;
@@ -235,7 +288,7 @@ __global__ __launch_bounds__(kThreads) void servo_sim_kernel(const catppo_servo_
       float head[9] = {ang[0], ang[1], ang[2], grav[0], grav[1], grav[2], cmd[0], cmd[1], cmd[2]};
       if (ends) {
         float cn[3];
-        command_of<kEval>(d, e, gid, ep_out, 0u, cn);
+        command_of<kMode>(d, e, gid, ep_out, 0u, 0, cn);
         head[0] = head[1] = head[2] = head[3] = head[4] = 0.f;
         head[5] = -1.f, head[6] = cn[0], head[7] = cn[1], head[8] = cn[2];
       }
@@ -298,6 +351,13 @@ extern "C" int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* de
   CATPPO_CHECK_ARG(ctx, ((uintptr_t)d.eval % 16) == 0);
   CATPPO_CHECK_ARG(ctx, d.fixed_command == nullptr || (d.fixed_command != d.state_in && d.fixed_command != d.state_out));
   CATPPO_CHECK_ARG(ctx, d.eval == nullptr || (d.eval != d.state_in && d.eval != d.state_out));
+  CATPPO_CHECK_ARG(ctx, d.fixed_segments >= 0);
+  CATPPO_CHECK_ARG(ctx, d.fixed_segments <= 1 || (d.fixed_segment_steps >= 1 && d.fixed_command != nullptr));
+  if (d.trace) {
+    CATPPO_CHECK_ARG(ctx, d.eval != nullptr && ((uintptr_t)d.trace % 16) == 0);
+    CATPPO_CHECK_ARG(ctx, d.trace_envs >= 1 && d.trace_envs <= d.N && d.trace_capacity >= 1);
+    CATPPO_CHECK_ARG(ctx, d.trace != d.state_in && d.trace != d.state_out && d.trace != d.eval && d.trace != d.fixed_command);
+  }
   // every field the kernel writes lies inside the row
   const struct { int32_t off, width; } fields[] = {
       {d.off_joint_pos, kJoints}, {d.off_joint_vel, kJoints}, {d.off_joint_acc, kJoints}, {d.off_applied_torque, kJoints},
@@ -307,7 +367,9 @@ extern "C" int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* de
   for (const auto& fl : fields) CATPPO_CHECK_ARG(ctx, fl.off >= 0 && (int64_t)fl.off + fl.width <= d.row_floats);
   const unsigned nblk = (unsigned)cdiv64(d.N, kEnvsPerBlock);
   const size_t lds_bytes = (size_t)d.row_floats * kEnvsPerBlock * sizeof(float);
-  const auto kernel = (d.fixed_command || d.eval) ? servo_sim_kernel<true> : servo_sim_kernel<false>;
+  const auto kernel = (d.trace || d.fixed_segments > 1) ? servo_sim_kernel<kStepResponse>
+                      : (d.fixed_command || d.eval)     ? servo_sim_kernel<kEvaluate>
+                                                        : servo_sim_kernel<kTrain>;
   hipLaunchKernelGGL(kernel, dim3(nblk), dim3(kThreads), lds_bytes, static_cast<hipStream_t>(stream), d);
   CATPPO_CHECK_LAUNCH(ctx);
   return CATPPO_OK;

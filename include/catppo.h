@@ -665,8 +665,24 @@ int catppo_set_grad_overlap(catppo_ctx* ctx, int on);      /* on: 0 | 1 | 2 set 
  * 5 (cw - wz)^2 | 6 roll^2 + pitch^2 | 7 tree16 of applied_torque^2 | 8 feet in contact | 9 return of the running
  * episode (zero after the step that ends it) | 10 returns of the ended episodes | 11 lengths of the ended episodes.
  * Both NULL: the launch computes what it did before the two fields existed, bit for bit.  Neither may alias a state
- * buffer; the record never changes a float of the state row. */
+ * buffer; the record never changes a float of the state row.
+ * Step responses (trailing fields; a zero-filled tail is the behaviour described so far, exactly).
+ * fixed_segments = S > 1: fixed_command is a schedule [S, N, 3].  A step that starts at episode length t uses row
+ * min(t / fixed_segment_steps, S - 1) of env i; the same index serves the init row (t = the env's episode_length, zero in
+ * an evaluation) and the post-reset observation (t = 0, segment 0).  The schedule is keyed on the episode length, like
+ * command resampling: an episode that ends restarts its schedule.  No dead zone, no standing fraction.  S of 0 or 1 reads
+ * [N, 3].  S > 1 needs fixed_segment_steps >= 1 and a table; S < 0 is an error.
+ * trace != NULL ([trace_capacity, trace_envs, CATPPO_SERVO_TRACE_FLOATS] fp32, 16-byte aligned, zeroed by the caller):
+ * every step writes one row for each of the envs 0 .. trace_envs - 1 of this simulator, at the slot that field 0 of the
+ * env's evaluation record (steps counted so far) held before the step - no host counter, so it survives graph capture,
+ * and it needs eval != NULL.  A step whose slot is >= trace_capacity writes nothing, and neither does an init launch.
+ * Needs 1 <= trace_envs <= N and trace_capacity >= 1; may alias none of state_in, state_out, eval, fixed_command.
+ * Row:  0 t (episode length the step started from) | 1 ends | 2 fallen | 3 reward (raw) | 4..6 the step's command |
+ * 7..9 vx vy wz after the step | 10 roll | 11 pitch | 12 base height z | 13 feet in contact | 14 15 zero |
+ * 16..19 contact flag per foot | 20..23 fz per foot | 24..35 q | 36..47 qd | 48..59 tau_w (applied_torque) |
+ * 60..71 the action of this step.  The trace never changes a float of the state row or of the record. */
 #define CATPPO_SERVO_EVAL_FLOATS 12
+#define CATPPO_SERVO_TRACE_FLOATS 72
 typedef struct catppo_servo_sim {
   int64_t N, env_offset;                 /* env_offset: global env id of row 0 (env-sharded runs) */
   const float* state_in;
@@ -685,8 +701,12 @@ typedef struct catppo_servo_sim {
   float dt, kp, kd, inertia, tau_max, action_scale, vel_alpha, tilt_beta, tilt_max, reward_scale, foot_clearance,
       contact_threshold, stand_height, height_drop, floor_height, min_height, base_stiffness, weight, impact_gain,
       init_noise, standing_fraction, command_deadzone;
-  const float* fixed_command;            /* [N, 3] or NULL */
+  const float* fixed_command;            /* [N, 3], [fixed_segments, N, 3] or NULL */
   float* eval;                           /* [N, CATPPO_SERVO_EVAL_FLOATS] or NULL; 16-byte aligned */
+  int32_t fixed_segments;                /* S > 1: fixed_command is a schedule [S, N, 3]; 0 or 1: [N, 3] */
+  int32_t fixed_segment_steps;           /* control steps per segment of the schedule */
+  float* trace;                          /* [trace_capacity, trace_envs, CATPPO_SERVO_TRACE_FLOATS] or NULL; 16-byte aligned */
+  int32_t trace_envs, trace_capacity;    /* envs 0 .. trace_envs - 1 are traced, for trace_capacity steps */
 } catppo_servo_sim;
 int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* desc, void* stream);
 

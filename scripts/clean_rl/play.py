@@ -9,6 +9,12 @@ observation normaliser) before rolling the policy out on the device kernels.
 (``cat_envs.tasks.utils.cleanrl.evaluate``): one line ``[EVAL] <json>`` and ``<run>/eval/<checkpoint name>.json``.
 ``--eval_grid NX NY NW`` fixes the commands to a grid over the task's command ranges (env i gets point i % (NX NY NW));
 without it the simulator draws them.  ``--stochastic`` samples the actions instead of taking the mean.
+
+``--eval_schedule VX VY WZ [VX VY WZ ...]`` (instead of ``--eval_grid``) has every env follow that sequence of commands,
+``--eval_segment_steps L`` control steps each, restarting with every episode; ``--trace_envs K`` records the first K envs
+step by step on the device.  With both, the ``[EVAL]`` line carries rise, settling, overshoot and steady-state error per
+command change (``"step_response"``), and ``<run>/eval/<checkpoint name>_trace.npz`` holds ``trace`` [steps, K, 72],
+``fields``, ``commands`` and ``segment_steps``.
 """
 import argparse
 import os
@@ -49,9 +55,18 @@ def main(argv=None):
     parser.add_argument("--eval_steps", type=int, default=0, help="Evaluate the policy for this many control steps (0: off).")
     parser.add_argument("--eval_grid", type=int, nargs=3, default=None, metavar=("NX", "NY", "NW"),
                         help="Fixed commands: a grid of NX x NY x NW points over the command ranges (default: sampled).")
+    parser.add_argument("--eval_schedule", type=float, nargs="+", default=None, metavar="V",
+                        help="Command schedule VX VY WZ [VX VY WZ ...] that every env follows (instead of --eval_grid).")
+    parser.add_argument("--eval_segment_steps", type=int, default=100, help="Control steps per segment of --eval_schedule.")
+    parser.add_argument("--trace_envs", type=int, default=0, help="Record the first K envs step by step (0: off).")
     parser.add_argument("--stochastic", action="store_true", default=False, help="Evaluate with sampled actions.")
     cli_args.add_clean_rl_args(parser)
     args_cli = parser.parse_args(argv)
+    if args_cli.eval_schedule is not None:
+        if args_cli.eval_grid is not None:
+            parser.error("--eval_schedule and --eval_grid are mutually exclusive")
+        if len(args_cli.eval_schedule) % 3 != 0:
+            parser.error("--eval_schedule takes a multiple of three values: VX VY WZ per segment")
     import torch
 
     import cat_envs.tasks  # noqa: F401
@@ -91,14 +106,19 @@ def main(argv=None):
     env.close()
 
     if args_cli.eval_steps > 0:
-        from cat_envs.tasks.utils.cleanrl.evaluate import COMMAND_RANGES, command_grid, evaluate_policy
+        import numpy as np
+        from cat_envs.tasks.utils.cleanrl.evaluate import COMMAND_RANGES, command_grid, command_sequence, evaluate_policy
         eval_env = make(args_cli.task, cfg=env_cfg)               # a fresh env: the evaluator leaves it in the evaluated state
-        commands = None
-        if args_cli.eval_grid is not None:
+        commands, segment_steps = None, None
+        if args_cli.eval_schedule is not None:
+            points = np.asarray(args_cli.eval_schedule, np.float32).reshape(-1, 3)
+            commands, segment_steps = command_sequence(points, eval_env.unwrapped.num_envs), args_cli.eval_segment_steps
+        elif args_cli.eval_grid is not None:
             axes = [(lo, hi, n) for (lo, hi), n in zip(COMMAND_RANGES, args_cli.eval_grid)]
             commands = command_grid(*axes, num_envs=eval_env.unwrapped.num_envs)[0]
         result = evaluate_policy(eval_env, actor, args_cli.eval_steps, commands=commands,
-                                 deterministic=not args_cli.stochastic)
+                                 deterministic=not args_cli.stochastic, segment_steps=segment_steps,
+                                 trace_envs=args_cli.trace_envs)
         text = result.to_json()
         print(f"[EVAL] {text}")
         out_dir = os.path.join(os.path.dirname(resume_path), "eval")
@@ -107,6 +127,12 @@ def main(argv=None):
         with open(out_path, "w") as f:
             f.write(text + "\n")
         print(f"[INFO] Wrote evaluation to {out_path}")
+        if result.trace is not None:
+            trace_path = os.path.splitext(out_path)[0] + "_trace.npz"
+            np.savez(trace_path, trace=result.trace, fields=np.array([name for name, _, _ in result.trace_fields]),
+                     commands=np.zeros((0, 3), np.float32) if result.commands is None else result.commands,
+                     segment_steps=np.int64(result.segment_steps or 0))
+            print(f"[INFO] Wrote trace to {trace_path}")
         eval_env.close()
 
 

@@ -6,6 +6,9 @@
 --eval attaches the evaluation record and a fixed command table to the simulator (both descriptor pointers non-NULL), for the
 three-arm comparison of profiles/servo_eval_kernel_stats.csv: CATPPO_LIB=<library of the parent commit>, this library without
 --eval (both pointers NULL), this library with --eval.
+--trace attaches the record, a command schedule of four segments and a step trace of 32 envs, for the five-arm comparison of
+profiles/servo_trace_kernel_stats.csv: the parent's library and this library, each without a flag and with --eval, and this library
+with --trace.
 
 Per env step the trace shows servo_sim_kernel (the simulator), the two launches of catppo_rollout_pre, the one of
 catppo_rollout_post and the policy forward."""
@@ -25,6 +28,7 @@ def main():
     ap.add_argument("--num_envs", type=int, default=4096)
     ap.add_argument("--rollouts", type=int, default=10)
     ap.add_argument("--eval", action="store_true", help="attach the evaluation record and fixed commands")
+    ap.add_argument("--trace", action="store_true", help="attach the record, a schedule of 4 segments and a trace of 32 envs")
     a = ap.parse_args()
     import cat_envs.tasks  # noqa: F401
     from cat_envs.shim import load_cfg_from_registry, make
@@ -36,9 +40,17 @@ def main():
     agent_cfg.minibatch_size = min(agent_cfg.minibatch_size, a.num_envs * agent_cfg.num_steps)
     trainer = PPOTrainer(make(task, cfg=env_cfg), agent_cfg)
     assert trainer.sink is not None
-    if a.eval:
+    env_u = trainer.envs.unwrapped
+    if a.trace:
+        from cat_envs.tasks.utils.cleanrl.evaluate import command_sequence
+        record = torch.zeros(a.num_envs, 12, device=env_u.device)
+        points = [[0, 0, 0], [0.6, 0, 0], [0.6, 0, 0.5], [0, 0, 0]]
+        trace = torch.zeros(a.rollouts * trainer.T, 32, 72, device=env_u.device)
+        env_u.set_eval_record(record)
+        env_u.set_fixed_commands(torch.from_numpy(command_sequence(points, a.num_envs)).to(env_u.device), 50)
+        env_u.set_trace(trace)
+    elif a.eval:
         from cat_envs.tasks.utils.cleanrl.evaluate import COMMAND_RANGES, command_grid
-        env_u = trainer.envs.unwrapped
         record = torch.zeros(a.num_envs, 12, device=env_u.device)
         axes = [(lo, hi, 4) for lo, hi in COMMAND_RANGES]
         commands = torch.from_numpy(command_grid(*axes, num_envs=a.num_envs)[0]).to(env_u.device)
@@ -50,10 +62,14 @@ def main():
     torch.cuda.synchronize()
     print(f"{a.rollouts} rollouts of {trainer.T} steps x {a.num_envs} envs; mean reward/step "
           f"{float(trainer.rewards.float().mean()):.4f}")
-    if a.eval:
+    if a.eval or a.trace:
         steps = record[:, 0].cpu()
         assert float(steps.min()) == float(steps.max()) == a.rollouts * trainer.T, (float(steps.min()), float(steps.max()))
         print(f"evaluation record: {int(steps[0])} steps per env, raw reward/step {float(record[:, 3].sum() / steps.sum()):.4f}")
+    if a.trace:
+        t = trace.cpu()
+        assert bool((t[:, :, 60:72].abs().sum(-1) > 0).all()), "a trace row was not written"
+        print(f"trace: {t.shape[0]} steps x {t.shape[1]} envs, {int(t[:, :, 1].sum())} episode ends")
 
 
 if __name__ == "__main__":
