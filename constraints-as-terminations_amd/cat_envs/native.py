@@ -130,6 +130,26 @@ class ServoSimStep(ServoSim):
                 ("trace_envs", C.c_int32), ("trace_capacity", C.c_int32)]
 
 
+#: kinds of the servo surrogate's reward terms (include/catppo.h, "Rewards"): name -> catppo_servo_reward_term.kind
+SERVO_REWARD_KINDS = {"track_lin_vel_xy_exp": 1, "track_ang_vel_z_exp": 2, "track_lin_vel_xy_rational": 3,
+                      "track_ang_vel_z_rational": 4, "ang_vel_xy_l2": 5, "flat_orientation_l2": 6, "joint_torques_l2": 7,
+                      "joint_acc_l2": 8, "joint_vel_l2": 9, "joint_deviation_l1": 10, "action_rate_l2": 11, "action_l2": 12,
+                      "feet_air_time": 13, "base_height_l2": 14, "is_terminated": 15, "is_alive": 16}
+SERVO_REWARD_FLOATS = 32                # CATPPO_SERVO_REWARD_FLOATS: running sums 0..14 | zero | ended sums 16..30 | ended count
+SERVO_REWARD_MAX_TERMS = 15             # CATPPO_SERVO_REWARD_MAX_TERMS
+
+
+class ServoRewardTerm(C.Structure):
+    """catppo_servo_reward_term: one entry of the device-resident reward table"""
+    _fields_ = [("kind", C.c_int32), ("joint_mask", C.c_uint32), ("weight", C.c_float), ("param", C.c_float)]
+
+
+class ServoSimRewards(ServoSimStep):
+    """``ServoSimStep`` with the descriptor's reward tail: the whole catppo_servo_sim.  A zero-filled tail (``reward_terms``
+    = 0) is the built-in reward, exactly.  ``reward_table`` is a device array of ``reward_terms`` ``ServoRewardTerm``."""
+    _fields_ = [("reward_terms", C.c_int32), ("reward_rec", C.c_void_p), ("reward_table", C.c_void_p)]
+
+
 F32, F16, F64 = 0, 1, 2                 # CATPPO_F32 / _F16 / _F64
 SUM, MAX = 0, 1                         # CATPPO_SUM / _MAX
 LR_FIXED, LR_LINEAR, LR_KEEP = 0, 1, 2
@@ -221,7 +241,7 @@ _SIGNATURES = {
     # ---- ABI 0.4
     "catppo_set_grad_overlap": (C.c_int, [_vp, C.c_int]),
     # ---- closed-loop Solo12 servo surrogate (one launch per env step)
-    "catppo_servo_sim_step": (C.c_int, [_vp, C.POINTER(ServoSimStep), _vp]),
+    "catppo_servo_sim_step": (C.c_int, [_vp, C.POINTER(ServoSimRewards), _vp]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
@@ -728,10 +748,10 @@ class Native:
     def rollout_flush(self):
         self._ok(self.lib.catppo_rollout_defer_tail(self.h, -1, self._stream()))      # -1: flush, the mode stays
 
-    def servo_sim_step(self, desc: ServoSimStep):
+    def servo_sim_step(self, desc: ServoSimRewards):
         """one control step (or, with ``desc.init``, the first state) of the Solo12 servo surrogate"""
-        if not isinstance(desc, ServoSimStep):              # the library reads the whole catppo_servo_sim, tail included
-            raise TypeError("servo_sim_step takes a native.ServoSimStep")
+        if not isinstance(desc, ServoSimRewards):           # the library reads the whole catppo_servo_sim, tail included
+            raise TypeError("servo_sim_step takes a native.ServoSimRewards (the whole catppo_servo_sim)")
         rc = self.lib.catppo_servo_sim_step(self.h, C.byref(desc), self._stream())
         if rc:
             self._ok(rc)

@@ -8,6 +8,6 @@ registry replacing ``gym.register`` / ``gym.make`` / ``load_cfg_from_registry``.
 """
 from .configclass import MISSING, configclass  # noqa: F401
 from .managers import (CurriculumTermCfg, ManagerBase, ManagerTermBase, ManagerTermBaseCfg,  # noqa: F401
-                       SceneEntityCfg)
+                       RewardTermCfg, SceneEntityCfg)
 from .registry import (apply_overrides, hydra_task_config, load_cfg_from_registry, make, register,  # noqa: F401
                        registry)

@@ -11,6 +11,7 @@ try:  # pragma: no cover
     from isaaclab.managers import SceneEntityCfg  # type: ignore
     from isaaclab.managers.manager_base import ManagerBase, ManagerTermBase  # type: ignore
     from isaaclab.managers.manager_term_cfg import CurriculumTermCfg, ManagerTermBaseCfg  # type: ignore
+    from isaaclab.managers.manager_term_cfg import RewardTermCfg  # type: ignore
     HAVE_ISAACLAB = True
 except Exception:
     HAVE_ISAACLAB = False
@@ -23,6 +24,11 @@ except Exception:
     @configclass
     class CurriculumTermCfg(ManagerTermBaseCfg):
         pass
+
+    @configclass
+    class RewardTermCfg(ManagerTermBaseCfg):
+        """IsaacLab's RewTerm: the step's reward is the sum of ``func(env, **params) * weight * dt`` over the terms"""
+        weight: float = MISSING
 
     class SceneEntityCfg:
         """Names are resolved to ids against ``scene[name].joint_names / body_names``."""

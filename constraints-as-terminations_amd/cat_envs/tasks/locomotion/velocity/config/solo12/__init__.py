@@ -37,3 +37,18 @@ register(
     disable_env_checker=True,
     kwargs={"env_cfg_entry_point": f"{__name__}.cat_flat_env_cfg:Solo12ServoFlatEnvCfg_PLAY", **_KW},
 )
+
+# the servo task with a RewardsCfg: reward terms evaluated inside the simulator's launch ("Rewards")
+register(
+    id="Isaac-Velocity-CaT-Flat-Solo12-Servo-Rewards-v0",
+    entry_point=CaTEnv,
+    disable_env_checker=True,
+    kwargs={"env_cfg_entry_point": f"{__name__}.cat_flat_env_cfg:Solo12ServoRewardsFlatEnvCfg", **_KW},
+)
+
+register(
+    id="Isaac-Velocity-CaT-Flat-Solo12-Servo-Rewards-Play-v0",
+    entry_point=CaTEnv,
+    disable_env_checker=True,
+    kwargs={"env_cfg_entry_point": f"{__name__}.cat_flat_env_cfg:Solo12ServoRewardsFlatEnvCfg_PLAY", **_KW},
+)

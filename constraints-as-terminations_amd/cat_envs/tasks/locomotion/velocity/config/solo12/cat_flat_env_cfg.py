@@ -2,14 +2,21 @@
 
 The ``ConstraintsCfg`` / ``CurriculumCfg`` below carry the reference's values
 (solo12/cat_flat_env_cfg.py:259-355 and :383-451: 13 terms / 78 columns, 8 annealed terms).
-Scene, physics, rewards, events and observation *terms* of the reference need Isaac Sim /
+Scene, physics, events and observation *terms* of the reference need Isaac Sim /
 PhysX (NVIDIA only) and are out of scope; ``SyntheticCfg`` configures the device-resident
-synthetic stream that stands in for the simulator.
+synthetic stream that stands in for the simulator.  Rewards: the stream simulator's are
+a pre-generated stream; on the servo surrogate ``RewardsCfg`` (the reference's two terms and values)
+or any other block of ``mdp.rewards`` terms is evaluated inside the simulator's launch
+(``Solo12ServoRewardsFlatEnvCfg``, DESIGN section 9 "Rewards").
 """
+import math
+
 from cat_envs.shim import CurriculumTermCfg as CurrTerm
+from cat_envs.shim import RewardTermCfg as RewTerm
 from cat_envs.shim import SceneEntityCfg, configclass
 from cat_envs.tasks.utils.cat import constraints, curriculums
 from cat_envs.tasks.utils.cat.manager_constraint_cfg import ConstraintTermCfg as ConstraintTerm
+from cat_envs.tasks.utils.mdp import rewards
 
 ALL_JOINTS = [".*_HAA", ".*_HFE", ".*_KFE"]
 
@@ -191,6 +198,45 @@ class Solo12ServoFlatEnvCfg(Solo12FlatEnvCfg):
 
 @configclass
 class Solo12ServoFlatEnvCfg_PLAY(Solo12ServoFlatEnvCfg):
+    scene: SceneCfg = SceneCfg(num_envs=50, env_spacing=3.0)
+    curriculum: object = None
+
+
+@configclass
+class RewardsCfg:
+    """the reference's reward block (solo12/cat_flat_env_cfg.py RewardsCfg): the two exp tracking terms"""
+    track_lin_vel_xy_exp = RewTerm(func=rewards.track_lin_vel_xy_exp, weight=1.0,
+                                   params={"command_name": "base_velocity", "std": math.sqrt(0.25)})
+    track_ang_vel_z_exp = RewTerm(func=rewards.track_ang_vel_z_exp, weight=0.5,
+                                  params={"command_name": "base_velocity", "std": math.sqrt(0.25)})
+
+
+@configclass
+class ShapedRewardsCfg:
+    """``RewardsCfg`` plus a few of the penalties people add first (IsaacLab's velocity-task magnitudes)"""
+    track_lin_vel_xy_exp = RewardsCfg.__dataclass_fields__["track_lin_vel_xy_exp"].default_factory()
+    track_ang_vel_z_exp = RewardsCfg.__dataclass_fields__["track_ang_vel_z_exp"].default_factory()
+    ang_vel_xy_l2 = RewTerm(func=rewards.ang_vel_xy_l2, weight=-0.05)
+    flat_orientation_l2 = RewTerm(func=rewards.flat_orientation_l2, weight=-1.0)
+    joint_torques_l2 = RewTerm(func=rewards.joint_torques_l2, weight=-1.0e-4,
+                               params={"asset_cfg": SceneEntityCfg("robot", joint_names=ALL_JOINTS)})
+    action_rate_l2 = RewTerm(func=rewards.action_rate_l2, weight=-0.01)
+    hip_deviation = RewTerm(func=rewards.joint_deviation_l1, weight=-0.1,
+                            params={"asset_cfg": SceneEntityCfg("robot", joint_names=[".*_HAA"])})
+    feet_air_time = RewTerm(func=rewards.feet_air_time, weight=0.25,
+                            params={"command_name": "base_velocity", "threshold": 0.25,
+                                    "sensor_cfg": SceneEntityCfg("contact_forces", body_names=".*_FOOT")})
+    is_terminated = RewTerm(func=rewards.is_terminated, weight=-20.0)
+
+
+@configclass
+class Solo12ServoRewardsFlatEnvCfg(Solo12ServoFlatEnvCfg):
+    """the servo task with a configurable reward block: the simulator's launch evaluates ``rewards`` term by term"""
+    rewards: RewardsCfg = RewardsCfg()
+
+
+@configclass
+class Solo12ServoRewardsFlatEnvCfg_PLAY(Solo12ServoRewardsFlatEnvCfg):
     scene: SceneCfg = SceneCfg(num_envs=50, env_spacing=3.0)
     curriculum: object = None
 

@@ -202,7 +202,7 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         self.default_joint_pos = torch.tensor(DEFAULT_JOINT_POS, device=self.device).repeat(num_envs, 1).contiguous()
         self._episode_length, self._reset = episode_length, reset       # referenced by the descriptor: keep alive
         self._nat = native.get(self.device)
-        d = self._desc = native.ServoSimStep()
+        d = self._desc = native.ServoSimRewards()
         d.N, d.env_offset, d.row_stride, d.row_floats = num_envs, int(env_offset), self.F, self.F
         d.obs_dim, d.H, d.B = obs_dim, H, B
         names = {"projected_gravity": "projected_gravity_b", "root_pos": "root_pos_w"}
@@ -217,6 +217,8 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         for n in native.SERVO_CONSTANTS[1:]:
             setattr(d, n, float(getattr(syn, "servo_" + n)))
         self._fixed_command = self._eval_record = self._trace = None    # referenced by the descriptor: keep alive
+        self._reward_record = self._reward_table = None                 # likewise; allocated by the first set_reward_table
+        self._reward_entries = []
         self._build_scene()
 
     def _table(self, t, width, what, lead=()):
@@ -270,6 +272,44 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         d = self._desc
         d.trace = None if t is None else t.data_ptr()
         d.trace_capacity, d.trace_envs = (0, 0) if t is None else (int(t.shape[0]), int(t.shape[1]))
+
+    def set_reward_table(self, entries):
+        """``entries``: up to 15 ``(kind, joint_mask, weight, param)`` (``native.SERVO_REWARD_KINDS``; what the terms of
+        ``mdp.rewards`` describe).  Every following step writes their sum into the row's ``reward`` field instead of the
+        built-in expression and keeps the per-term episode sums in ``reward_record`` [N, 32], inside the simulator's own
+        launch.  The table lives on the device and is rewritten here, in stream order: a new weight is in the next launch.
+        Empty or None: back to the built-in reward.  The entries are checked here - the library cannot read them."""
+        entries = [(int(k), int(m), float(w), float(p)) for k, m, w, p in (entries or [])]
+        if len(entries) > native.SERVO_REWARD_MAX_TERMS:
+            raise ValueError(f"{len(entries)} reward terms: the simulator evaluates at most {native.SERVO_REWARD_MAX_TERMS}")
+        for k, m, w, p in entries:
+            if not 1 <= k <= 16:
+                raise ValueError(f"unknown reward kind {k}")
+            if k <= 4 and not p > 0.0:
+                raise ValueError(f"reward kind {k} needs param > 0, got {p}")
+            if 7 <= k <= 10 and not (m != 0 and (m & ~0xFFF) == 0):
+                raise ValueError(f"reward kind {k} needs a joint mask in 1 .. 0xFFF, got {m:#x}")
+            if k == 11 and self.D < 45:
+                raise ValueError(f"action_rate_l2 reads the last-action block of the observation: obs_dim {self.D} < 45")
+        d = self._desc
+        self._reward_entries = entries
+        if not entries:
+            d.reward_terms, d.reward_rec, d.reward_table = 0, None, None
+            return
+        if self._reward_record is None:
+            self._reward_record = torch.zeros(self.N, native.SERVO_REWARD_FLOATS, device=self.device)
+            self._reward_table = torch.zeros(native.SERVO_REWARD_MAX_TERMS * C.sizeof(native.ServoRewardTerm),
+                                             dtype=torch.uint8, device=self.device)
+        host = (native.ServoRewardTerm * native.SERVO_REWARD_MAX_TERMS)()
+        for i, (k, m, w, p) in enumerate(entries):
+            host[i].kind, host[i].joint_mask, host[i].weight, host[i].param = k, m, w, p
+        self._reward_table.copy_(torch.frombuffer(bytearray(host), dtype=torch.uint8))
+        d.reward_terms, d.reward_rec, d.reward_table = len(entries), self._reward_record.data_ptr(), self._reward_table.data_ptr()
+
+    @property
+    def reward_record(self):
+        """[N, 32] fp32 or None: 0..14 running sums per term | 15 zero | 16..30 sums of the ended episodes | 31 their count"""
+        return self._reward_record if self._reward_entries else None
 
     def reset(self):
         """the first state of episode 0 in the state buffer"""
@@ -457,6 +497,13 @@ class CaTEnv:
         if hasattr(self.cfg, "constraints"):
             self.constraint_manager = ConstraintManager(self.cfg.constraints, self)
             print("[INFO] Constraint Manager: ", self.constraint_manager)
+        if getattr(self.cfg, "rewards", None) is not None:
+            if not isinstance(self.sim, Solo12ServoSim):
+                raise TypeError("cfg.rewards needs the closed-loop simulator (SyntheticCfg.kind = 'servo'): the reward terms "
+                                "are evaluated inside its launch; the stream simulator's reward is a pre-generated stream")
+            from cat_envs.tasks.utils.mdp.reward_manager import RewardManager
+            self.reward_manager = RewardManager(self.cfg.rewards, self)
+            print("[INFO] Reward Manager: ", self.reward_manager)
 
     # evaluation ------------------------------------------------------------------------------
     def _servo_sim(self) -> Solo12ServoSim:
@@ -515,6 +562,8 @@ class CaTEnv:
               "exact_reset_sync": bool(self.exact_reset_sync),
               "constraint_terms": [[n, int(w)] for n, w in zip(cm._term_names, cm._widths)] if cm is not None else []}
         fp.update(self.sim.fingerprint())
+        if hasattr(self, "reward_manager"):          # only then: fingerprints of runs without rewards keep their fields
+            fp["reward_terms"] = self.reward_manager.fingerprint()
         return fp
 
     def state_dict(self) -> dict:
@@ -526,6 +575,8 @@ class CaTEnv:
         sd.update(self._state_tensors())
         if hasattr(self, "constraint_manager"):
             sd["constraints"] = self.constraint_manager.state_dict()
+        if hasattr(self, "reward_manager"):
+            sd["rewards"] = self.reward_manager.state_dict()
         return sd
 
     def check_state_dict(self, sd: dict):
@@ -533,6 +584,10 @@ class CaTEnv:
         keys = ["common_step_counter", "sim_step_counter", "curriculum", "sim", *self._state_tensors()]
         if hasattr(self, "constraint_manager"):
             keys.append("constraints")
+        if hasattr(self, "reward_manager"):
+            keys.append("rewards")
+        elif "rewards" in sd:
+            raise ValueError("run state: it carries reward terms, this env has no cfg.rewards")
         missing = [k for k in keys if k not in sd]
         if missing:
             raise ValueError(f"run state: the env's part lacks {missing}")
@@ -548,6 +603,8 @@ class CaTEnv:
             unknown = [n for n in sd["curriculum"]["max_p"] if n not in cm.active_terms]
             if unknown:
                 raise ValueError(f"run state: max_p of constraint terms {unknown} that this env does not have")
+        if hasattr(self, "reward_manager"):
+            self.reward_manager.check_state_dict(sd["rewards"])
 
     def load_state_dict(self, sd: dict):
         """IN PLACE (``copy_`` into the existing tensors, never a rebound attribute): the fused step's argument block, the
@@ -561,6 +618,8 @@ class CaTEnv:
         self.sim.load_state_dict(sd["sim"])
         if hasattr(self, "constraint_manager"):
             self.constraint_manager.load_state_dict(sd["constraints"])
+        if hasattr(self, "reward_manager"):
+            self.reward_manager.load_state_dict(sd["rewards"])
         self.curriculum_manager.load_state_dict(sd["curriculum"])      # through set_term_cfg: the next launch carries it
 
     # episode control -------------------------------------------------------------------------

@@ -1103,6 +1103,10 @@ class PPOTrainer:
             parallel.allreduce_sum_(self.diag)
             self.diag[7] /= self.world
         d = self.diag.cpu().numpy()                              # the one host sync of the iteration
+        # per-term episode sums of a configured reward block: read where the host has just waited anyway (env-sharded
+        # runs log rank 0's shard; every rank pops, so that every shard's ended sums cover the same iterations)
+        rm = getattr(self.envs.unwrapped, "reward_manager", None)
+        reward_log = rm.pop_log() if rm is not None else None
         if self.lr_schedule == "adaptive":
             self.lr = float(self.nat.iter_state_read(self.state).lr)
         n_upd = max(d[7], 1.0)
@@ -1117,6 +1121,8 @@ class PPOTrainer:
             w.add_scalar("Loss/mean_v_loss", stats["mean_v_loss"], it)
             w.add_scalar("Loss/mean_surrogate_loss", stats["mean_surrogate_loss"], it)
             w.add_scalar("Loss/learning_rate", self.lr, it)
+            for key, value in (reward_log or {}).items():        # "Episode_Reward/<term>"
+                w.add_scalar(key, value, it)
         if self.run_path is not None and self.rank == 0 and (it + 1) % c.save_interval == 0:
             torch.save(self.agent.state_dict(), f"{self.run_path}/model_{it}.pt")     # same off-by-one naming
             print("Saved model")

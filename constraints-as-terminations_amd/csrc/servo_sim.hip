@@ -49,6 +49,10 @@ __device__ __forceinline__ float pick(const rng::u32x4& r, int w) { return rng::
 // the three instances of the kernel (see the kernel): what the launch's descriptor asks for
 constexpr int kTrain = 0, kEvaluate = 1, kStepResponse = 2;
 
+// the descriptor's size is part of the ABI: cat_envs/native.py (ServoSimRewards) and tests/test_servo_reward_twin.py pin it
+static_assert(sizeof(catppo_servo_sim) == 368, "catppo_servo_sim: 344 bytes up to trace_capacity + the 24-byte reward tail");
+static_assert(sizeof(catppo_servo_reward_term) == 16 && CATPPO_SERVO_REWARD_FLOATS == 32, "reward table entry / record row");
+
 // command of (env, episode, resample index): uniform in the reference ranges, dead zone, standing fraction; with a
 // fixed-command table the caller's row `e` as it stands, for every episode and resample index - in the step-response
 // instance, of segment min(t / fixed_segment_steps, S - 1) when the table is a schedule of S > 1 segments, `t` being the
@@ -90,9 +94,13 @@ __device__ __forceinline__ float init_q(const catppo_servo_sim& d, uint32_t gid,
 // that a training step runs the code it ran before the fields existed.  kEvaluate: a fixed-command table [N, 3] or an
 // evaluation record, and nothing else - the evaluation that runs inside training keeps the code it had, too.
 // kStepResponse: a command schedule or a step trace (either may be absent: two wave-uniform branches).  It is held to
-// the 64 VGPRs the other two come out at: at 8 workgroups per CU 32768 envs are one resident round, at 7 they are two
-template <int kMode>
-__global__ __launch_bounds__(kThreads, kMode == kStepResponse ? 8 : 1) void servo_sim_kernel(const catppo_servo_sim d) {
+// the 64 VGPRs the other two come out at: at 8 workgroups per CU 32768 envs are one resident round, at 7 they are two.
+// kRew: the launch with reward_terms > 0 ("Rewards").  Orthogonal to the mode; with kRew false every
+// line it adds is compiled out, so the three instances above keep their instruction streams.  The reward terms are
+// evaluated in a wave-uniform loop over the table (lane k loads entry k up front, the loop reads it with readlane), every
+// lane ends up with the same bits of every term, lane k keeps term k for the record.  The rewards-on instances are not held to 64 VGPRs
+template <int kMode, bool kRew>
+__global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew) ? 8 : 1) void servo_sim_kernel(const catppo_servo_sim d) {
   constexpr bool kEval = kMode != kTrain;
   extern __shared__ float4 lds4[];
   float* lds = reinterpret_cast<float*>(lds4);
@@ -125,6 +133,19 @@ __global__ __launch_bounds__(kThreads, kMode == kStepResponse ? 8 : 1) void serv
   float rec0 = 0.f;
   if constexpr (kEval)
     if (rec && !init) rec0 = d.eval[rec_at];
+  // reward record: lane k of a live lane group owns floats k and 16 + k of its env (two 64-byte accesses per env)
+  const bool rrec = kRew && e0 + grp < d.N;
+  const int64_t rrec_at = e * CATPPO_SERVO_REWARD_FLOATS + lane;
+  float run0 = 0.f, done0 = 0.f, a_prev = 0.f;
+  // lane k holds entry k of the table (one 16-byte load per lane, issued here, long before the loop that reads it through
+  // readlane: the loop then waits for no memory)
+  catppo_servo_reward_term mine_tm = {0, 0u, 0.f, 0.f};
+  if constexpr (kRew) {
+    if (!init && lane < d.reward_terms) mine_tm = d.reward_table[lane];
+    if (rrec && !init) run0 = d.reward_rec[rrec_at], done0 = d.reward_rec[rrec_at + 16];
+    // the last-action block of the input row: the action manager's history (zero after a step that ended an episode)
+    if (isj && !rst && D >= 45) a_prev = in[d.off_obs + 33 + lane];
+  }
 
   if (init) {
     // the first state of episode 0: default pose + noise, at rest, four feet on the ground
@@ -148,6 +169,8 @@ __global__ __launch_bounds__(kThreads, kMode == kStepResponse ? 8 : 1) void serv
     }
     if constexpr (kEval)
       if (rec) d.eval[rec_at] = 0.f;
+    if constexpr (kRew)
+      if (rrec) d.reward_rec[rrec_at] = 0.f, d.reward_rec[rrec_at + 16] = 0.f;
   } else {
     // ---- the state this step starts from: the row, or the first state of episode `ep` re-derived from the counter
     float q = 0.f, qd = 0.f, a = 0.f;
@@ -211,6 +234,50 @@ __global__ __launch_bounds__(kThreads, kMode == kStepResponse ? 8 : 1) void serv
     // ---- does this step end the episode?  Then `obs` already shows the first state of the next one.
     const bool ends = t + 1 >= d.max_episode_length || fallen;
     const uint32_t ep_out = ep + (ends ? 1u : 0u);
+    // ---- reward terms: value_k = (raw_k * weight_k) * step_dt in table order, summed from 0.f; lane k keeps value_k
+    float rsum = 0.f, mine = 0.f;
+    if constexpr (kRew) {
+      const float acc = tau_w / d.inertia, da = a - a_prev;
+      const float moving = sqrtf(cmd[0] * cmd[0] + cmd[1] * cmd[1]) > 0.1f ? 1.f : 0.f;
+      for (int k = 0; k < d.reward_terms; ++k) {
+        // lanes 0 .. 15 of the wave are its first lane group: lane k of the wave holds entry k
+        catppo_servo_reward_term tm;
+        tm.kind = __builtin_amdgcn_readlane(mine_tm.kind, k);
+        tm.joint_mask = (uint32_t)__builtin_amdgcn_readlane((int)mine_tm.joint_mask, k);
+        tm.weight = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine_tm.weight), k));
+        tm.param = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine_tm.param), k));
+        const float m = ((tm.joint_mask >> lane) & 1u) ? 1.f : 0.f;
+        float raw = 0.f;
+        switch (tm.kind) {
+          case 1: raw = expf(0.f - (ex * ex + ey * ey) / tm.param); break;
+          case 2: raw = expf(0.f - (ew * ew) / tm.param); break;
+          case 3: raw = 1.f / (1.f + (ex * ex + ey * ey) / tm.param); break;
+          case 4: raw = 1.f / (1.f + (ew * ew) / tm.param); break;
+          case 5: raw = ang[0] * ang[0] + ang[1] * ang[1]; break;
+          case 6: raw = grav[0] * grav[0] + grav[1] * grav[1]; break;
+          case 7: raw = tree16(m * (tau_w * tau_w)); break;
+          case 8: raw = tree16(m * (acc * acc)); break;
+          case 9: raw = tree16(m * (qd * qd)); break;
+          case 10: raw = tree16(m * fabsf(dq)); break;
+          case 11: raw = tree16(da * da); break;
+          case 12: raw = tree16(a * a); break;
+          case 13: raw = tree4((last_air - tm.param) * (touch ? 1.f : 0.f)) * moving; break;
+          case 14: raw = (z - tm.param) * (z - tm.param); break;
+          case 15: raw = fallen ? 1.f : 0.f; break;
+          case 16: raw = fallen ? 0.f : 1.f; break;
+          default: break;                                // the table's writer admits no other kind
+        }
+        const float value = (raw * tm.weight) * step_dt;
+        rsum = rsum + value;
+        if (lane == k) mine = value;
+      }
+      // the record: lane 15 owns the zero float 15 and the count of ended episodes (float 31)
+      const float s = run0 + mine;
+      if (rrec) {
+        d.reward_rec[rrec_at] = ends ? 0.f : s;
+        if (ends) d.reward_rec[rrec_at + 16] = done0 + (lane == 15 ? 1.f : s);
+      }
+    }
 
     // ---- step trace: one row of CATPPO_SERVO_TRACE_FLOATS per traced env, at the slot its record had counted before
     // this step (field 0, held by lane 0); registers to memory, neighbouring lanes write neighbouring floats
@@ -275,7 +342,7 @@ __global__ __launch_bounds__(kThreads, kMode == kStepResponse ? 8 : 1) void serv
     }
     if (lane == 13) {
       for (int k = 0; k < 3; ++k) row[d.off_command + k] = cmd[k];
-      row[d.off_reward] = reward;
+      row[d.off_reward] = kRew ? rsum : reward;
       row[d.off_hard_reset] = fallen ? 1.f : 0.f;
     }
     if (lane == 14) {
@@ -358,6 +425,16 @@ extern "C" int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* de
     CATPPO_CHECK_ARG(ctx, d.trace_envs >= 1 && d.trace_envs <= d.N && d.trace_capacity >= 1);
     CATPPO_CHECK_ARG(ctx, d.trace != d.state_in && d.trace != d.state_out && d.trace != d.eval && d.trace != d.fixed_command);
   }
+  CATPPO_CHECK_ARG(ctx, d.reward_terms >= 0 && d.reward_terms <= CATPPO_SERVO_REWARD_MAX_TERMS);
+  if (d.reward_terms > 0) {
+    CATPPO_CHECK_ARG(ctx, d.reward_rec != nullptr && ((uintptr_t)d.reward_rec % 16) == 0);
+    CATPPO_CHECK_ARG(ctx, d.reward_rec != d.state_in && d.reward_rec != d.state_out && d.reward_rec != d.eval &&
+                              d.reward_rec != d.trace && d.reward_rec != d.fixed_command);
+    // the entries are device memory: their writer checks kinds, masks and params (Solo12ServoSim.set_reward_table)
+    CATPPO_CHECK_ARG(ctx, d.reward_table != nullptr && ((uintptr_t)d.reward_table % 16) == 0);
+    CATPPO_CHECK_ARG(ctx, (const void*)d.reward_table != d.state_in && (const void*)d.reward_table != d.state_out &&
+                              (const void*)d.reward_table != d.reward_rec);
+  }
   // every field the kernel writes lies inside the row
   const struct { int32_t off, width; } fields[] = {
       {d.off_joint_pos, kJoints}, {d.off_joint_vel, kJoints}, {d.off_joint_acc, kJoints}, {d.off_applied_torque, kJoints},
@@ -367,9 +444,11 @@ extern "C" int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* de
   for (const auto& fl : fields) CATPPO_CHECK_ARG(ctx, fl.off >= 0 && (int64_t)fl.off + fl.width <= d.row_floats);
   const unsigned nblk = (unsigned)cdiv64(d.N, kEnvsPerBlock);
   const size_t lds_bytes = (size_t)d.row_floats * kEnvsPerBlock * sizeof(float);
-  const auto kernel = (d.trace || d.fixed_segments > 1) ? servo_sim_kernel<kStepResponse>
-                      : (d.fixed_command || d.eval)     ? servo_sim_kernel<kEvaluate>
-                                                        : servo_sim_kernel<kTrain>;
+  const int mode = (d.trace || d.fixed_segments > 1) ? kStepResponse : (d.fixed_command || d.eval) ? kEvaluate : kTrain;
+  const bool rew = d.reward_terms > 0;
+  const auto kernel = mode == kStepResponse ? (rew ? servo_sim_kernel<kStepResponse, true> : servo_sim_kernel<kStepResponse, false>)
+                      : mode == kEvaluate   ? (rew ? servo_sim_kernel<kEvaluate, true> : servo_sim_kernel<kEvaluate, false>)
+                                            : (rew ? servo_sim_kernel<kTrain, true> : servo_sim_kernel<kTrain, false>);
   hipLaunchKernelGGL(kernel, dim3(nblk), dim3(kThreads), lds_bytes, static_cast<hipStream_t>(stream), d);
   CATPPO_CHECK_LAUNCH(ctx);
   return CATPPO_OK;

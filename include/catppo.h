@@ -680,9 +680,43 @@ int catppo_set_grad_overlap(catppo_ctx* ctx, int on);      /* on: 0 | 1 | 2 set 
  * Row:  0 t (episode length the step started from) | 1 ends | 2 fallen | 3 reward (raw) | 4..6 the step's command |
  * 7..9 vx vy wz after the step | 10 roll | 11 pitch | 12 base height z | 13 feet in contact | 14 15 zero |
  * 16..19 contact flag per foot | 20..23 fz per foot | 24..35 q | 36..47 qd | 48..59 tau_w (applied_torque) |
- * 60..71 the action of this step.  The trace never changes a float of the state row or of the record. */
+ * 60..71 the action of this step.  The trace never changes a float of the state row or of the record.
+ * Rewards (trailing fields after trace_capacity; a zero-filled tail is the behaviour described so far, exactly).
+ * reward_terms = T in 1 .. CATPPO_SERVO_REWARD_MAX_TERMS: the row's off_reward field receives the sum of the T terms of
+ * reward_table instead of the built-in expression - in table order k = 0 .. T - 1, value_k = (raw_k * weight_k) * step_dt
+ * (two rounded fp32 multiplies, step_dt = dt * (float)decimation; IsaacLab's func * weight * dt) and reward = reward +
+ * value_k from 0.f, unfused.  reward_table is a device array of T entries, 16-byte aligned, read by every launch (a weight
+ * the host writes into it, in stream order, is in the next launch; by value the table would have grown the kernel
+ * arguments past the size at which the compiler keeps the code of the launches without rewards as it was).  T = 0: the
+ * built-in reward.  The evaluation record's field 3 (and 9, 10) and the trace's field 3 keep the built-in tracking
+ * expression whatever T is: a fixed score, comparable across reward configurations.
+ * raw by kind (symbols of csrc/servo_sim.hip; ex ey ew = command - velocity after the step; m = bit `lane` of joint_mask
+ * as 0 / 1; tree16, tree4: the kernel's orders):
+ *  1 expf(0 - (ex ex + ey ey) / param)       2 expf(0 - (ew ew) / param)         [param = std^2]
+ *  3 1 / (1 + (ex ex + ey ey) / param)       4 1 / (1 + (ew ew) / param)
+ *  5 ang0^2 + ang1^2                         6 g0^2 + g1^2 (after the roll-over override)
+ *  7 tree16(m tau_w^2)    8 tree16(m acc^2), acc = tau_w / inertia    9 tree16(m qd^2)    10 tree16(m |q - default|)
+ * 11 tree16((a - a_prev)^2), a_prev = state_in[off_obs + 33 + lane], 0 for an env that starts an episode: obs_dim >= 45
+ * 12 tree16(a^2)         13 tree4((last_air - param) touch) * (sqrtf(cx cx + cy cy) > 0.1f)       14 (z - param)^2
+ * 15 fallen ? 1 : 0      16 fallen ? 0 : 1
+ * Kinds 1 - 4 need param > 0, kinds 7 - 10 a joint_mask in 1 .. 0xFFF, kind 11 obs_dim >= 45: the table is device memory,
+ * so its writer checks the entries (Solo12ServoSim.set_reward_table); the entry point checks T, the record and the table
+ * pointer.  Whatever the table holds the launch stays inside its buffers: an unknown kind contributes raw = 0, kind 11
+ * with obs_dim < 45 reads a_prev = 0.
+ * reward_rec ([N, CATPPO_SERVO_REWARD_FLOATS] fp32, 16-byte aligned, required when T > 0; may alias none of state_in,
+ * state_out, eval, trace, fixed_command): floats 0 .. 14 the sums of the running episode per term, 16 .. 30 the sums of
+ * the ended episodes per term since the caller last zeroed them, 31 the count of ended episodes, 15 zero.  Per step
+ * s = rec[k] + value_k (one fp32 add); a step that ends the episode does rec[16 + k] += s, rec[k] = 0, rec[31] += 1, any
+ * other rec[k] = s.  An init launch zeroes the whole record.  No atomics, no communication between envs. */
 #define CATPPO_SERVO_EVAL_FLOATS 12
 #define CATPPO_SERVO_TRACE_FLOATS 72
+#define CATPPO_SERVO_REWARD_FLOATS 32
+#define CATPPO_SERVO_REWARD_MAX_TERMS 15
+typedef struct catppo_servo_reward_term {
+  int32_t kind;
+  uint32_t joint_mask;
+  float weight, param;
+} catppo_servo_reward_term;
 typedef struct catppo_servo_sim {
   int64_t N, env_offset;                 /* env_offset: global env id of row 0 (env-sharded runs) */
   const float* state_in;
@@ -707,6 +741,9 @@ typedef struct catppo_servo_sim {
   int32_t fixed_segment_steps;           /* control steps per segment of the schedule */
   float* trace;                          /* [trace_capacity, trace_envs, CATPPO_SERVO_TRACE_FLOATS] or NULL; 16-byte aligned */
   int32_t trace_envs, trace_capacity;    /* envs 0 .. trace_envs - 1 are traced, for trace_capacity steps */
+  int32_t reward_terms;                  /* T in 0 .. 15; 0: the built-in reward */
+  float* reward_rec;                     /* [N, CATPPO_SERVO_REWARD_FLOATS] or NULL; 16-byte aligned */
+  const catppo_servo_reward_term* reward_table;   /* device, [reward_terms]; 16-byte aligned */
 } catppo_servo_sim;
 int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* desc, void* stream);
 

@@ -9,6 +9,9 @@ three-arm comparison of profiles/servo_eval_kernel_stats.csv: CATPPO_LIB=<librar
 --trace attaches the record, a command schedule of four segments and a step trace of 32 envs, for the five-arm comparison of
 profiles/servo_trace_kernel_stats.csv: the parent's library and this library, each without a flag and with --eval, and this library
 with --trace.
+--rewards runs the task with a reward block (Isaac-Velocity-CaT-Flat-Solo12-Servo-Rewards-v0 with ShapedRewardsCfg: nine terms,
+the two exp ones among them), so that the simulator's launch is the rewards-on training instance; without the flag it is the
+rewards-off one.  profiles/servo_reward_kernel_stats.csv: the two arms alternating in one session, every run listed.
 
 Per env step the trace shows servo_sim_kernel (the simulator), the two launches of catppo_rollout_pre, the one of
 catppo_rollout_post and the policy forward."""
@@ -29,12 +32,16 @@ def main():
     ap.add_argument("--rollouts", type=int, default=10)
     ap.add_argument("--eval", action="store_true", help="attach the evaluation record and fixed commands")
     ap.add_argument("--trace", action="store_true", help="attach the record, a schedule of 4 segments and a trace of 32 envs")
+    ap.add_argument("--rewards", action="store_true", help="the task with ShapedRewardsCfg: reward terms inside the simulator launch")
     a = ap.parse_args()
     import cat_envs.tasks  # noqa: F401
     from cat_envs.shim import load_cfg_from_registry, make
     from cat_envs.tasks.utils.cleanrl.ppo import PPOTrainer
-    task = "Isaac-Velocity-CaT-Flat-Solo12-Servo-v0"
+    task = "Isaac-Velocity-CaT-Flat-Solo12-Servo-Rewards-v0" if a.rewards else "Isaac-Velocity-CaT-Flat-Solo12-Servo-v0"
     env_cfg = load_cfg_from_registry(task, "env_cfg_entry_point")
+    if a.rewards:
+        from cat_envs.tasks.locomotion.velocity.config.solo12.cat_flat_env_cfg import ShapedRewardsCfg
+        env_cfg.rewards = ShapedRewardsCfg()
     agent_cfg = load_cfg_from_registry(task, "clean_rl_cfg_entry_point")
     env_cfg.scene.num_envs = a.num_envs
     agent_cfg.minibatch_size = min(agent_cfg.minibatch_size, a.num_envs * agent_cfg.num_steps)
@@ -62,6 +69,9 @@ def main():
     torch.cuda.synchronize()
     print(f"{a.rollouts} rollouts of {trainer.T} steps x {a.num_envs} envs; mean reward/step "
           f"{float(trainer.rewards.float().mean()):.4f}")
+    if a.rewards:
+        log = env_u.reward_manager.pop_log()
+        print("reward record:", {k: round(v, 5) for k, v in (log or {}).items()})
     if a.eval or a.trace:
         steps = record[:, 0].cpu()
         assert float(steps.min()) == float(steps.max()) == a.rollouts * trainer.T, (float(steps.min()), float(steps.max()))
