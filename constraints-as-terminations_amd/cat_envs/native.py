@@ -150,6 +150,31 @@ class ServoSimRewards(ServoSimStep):
     _fields_ = [("reward_terms", C.c_int32), ("reward_rec", C.c_void_p), ("reward_table", C.c_void_p)]
 
 
+SERVO_OBS_RAW = 45                      # the raw observation: ang_vel 3 | gravity 3 | command 3 | dq 12 | qd 12 | last action 12
+SERVO_OBS_MAX_WIDTH = 64                # CATPPO_SERVO_OBS_MAX_WIDTH
+SERVO_OBS_BIAS, SERVO_OBS_NOISE, SERVO_OBS_CLIP = 1, 2, 4          # catppo_servo_obs_entry.flags
+
+
+class ServoObsEntry(C.Structure):
+    """catppo_servo_obs_entry: one float of the policy observation (device-resident table)"""
+    _fields_ = [("src", C.c_int32), ("flags", C.c_uint32), ("bias", C.c_float), ("noise_lo", C.c_float),
+                ("noise_width", C.c_float), ("clip_lo", C.c_float), ("clip_hi", C.c_float), ("scale", C.c_float)]
+
+
+SERVO_EXT_OBS = 0x4F425331              # CATPPO_SERVO_EXT_OBS: ``reserved`` of a descriptor that is followed by a ServoObs
+
+
+class ServoObs(C.Structure):
+    """catppo_servo_obs: the observation descriptor; ``table`` is a device array of ``width`` ``ServoObsEntry``"""
+    _fields_ = [("width", C.c_int32), ("off_policy_obs", C.c_int32), ("table", C.c_void_p)]
+
+
+class ServoSimObs(ServoSimRewards):
+    """catppo_servo_sim_obs: the whole catppo_servo_sim (its 368 bytes as they are) with a ``ServoObs`` right behind it.
+    ``servo_sim_step`` takes it like its base; the library reads ``obs`` only while ``reserved`` is ``SERVO_EXT_OBS``."""
+    _fields_ = [("obs", ServoObs)]
+
+
 F32, F16, F64 = 0, 1, 2                 # CATPPO_F32 / _F16 / _F64
 SUM, MAX = 0, 1                         # CATPPO_SUM / _MAX
 LR_FIXED, LR_LINEAR, LR_KEEP = 0, 1, 2
@@ -752,6 +777,8 @@ class Native:
         """one control step (or, with ``desc.init``, the first state) of the Solo12 servo surrogate"""
         if not isinstance(desc, ServoSimRewards):           # the library reads the whole catppo_servo_sim, tail included
             raise TypeError("servo_sim_step takes a native.ServoSimRewards (the whole catppo_servo_sim)")
+        if desc.reserved and not isinstance(desc, ServoSimObs):   # the library would read a catppo_servo_obs behind it
+            raise TypeError("servo_sim_step: a descriptor whose 'reserved' announces observations must be a native.ServoSimObs")
         rc = self.lib.catppo_servo_sim_step(self.h, C.byref(desc), self._stream())
         if rc:
             self._ok(rc)

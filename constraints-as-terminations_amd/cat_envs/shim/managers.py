@@ -12,6 +12,8 @@ try:  # pragma: no cover
     from isaaclab.managers.manager_base import ManagerBase, ManagerTermBase  # type: ignore
     from isaaclab.managers.manager_term_cfg import CurriculumTermCfg, ManagerTermBaseCfg  # type: ignore
     from isaaclab.managers.manager_term_cfg import RewardTermCfg  # type: ignore
+    from isaaclab.managers.manager_term_cfg import ObservationGroupCfg, ObservationTermCfg  # type: ignore
+    from isaaclab.utils.noise import AdditiveUniformNoiseCfg  # type: ignore
     HAVE_ISAACLAB = True
 except Exception:
     HAVE_ISAACLAB = False
@@ -29,6 +31,26 @@ except Exception:
     class RewardTermCfg(ManagerTermBaseCfg):
         """IsaacLab's RewTerm: the step's reward is the sum of ``func(env, **params) * weight * dt`` over the terms"""
         weight: float = MISSING
+
+    @configclass
+    class ObservationTermCfg(ManagerTermBaseCfg):
+        """IsaacLab's ObsTerm: ``func(env, **params)``, then noise, clip and scale, in this order"""
+        noise: Any = None
+        clip: Any = None              # (lo, hi) or None
+        scale: Any = None             # a number, one per element, or None
+
+    @configclass
+    class ObservationGroupCfg:
+        """IsaacLab's ObsGroup: its ObsTerm attributes in definition order are the group's terms"""
+        concatenate_terms: bool = True
+        enable_corruption: bool = False
+
+    @configclass
+    class AdditiveUniformNoiseCfg:
+        """IsaacLab's Unoise: x + U(n_min, n_max)"""
+        n_min: float = -1.0
+        n_max: float = 1.0
+        operation: str = "add"
 
     class SceneEntityCfg:
         """Names are resolved to ids against ``scene[name].joint_names / body_names``."""

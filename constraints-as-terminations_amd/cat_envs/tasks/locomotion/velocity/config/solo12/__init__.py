@@ -52,3 +52,19 @@ register(
     disable_env_checker=True,
     kwargs={"env_cfg_entry_point": f"{__name__}.cat_flat_env_cfg:Solo12ServoRewardsFlatEnvCfg_PLAY", **_KW},
 )
+
+# the servo task with an ObservationsCfg: observation terms, scales and noise inside the simulator's launch (DESIGN
+# section 9, "Observations"); the play cfg switches the noise off
+register(
+    id="Isaac-Velocity-CaT-Flat-Solo12-Servo-Obs-v0",
+    entry_point=CaTEnv,
+    disable_env_checker=True,
+    kwargs={"env_cfg_entry_point": f"{__name__}.cat_flat_env_cfg:Solo12ServoObsFlatEnvCfg", **_KW},
+)
+
+register(
+    id="Isaac-Velocity-CaT-Flat-Solo12-Servo-Obs-Play-v0",
+    entry_point=CaTEnv,
+    disable_env_checker=True,
+    kwargs={"env_cfg_entry_point": f"{__name__}.cat_flat_env_cfg:Solo12ServoObsFlatEnvCfg_PLAY", **_KW},
+)

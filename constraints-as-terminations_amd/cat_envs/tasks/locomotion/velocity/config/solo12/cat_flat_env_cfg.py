@@ -7,16 +7,21 @@ PhysX (NVIDIA only) and are out of scope; ``SyntheticCfg`` configures the device
 synthetic stream that stands in for the simulator.  Rewards: the stream simulator's are
 a pre-generated stream; on the servo surrogate ``RewardsCfg`` (the reference's two terms and values)
 or any other block of ``mdp.rewards`` terms is evaluated inside the simulator's launch
-(``Solo12ServoRewardsFlatEnvCfg``, DESIGN section 9 "Rewards").
+(``Solo12ServoRewardsFlatEnvCfg``, DESIGN section 9 "Rewards").  Observations: likewise, ``ObservationsCfg``
+(the reference's six terms, order, scales and noise ranges) is evaluated inside the servo simulator's launch
+(``Solo12ServoObsFlatEnvCfg``, DESIGN section 9 "Observations").
 """
 import math
 
+from cat_envs.shim import AdditiveUniformNoiseCfg as Unoise
 from cat_envs.shim import CurriculumTermCfg as CurrTerm
+from cat_envs.shim import ObservationGroupCfg as ObsGroup
+from cat_envs.shim import ObservationTermCfg as ObsTerm
 from cat_envs.shim import RewardTermCfg as RewTerm
 from cat_envs.shim import SceneEntityCfg, configclass
 from cat_envs.tasks.utils.cat import constraints, curriculums
 from cat_envs.tasks.utils.cat.manager_constraint_cfg import ConstraintTermCfg as ConstraintTerm
-from cat_envs.tasks.utils.mdp import rewards
+from cat_envs.tasks.utils.mdp import observations, rewards
 
 ALL_JOINTS = [".*_HAA", ".*_HFE", ".*_KFE"]
 
@@ -239,6 +244,46 @@ class Solo12ServoRewardsFlatEnvCfg(Solo12ServoFlatEnvCfg):
 class Solo12ServoRewardsFlatEnvCfg_PLAY(Solo12ServoRewardsFlatEnvCfg):
     scene: SceneCfg = SceneCfg(num_envs=50, env_spacing=3.0)
     curriculum: object = None
+
+
+# the reference observes the joints in this order (hind right before hind left), by name
+OBS_JOINTS = ["FL_HAA", "FL_HFE", "FL_KFE", "FR_HAA", "FR_HFE", "FR_KFE", "HR_HAA", "HR_HFE", "HR_KFE", "HL_HAA", "HL_HFE", "HL_KFE"]
+
+
+@configclass
+class ObservationsCfg:
+    """the reference's observation block (solo12/cat_flat_env_cfg.py ObservationsCfg): six terms, 45 floats"""
+
+    @configclass
+    class PolicyCfg(ObsGroup):
+        base_ang_vel = ObsTerm(func=observations.base_ang_vel, noise=Unoise(n_min=-0.001, n_max=0.001), scale=0.25)
+        velocity_commands = ObsTerm(func=observations.generated_commands, params={"command_name": "base_velocity"},
+                                    scale=(2.0, 2.0, 0.25))
+        projected_gravity = ObsTerm(func=observations.projected_gravity, noise=Unoise(n_min=-0.05, n_max=0.05), scale=0.1)
+        joint_pos = ObsTerm(func=observations.joint_pos, noise=Unoise(n_min=-0.01, n_max=0.01), scale=1.0,
+                            params={"asset_cfg": SceneEntityCfg("robot", joint_names=OBS_JOINTS, preserve_order=True)})
+        joint_vel = ObsTerm(func=observations.joint_vel, noise=Unoise(n_min=-0.2, n_max=0.2), scale=0.05,
+                            params={"asset_cfg": SceneEntityCfg("robot", joint_names=OBS_JOINTS, preserve_order=True)})
+        actions = ObsTerm(func=observations.last_action, scale=1.0)
+        enable_corruption: bool = True
+        concatenate_terms: bool = True
+
+    policy: PolicyCfg = PolicyCfg()
+
+
+@configclass
+class Solo12ServoObsFlatEnvCfg(Solo12ServoFlatEnvCfg):
+    """the servo task with a configurable observation block: the simulator's launch evaluates ``observations`` term by term"""
+    observations: ObservationsCfg = ObservationsCfg()
+
+
+@configclass
+class Solo12ServoObsFlatEnvCfg_PLAY(Solo12ServoObsFlatEnvCfg):
+    scene: SceneCfg = SceneCfg(num_envs=50, env_spacing=3.0)
+    curriculum: object = None
+
+    def __post_init__(self):
+        self.observations.policy.enable_corruption = False
 
 
 @configclass

@@ -183,8 +183,15 @@ class Solo12ServoSim(SyntheticSolo12Sim):
     NX = 14
 
     def __init__(self, num_envs: int, obs_dim: int, device, seed: int, syn, dt: float, decimation: int,
-                 max_episode_length: int, episode_length: torch.Tensor, reset: torch.Tensor, env_offset: int = 0):
+                 max_episode_length: int, episode_length: torch.Tensor, reset: torch.Tensor, env_offset: int = 0,
+                 policy_obs_dim: int = 0):
+        """``policy_obs_dim`` = P > 0: the row gets a second observation field ``policy_obs`` of P floats (padded to a
+        multiple of 4) that ``set_observation_table`` configures; the raw field ``obs`` stays what it is"""
         self.N, self.D, self.device = num_envs, obs_dim, torch.device(device)
+        self.P = int(policy_obs_dim)
+        if self.P and not (1 <= self.P <= native.SERVO_OBS_MAX_WIDTH and obs_dim == native.SERVO_OBS_RAW):
+            raise ValueError(f"a policy observation needs 1 <= width <= {native.SERVO_OBS_MAX_WIDTH} and the raw observation "
+                             f"of {native.SERVO_OBS_RAW} floats (got width {self.P}, obs_dim {obs_dim})")
         J, B, H = len(SOLO12_JOINTS), len(SOLO12_BODIES), self.H
         self.J, self.B = J, B
         fields = [("joint_pos", J), ("joint_vel", J), ("joint_acc", J), ("applied_torque", J),
@@ -196,13 +203,17 @@ class Solo12ServoSim(SyntheticSolo12Sim):
             self.off[name] = (o, w)
             o += w
         self.F = (o + 3) // 4 * 4
+        if self.P:                                                      # behind everything else, on a 16-byte boundary
+            self.off["policy_obs"] = (self.F, self.P)
+            self.F += (self.P + 3) // 4 * 4
         self.cur = torch.zeros(num_envs, self.F, device=self.device)
         self._slabs = [torch.zeros(num_envs, self.F, device=self.device) for _ in range(2)]
         self.cursor = -1
         self.default_joint_pos = torch.tensor(DEFAULT_JOINT_POS, device=self.device).repeat(num_envs, 1).contiguous()
         self._episode_length, self._reset = episode_length, reset       # referenced by the descriptor: keep alive
         self._nat = native.get(self.device)
-        d = self._desc = native.ServoSimRewards()
+        # with a policy observation the descriptor carries the observation descriptor behind its 368 bytes
+        d = self._desc = native.ServoSimObs() if self.P else native.ServoSimRewards()
         d.N, d.env_offset, d.row_stride, d.row_floats = num_envs, int(env_offset), self.F, self.F
         d.obs_dim, d.H, d.B = obs_dim, H, B
         names = {"projected_gravity": "projected_gravity_b", "root_pos": "root_pos_w"}
@@ -219,6 +230,8 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         self._fixed_command = self._eval_record = self._trace = None    # referenced by the descriptor: keep alive
         self._reward_record = self._reward_table = None                 # likewise; allocated by the first set_reward_table
         self._reward_entries = []
+        self._obs_table = None                                          # device table of the observation descriptor
+        self._obs_entries = []
         self._build_scene()
 
     def _table(self, t, width, what, lead=()):
@@ -310,6 +323,37 @@ class Solo12ServoSim(SyntheticSolo12Sim):
     def reward_record(self):
         """[N, 32] fp32 or None: 0..14 running sums per term | 15 zero | 16..30 sums of the ended episodes | 31 their count"""
         return self._reward_record if self._reward_entries else None
+
+    def set_observation_table(self, entries):
+        """``entries``: exactly ``policy_obs_dim`` rows ``(src, flags, bias, noise_lo, noise_width, clip_lo, clip_hi, scale)``
+        (``native.ServoObsEntry``; what ``mdp.observation_manager.build_table`` returns).  Every following launch, init
+        launches included, fills the row's ``policy_obs`` field from the finished raw observation.  The table lives on the
+        device and is rewritten here, in stream order: new noise bits are in the next launch.  The entries are checked
+        here - the library cannot read them (the kernel clamps ``src`` anyway)."""
+        entries = [tuple(e) for e in entries]
+        if not self.P:
+            raise ValueError("this simulator was built without a policy observation field (policy_obs_dim = 0)")
+        if len(entries) != self.P:
+            raise ValueError(f"{len(entries)} observation entries, the row's policy observation has {self.P} floats")
+        host = (native.ServoObsEntry * native.SERVO_OBS_MAX_WIDTH)()
+        for i, e in enumerate(entries):
+            src, flags = int(e[0]), int(e[1])
+            vals = [float(v) for v in e[2:]]
+            if len(vals) != 6 or not 0 <= src < native.SERVO_OBS_RAW or flags & ~7:
+                raise ValueError(f"observation entry {i}: src must be in 0 .. {native.SERVO_OBS_RAW - 1}, flags in 0 .. 7 and "
+                                 f"six floats must follow, got {e!r}")
+            if not all(math.isfinite(v) for v in vals) or vals[2] < 0.0 or vals[3] > vals[4]:
+                raise ValueError(f"observation entry {i}: floats must be finite, noise_width >= 0 and clip_lo <= clip_hi, got {e!r}")
+            h = host[i]
+            h.src, h.flags = src, flags
+            h.bias, h.noise_lo, h.noise_width, h.clip_lo, h.clip_hi, h.scale = vals
+        if self._obs_table is None:
+            self._obs_table = torch.zeros(C.sizeof(host), dtype=torch.uint8, device=self.device)
+            d = self._desc
+            d.obs.width, d.obs.off_policy_obs, d.obs.table = self.P, self.off["policy_obs"][0], self._obs_table.data_ptr()
+            d.reserved = native.SERVO_EXT_OBS                           # from now on every launch fills the field
+        self._obs_table.copy_(torch.frombuffer(bytearray(host), dtype=torch.uint8))
+        self._obs_entries = entries
 
     def reset(self):
         """the first state of episode 0 in the state buffer"""
@@ -444,6 +488,20 @@ class CaTEnv:
         kind = str(getattr(syn, "kind", "stream"))
         if kind not in ("stream", "servo"):
             raise ValueError(f"SyntheticCfg.kind must be 'stream' or 'servo', got {kind!r}")
+        # cfg.observations: the policy's input is a second field of the simulator's row, filled inside its launch (DESIGN
+        # section 9, "Observations"); the table is built first because its width is part of the row's layout
+        self._obs_field, self._obs_table = "obs", None
+        if getattr(cfg, "observations", None) is not None:
+            if kind != "servo":
+                raise TypeError("cfg.observations needs the closed-loop simulator (SyntheticCfg.kind = 'servo'): the "
+                                "observation terms are evaluated inside its launch; the stream simulator's observation is a "
+                                "pre-generated stream")
+            if int(syn.obs_dim) != native.SERVO_OBS_RAW:
+                raise ValueError(f"cfg.observations reads the simulator's raw observation of {native.SERVO_OBS_RAW} floats: "
+                                 f"synthetic.obs_dim is {syn.obs_dim}")
+            from cat_envs.tasks.utils.mdp import observation_manager as OM
+            self._obs_table = OM.build_table(OM.policy_group(cfg.observations), SOLO12_JOINTS, DEFAULT_JOINT_POS)
+            self._obs_field, self.obs_dim = "policy_obs", len(self._obs_table[0])
         if kind == "stream":
             self.sim = SyntheticSolo12Sim(self.num_envs, self.obs_dim, self.device, seed + int(syn.seed_offset),
                                           int(syn.stream_steps))
@@ -466,11 +524,12 @@ class CaTEnv:
         if kind == "servo":
             # the closed-loop simulator reads the env's own episode counters and reset mask; an env-sharded run names the
             # global id of its first env (cfg.scene.env_offset), so that the shards reproduce the single-process envs
-            self.sim = Solo12ServoSim(self.num_envs, self.obs_dim, self.device, seed + int(syn.seed_offset), syn,
+            self.sim = Solo12ServoSim(self.num_envs, int(syn.obs_dim), self.device, seed + int(syn.seed_offset), syn,
                                       cfg.sim.dt, cfg.decimation, self.max_episode_length, self.episode_length_buf,
-                                      self.reset_buf, env_offset=int(getattr(cfg.scene, "env_offset", 0) or 0))
+                                      self.reset_buf, env_offset=int(getattr(cfg.scene, "env_offset", 0) or 0),
+                                      policy_obs_dim=self.obs_dim if self._obs_table is not None else 0)
             self.scene = self.sim.scene
-        self.obs_buf = {"policy": self.sim.view("obs")}
+        self.obs_buf = {"policy": self.sim.view(self._obs_field)}
         self._rstep = None
         self._nat = None
         self.load_managers()
@@ -504,6 +563,10 @@ class CaTEnv:
             from cat_envs.tasks.utils.mdp.reward_manager import RewardManager
             self.reward_manager = RewardManager(self.cfg.rewards, self)
             print("[INFO] Reward Manager: ", self.reward_manager)
+        if self._obs_table is not None:
+            from cat_envs.tasks.utils.mdp.observation_manager import ObservationManager
+            self.observation_manager = ObservationManager(self.cfg.observations, self, *self._obs_table)
+            print("[INFO] Observation Manager: ", self.observation_manager)
 
     # evaluation ------------------------------------------------------------------------------
     def _servo_sim(self) -> Solo12ServoSim:
@@ -520,6 +583,12 @@ class CaTEnv:
     def set_trace(self, trace: torch.Tensor | None):
         """attach (or, with None, detach) the simulator's step trace [T, K, 72]"""
         self._servo_sim().set_trace(trace)
+
+    def set_observation_corruption(self, on: bool):
+        """observation noise on or off from the next step on (needs cfg.observations)"""
+        if not hasattr(self, "observation_manager"):
+            raise TypeError("observation corruption needs cfg.observations")
+        self.observation_manager.set_corruption(on)
 
     def set_eval_record(self, record: torch.Tensor | None):
         """attach (or, with None, detach) the simulator's per-env evaluation record [N, 12]"""
@@ -564,6 +633,8 @@ class CaTEnv:
         fp.update(self.sim.fingerprint())
         if hasattr(self, "reward_manager"):          # only then: fingerprints of runs without rewards keep their fields
             fp["reward_terms"] = self.reward_manager.fingerprint()
+        if hasattr(self, "observation_manager"):     # likewise
+            fp["observation_terms"] = self.observation_manager.fingerprint()
         return fp
 
     def state_dict(self) -> dict:
@@ -577,6 +648,8 @@ class CaTEnv:
             sd["constraints"] = self.constraint_manager.state_dict()
         if hasattr(self, "reward_manager"):
             sd["rewards"] = self.reward_manager.state_dict()
+        if hasattr(self, "observation_manager"):     # the policy field is part of the simulator's ``cur``; the switch is not
+            sd["observations"] = self.observation_manager.state_dict()
         return sd
 
     def check_state_dict(self, sd: dict):
@@ -588,6 +661,10 @@ class CaTEnv:
             keys.append("rewards")
         elif "rewards" in sd:
             raise ValueError("run state: it carries reward terms, this env has no cfg.rewards")
+        if hasattr(self, "observation_manager"):
+            keys.append("observations")
+        elif "observations" in sd:
+            raise ValueError("run state: it carries observation terms, this env has no cfg.observations")
         missing = [k for k in keys if k not in sd]
         if missing:
             raise ValueError(f"run state: the env's part lacks {missing}")
@@ -605,6 +682,8 @@ class CaTEnv:
                 raise ValueError(f"run state: max_p of constraint terms {unknown} that this env does not have")
         if hasattr(self, "reward_manager"):
             self.reward_manager.check_state_dict(sd["rewards"])
+        if hasattr(self, "observation_manager"):
+            self.observation_manager.check_state_dict(sd["observations"])
 
     def load_state_dict(self, sd: dict):
         """IN PLACE (``copy_`` into the existing tensors, never a rebound attribute): the fused step's argument block, the
@@ -620,6 +699,8 @@ class CaTEnv:
             self.constraint_manager.load_state_dict(sd["constraints"])
         if hasattr(self, "reward_manager"):
             self.reward_manager.load_state_dict(sd["rewards"])
+        if hasattr(self, "observation_manager"):
+            self.observation_manager.load_state_dict(sd["observations"])
         self.curriculum_manager.load_state_dict(sd["curriculum"])      # through set_term_cfg: the next launch carries it
 
     # episode control -------------------------------------------------------------------------
@@ -699,7 +780,7 @@ class CaTEnv:
             st.time_outs, st.terminated = self.reset_time_outs.data_ptr(), self.reset_terminated.data_ptr()
             st.reset, st.reward, st.dones = self.reset_buf.data_ptr(), self.reward_buf.data_ptr(), self._dones.data_ptr()
             st.zero_action_on_reset = 1
-            obs = self.sim.view("obs")
+            obs = self.sim.view(self._obs_field)
             st.obs_raw, st.obs_ld = obs.data_ptr(), obs.stride(0)
             self._xchg = nat.rollout_xchg_new(cm.cat._p_cstr.shape[1], self.obs_dim)
             st.xchg = self._xchg.data_ptr()

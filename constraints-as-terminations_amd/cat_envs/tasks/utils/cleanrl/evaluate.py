@@ -208,7 +208,8 @@ class EvalResult:
 
 
 def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool = True,
-                    fresh_cat_state: bool = False, segment_steps: int | None = None, trace_envs: int = 0) -> EvalResult:
+                    fresh_cat_state: bool = False, segment_steps: int | None = None, trace_envs: int = 0,
+                    corruption: bool | None = None) -> EvalResult:
     """Roll ``policy`` out for ``steps`` control steps from a fresh reset and measure it.
 
     ``policy`` is an ``Agent`` - its observations are normalised by the frozen ``obs_rms`` and the action is the mean
@@ -228,7 +229,11 @@ def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool 
     running for the length of the evaluation, so every term's ``max_p`` is what the caller set through ``set_term_cfg``.  The
     result is then a function of the parameters, the observation normaliser, the ``max_p`` vector, the env cfg and seed,
     ``steps`` and ``commands`` alone: two such evaluations agree bit for bit whatever the env did in between (DESIGN
-    section 11).  The default leaves the CaT state as the env's last step left it."""
+    section 11).  The default leaves the CaT state as the env's last step left it.
+
+    ``corruption`` (envs with ``cfg.observations``): None leaves the env's observation-noise switch as it is; a bool sets it
+    for the evaluation and puts it back afterwards, also when the roll-out raises.  The record and the trace read state,
+    not observations: the noise reaches them only through the actions the policy takes on what it sees."""
     import contextlib
     import torch
     from cat_envs.tasks.utils.cleanrl.ppo import Agent
@@ -276,11 +281,18 @@ def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool 
         cm._ep_prob.zero_()
     u.set_eval_record(record)                                         # TypeError on the stream simulator
     trace = torch.zeros(steps, trace_envs, TRACE_FLOATS, device=dev) if trace_envs else None
+    om = getattr(u, "observation_manager", None)
+    if corruption is not None and om is None:
+        u.set_eval_record(None)
+        raise TypeError("evaluate_policy(corruption=...) needs an env with cfg.observations")
+    corruption_before = None if om is None else om.corruption
     frozen = contextlib.ExitStack()
     if fresh_cat_state:
         u.fresh_cat_state()
         frozen.enter_context(u.curriculum_frozen())
     try:
+        if corruption is not None:
+            om.set_corruption(corruption)
         if lead:
             u.set_fixed_commands(table, segment_steps)
         else:
@@ -309,6 +321,8 @@ def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool 
             u.set_trace(None)
         u.set_eval_record(None)
         u.set_fixed_commands(None)
+        if corruption is not None:
+            om.set_corruption(corruption_before)
     res = EvalResult(per_env=record.cpu().numpy(), commands=None if table is None else table.cpu().numpy(),
                      cat_reward=cat_reward.cpu().numpy(), termination_prob=term_prob.cpu().numpy(),
                      violations=viol.cpu().numpy(), term_names=names, trace=None if trace is None else trace.cpu().numpy(),

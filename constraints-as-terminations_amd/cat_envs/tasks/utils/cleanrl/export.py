@@ -196,7 +196,15 @@ def export_policy_as_onnx(state_dict, path: str, batch=1) -> str:
     return path
 
 
-def export_policy(state_dict, directory: str) -> Dict[str, str]:
-    """``<directory>/model.onnx`` + ``<directory>/model.pt`` (play.py:111-135)"""
-    return {"onnx": export_policy_as_onnx(state_dict, os.path.join(directory, "model.onnx")),
-            "jit": export_policy_as_jit(state_dict, os.path.join(directory, "model.pt"))}
+def export_policy(state_dict, directory: str, observation_spec=None) -> Dict[str, str]:
+    """``<directory>/model.onnx`` + ``<directory>/model.pt`` (play.py:111-135).  ``observation_spec`` (a dict, see
+    ``ObservationManager.spec``): also ``<directory>/observations.json``, the input contract of the deployed policy -
+    term names, slices, sources, scales, clips and the joint order of the vector the models take"""
+    out = {"onnx": export_policy_as_onnx(state_dict, os.path.join(directory, "model.onnx")),
+           "jit": export_policy_as_jit(state_dict, os.path.join(directory, "model.pt"))}
+    if observation_spec is not None:
+        import json
+        out["observations"] = os.path.join(directory, "observations.json")
+        with open(out["observations"], "w") as f:
+            json.dump(observation_spec, f, indent=1)
+    return out

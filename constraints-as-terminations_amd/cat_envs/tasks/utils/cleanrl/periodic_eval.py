@@ -246,6 +246,13 @@ def make_eval_env_cfg(env_cfg, eval_envs: int):
         cfg.scene.env_offset = 0
     cfg.seed = eval_seed(int(getattr(env_cfg, "seed", 0) or 0))
     cfg.curriculum = None
+    obs = getattr(cfg, "observations", None)
+    if obs is not None:                          # Eval/* is measured without sensor noise: a clean, comparable yardstick
+        group = obs["policy"] if isinstance(obs, dict) else obs.policy
+        if isinstance(group, dict):
+            group["enable_corruption"] = False
+        else:
+            group.enable_corruption = False
     return cfg
 
 

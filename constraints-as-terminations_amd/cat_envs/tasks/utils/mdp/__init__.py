@@ -1,2 +1,3 @@
-from . import rewards  # noqa: F401
+from . import observations, rewards  # noqa: F401
+from .observation_manager import ObservationManager  # noqa: F401
 from .reward_manager import RewardManager  # noqa: F401

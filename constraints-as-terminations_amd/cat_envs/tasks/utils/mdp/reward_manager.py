@@ -30,7 +30,7 @@ class RewardManager(ManagerBase):
                 raise TypeError(f"Configuration for term '{name}' is not RewardTermCfg. Received: '{type(term)}'.")
             self._cfgs[name] = term
         joint_names = env.scene["robot"].joint_names
-        self._names, table = R.build_table(self.cfg, joint_names, env.obs_dim)
+        self._names, table = R.build_table(self.cfg, joint_names, env.sim.D)       # the raw observation's width
         if not table:
             raise ValueError("cfg.rewards has no term of non-zero weight: nothing to evaluate (leave cfg.rewards unset for "
                              "the simulator's built-in reward)")

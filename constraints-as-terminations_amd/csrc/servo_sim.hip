@@ -15,6 +15,8 @@ namespace {
 
 constexpr int kEnvsPerBlock = 16, kThreads = 256, kJoints = 12, kPrivate = 14;
 constexpr uint32_t kTagCommand = 0x434D4453u, kTagInit = 0x494E4954u;   // "CMDS", "INIT": fourth Philox counter word
+constexpr uint32_t kTagObs = 0x4F42534Eu;                                // "OBSN": the observation noise
+constexpr int kRawObs = 45;                                              // the raw observation a policy observation reads
 
 // G[k][lane]: the fixed 5 x 12 matrix of the base model (rows vx, vy, wz, roll, pitch)
 __device__ __forceinline__ float gain(int k, int lane) {
@@ -44,6 +46,8 @@ __device__ __forceinline__ float tree4(float x) {
   return x;
 }
 
+__device__ __forceinline__ const catppo_servo_obs& first_of(const catppo_servo_obs& o) { return o; }
+
 __device__ __forceinline__ float pick(const rng::u32x4& r, int w) { return rng::uniform_open(w == 0 ? r.x : w == 1 ? r.y : w == 2 ? r.z : r.w); }
 
 // the three instances of the kernel (see the kernel): what the launch's descriptor asks for
@@ -52,6 +56,9 @@ constexpr int kTrain = 0, kEvaluate = 1, kStepResponse = 2;
 // the descriptor's size is part of the ABI: cat_envs/native.py (ServoSimRewards) and tests/test_servo_reward_twin.py pin it
 static_assert(sizeof(catppo_servo_sim) == 368, "catppo_servo_sim: 344 bytes up to trace_capacity + the 24-byte reward tail");
 static_assert(sizeof(catppo_servo_reward_term) == 16 && CATPPO_SERVO_REWARD_FLOATS == 32, "reward table entry / record row");
+static_assert(sizeof(catppo_servo_obs_entry) == 32 && CATPPO_SERVO_OBS_MAX_WIDTH == 64, "observation table entry: two 16-byte loads");
+static_assert(offsetof(catppo_servo_sim_obs, obs) == sizeof(catppo_servo_sim) && sizeof(catppo_servo_obs) == 16,
+              "catppo_servo_sim_obs: the observation descriptor lies right behind the 368 bytes");
 
 // command of (env, episode, resample index): uniform in the reference ranges, dead zone, standing fraction; with a
 // fixed-command table the caller's row `e` as it stands, for every episode and resample index - in the step-response
@@ -99,8 +106,14 @@ __device__ __forceinline__ float init_q(const catppo_servo_sim& d, uint32_t gid,
 // line it adds is compiled out, so the three instances above keep their instruction streams.  The reward terms are
 // evaluated in a wave-uniform loop over the table (lane k loads entry k up front, the loop reads it with readlane), every
 // lane ends up with the same bits of every term, lane k keeps term k for the record.  The rewards-on instances are not held to 64 VGPRs
-template <int kMode, bool kRew>
-__global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew) ? 8 : 1) void servo_sim_kernel(const catppo_servo_sim d) {
+// Obs: empty, or catppo_servo_obs for the launch with an observation table ("Observations"): a post-pass
+// over the finished LDS row fills the row's second observation field.  Orthogonal to both; only the obs-on launch carries
+// the second kernel argument, and with the pack empty every line it adds is compiled out.  LDS (16 rows of about 356
+// floats) admits 7 workgroups of the obs-on instances per CU, so they are not held to 64 VGPRs either.
+template <int kMode, bool kRew, typename... Obs>
+__global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeof...(Obs) == 0) ? 8 : 1) void servo_sim_kernel(
+    const catppo_servo_sim d, const Obs... obs_desc) {
+  constexpr bool kObs = sizeof...(Obs) != 0;
   constexpr bool kEval = kMode != kTrain;
   extern __shared__ float4 lds4[];
   float* lds = reinterpret_cast<float*>(lds4);
@@ -126,6 +139,8 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew) ? 8 : 1
   float cmd[3];
   command_of<kMode>(d, e, gid, ep, (uint32_t)(t / d.resample_steps), t, cmd);
   float* obs = row + d.off_obs;
+  // (episode, episode length) of the state the observation describes: the key of its noise
+  uint32_t obs_ep = 0u, obs_t = 0u;
   // evaluation record: lane k < 12 of a live lane group owns field k of its env (one 48-byte access per env); the spare
   // groups past N, which recompute env N - 1, neither read nor write it
   const bool rec = kEval && d.eval != nullptr && e0 + grp < d.N && isj;
@@ -234,6 +249,7 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew) ? 8 : 1
     // ---- does this step end the episode?  Then `obs` already shows the first state of the next one.
     const bool ends = t + 1 >= d.max_episode_length || fallen;
     const uint32_t ep_out = ep + (ends ? 1u : 0u);
+    if constexpr (kObs) obs_ep = ep_out, obs_t = ends ? 0u : (uint32_t)(t + 1);
     // ---- reward terms: value_k = (raw_k * weight_k) * step_dt in table order, summed from 0.f; lane k keeps value_k
     float rsum = 0.f, mine = 0.f;
     if constexpr (kRew) {
@@ -391,6 +407,44 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew) ? 8 : 1
   }
   __syncthreads();
 
+  // ---- policy observation: float j = scale((clip(noise(bias(raw[src_j]))))) in IsaacLab's ObservationManager order.  Lane l
+  // of the env's group produces floats 4 l .. 4 l + 3 from one Philox block and writes one float4; the floats past `width`
+  // of the padded field stay the zeros the row was filled with
+  if constexpr (kObs) {
+    const catppo_servo_obs& o = first_of(obs_desc...);
+    if (4 * lane < o.width) {
+      float x[4] = {0.f, 0.f, 0.f, 0.f};
+      catppo_servo_obs_entry en[4];
+      uint32_t noisy = 0u;
+#pragma unroll
+      for (int w = 0; w < 4; ++w) {
+        const int j = 4 * lane + w;
+        en[w] = o.table[j < o.width ? j : o.width - 1];
+        noisy |= en[w].flags & 2u;
+      }
+      rng::u32x4 r = {0u, 0u, 0u, 0u};
+      if (noisy)
+        r = rng::philox4x32_10(rng::u32x4{gid, obs_ep, (obs_t << 4) | (uint32_t)lane, kTagObs}, (uint32_t)d.seed,
+                               (uint32_t)(d.seed >> 32));
+#pragma unroll
+      for (int w = 0; w < 4; ++w) {
+        const catppo_servo_obs_entry& E = en[w];
+        const int src = E.src < 0 ? 0 : E.src < kRawObs ? E.src : kRawObs - 1;
+        float v = obs[src];
+        if (E.flags & 1u) v = v + E.bias;
+        if (E.flags & 2u) v = (v + pick(r, w) * E.noise_width) + E.noise_lo;
+        if (E.flags & 4u) {
+          v = v < E.clip_lo ? E.clip_lo : v;
+          v = v > E.clip_hi ? E.clip_hi : v;
+        }
+        v = v * E.scale;
+        if (4 * lane + w < o.width) x[w] = v;
+      }
+      *reinterpret_cast<float4*>(row + o.off_policy_obs + 4 * lane) = float4{x[0], x[1], x[2], x[3]};
+    }
+    __syncthreads();
+  }
+
   const int F4 = F >> 2;
   const int64_t stride4 = d.row_stride >> 2;
   float4* out4 = reinterpret_cast<float4*>(d.state_out);
@@ -406,6 +460,9 @@ extern "C" int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* de
   CATPPO_CHECK_ARG(ctx, ctx != nullptr);
   CATPPO_CHECK_ARG(ctx, desc != nullptr);
   const catppo_servo_sim& d = *desc;
+  // reserved names what lies behind the descriptor: nothing, or the observation descriptor of a catppo_servo_sim_obs
+  CATPPO_CHECK_ARG(ctx, d.reserved == 0 || d.reserved == CATPPO_SERVO_EXT_OBS);
+  const catppo_servo_obs* obs = d.reserved == CATPPO_SERVO_EXT_OBS ? &reinterpret_cast<const catppo_servo_sim_obs*>(desc)->obs : nullptr;
   CATPPO_CHECK_ARG(ctx, d.N >= 1 && d.N < (int64_t(1) << 31) && d.env_offset >= 0 && d.env_offset + d.N < (int64_t(1) << 32));
   CATPPO_CHECK_ARG(ctx, d.state_in && d.state_out && d.episode_length);
   CATPPO_CHECK_ARG(ctx, d.init || (d.action && d.reset && d.state_in != d.state_out));
@@ -442,6 +499,19 @@ extern "C" int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* de
       {d.off_first_contact, d.B}, {d.off_forces, d.H * d.B * 3}, {d.off_reward, 1}, {d.off_hard_reset, 1},
       {d.off_obs, d.obs_dim}, {d.off_servo, kPrivate}};
   for (const auto& fl : fields) CATPPO_CHECK_ARG(ctx, fl.off >= 0 && (int64_t)fl.off + fl.width <= d.row_floats);
+  if (obs) {
+    const catppo_servo_obs& o = *obs;
+    CATPPO_CHECK_ARG(ctx, d.obs_dim == kRawObs && d.max_episode_length < (int64_t(1) << 27));
+    CATPPO_CHECK_ARG(ctx, o.width >= 1 && o.width <= CATPPO_SERVO_OBS_MAX_WIDTH);
+    const int64_t padded = (o.width + 3) / 4 * 4;
+    CATPPO_CHECK_ARG(ctx, o.off_policy_obs >= 0 && o.off_policy_obs % 4 == 0 && o.off_policy_obs + padded <= d.row_floats);
+    CATPPO_CHECK_ARG(ctx, o.off_policy_obs + padded <= d.off_obs || o.off_policy_obs >= d.off_obs + kRawObs);
+    // the entries are device memory: whatever they hold the launch stays inside the row (src is clamped in the kernel)
+    const void* tb = o.table;
+    CATPPO_CHECK_ARG(ctx, tb != nullptr && ((uintptr_t)tb % 16) == 0);
+    CATPPO_CHECK_ARG(ctx, tb != d.state_in && tb != d.state_out && tb != d.eval && tb != d.trace && tb != d.fixed_command &&
+                              tb != d.reward_rec && tb != (const void*)d.reward_table);
+  }
   const unsigned nblk = (unsigned)cdiv64(d.N, kEnvsPerBlock);
   const size_t lds_bytes = (size_t)d.row_floats * kEnvsPerBlock * sizeof(float);
   const int mode = (d.trace || d.fixed_segments > 1) ? kStepResponse : (d.fixed_command || d.eval) ? kEvaluate : kTrain;
@@ -449,7 +519,16 @@ extern "C" int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* de
   const auto kernel = mode == kStepResponse ? (rew ? servo_sim_kernel<kStepResponse, true> : servo_sim_kernel<kStepResponse, false>)
                       : mode == kEvaluate   ? (rew ? servo_sim_kernel<kEvaluate, true> : servo_sim_kernel<kEvaluate, false>)
                                             : (rew ? servo_sim_kernel<kTrain, true> : servo_sim_kernel<kTrain, false>);
-  hipLaunchKernelGGL(kernel, dim3(nblk), dim3(kThreads), lds_bytes, static_cast<hipStream_t>(stream), d);
+  if (obs) {
+    const auto okernel =
+        mode == kStepResponse ? (rew ? servo_sim_kernel<kStepResponse, true, catppo_servo_obs> : servo_sim_kernel<kStepResponse, false, catppo_servo_obs>)
+        : mode == kEvaluate   ? (rew ? servo_sim_kernel<kEvaluate, true, catppo_servo_obs> : servo_sim_kernel<kEvaluate, false, catppo_servo_obs>)
+                              : (rew ? servo_sim_kernel<kTrain, true, catppo_servo_obs> : servo_sim_kernel<kTrain, false, catppo_servo_obs>);
+    hipLaunchKernelGGL(okernel, dim3(nblk), dim3(kThreads), lds_bytes, static_cast<hipStream_t>(stream), d, *obs);
+  } else {
+    hipLaunchKernelGGL(kernel, dim3(nblk), dim3(kThreads), lds_bytes, static_cast<hipStream_t>(stream), d);
+  }
   CATPPO_CHECK_LAUNCH(ctx);
   return CATPPO_OK;
 }
+

@@ -729,7 +729,7 @@ typedef struct catppo_servo_sim {
   const uint8_t* reset;                  /* [N] */
   const int64_t* episode_length;         /* [N], before this step's increment */
   int64_t max_episode_length;
-  int32_t decimation, resample_steps, init, reserved;
+  int32_t decimation, resample_steps, init, reserved;   /* reserved: 0, or CATPPO_SERVO_EXT_OBS (see "Observations" below) */
   uint64_t seed;
   float default_joint_pos[12];
   float dt, kp, kd, inertia, tau_max, action_scale, vel_alpha, tilt_beta, tilt_max, reward_scale, foot_clearance,
@@ -746,6 +746,45 @@ typedef struct catppo_servo_sim {
   const catppo_servo_reward_term* reward_table;   /* device, [reward_terms]; 16-byte aligned */
 } catppo_servo_sim;
 int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* desc, void* stream);
+
+/* Observations ("Observations").  desc->reserved == CATPPO_SERVO_EXT_OBS: `desc` is the head of a
+ * catppo_servo_sim_obs, i.e. a second, small descriptor lies right behind the 368 bytes of catppo_servo_sim (which stays
+ * what it is: the launches without it carry the same kernel argument as before).  reserved == 0: nothing lies behind it;
+ * any other value is an error.  With it the row gets a second observation field, the POLICY observation - `width` = P
+ * floats at off_policy_obs (multiple of 4; the field is padded with zeros to a multiple of 4 floats, lies inside row_floats
+ * and is disjoint from [off_obs, off_obs + 45)).  The raw observation at off_obs stays exactly where and what it is
+ * (obs_dim == 45 is required); every other float of the row, the records and the trace are what the launch without the
+ * second descriptor writes.
+ * A post-pass over the finished row computes, for output float j with entry E = table[j], in fp32, unfused, in the order of
+ * IsaacLab's ObservationManager (noise, clip, scale):
+ *   x = raw[clamp(E.src, 0, 44)]
+ *   if (E.flags & 1) x = x + E.bias
+ *   if (E.flags & 2) x = (x + u * E.noise_width) + E.noise_lo            u = uniform in (0, 1) from the Philox word below
+ *   if (E.flags & 4) x = x < E.clip_lo ? E.clip_lo : x;  x = x > E.clip_hi ? E.clip_hi : x       (a NaN passes through)
+ *   x = x * E.scale
+ * u: word j & 3 of Philox4x32-10 with key = seed and counter {global env id, ep', (t' << 4) | (j >> 2), "OBSN"}, where
+ * (ep', t') are the episode and the episode length of the state the observation describes: (0, 0) in an init launch,
+ * (episode + 1, 0) in a step that ends its episode, (episode, episode_length + 1) otherwise; max_episode_length < 2^27.
+ * It covers init launches and the post-reset observation of a step that ends an episode alike.
+ * table is a DEVICE array of P entries, 16-byte aligned, read by every launch: entries the host rewrites in stream order
+ * (the noise bits, say) are in the next launch, under graph replay too.  It may alias none of the state buffers, the
+ * records, the trace, the command table or the reward table. */
+#define CATPPO_SERVO_OBS_MAX_WIDTH 64
+#define CATPPO_SERVO_EXT_OBS 0x4F425331   /* "OBS1": value of catppo_servo_sim.reserved that announces catppo_servo_sim_obs */
+typedef struct catppo_servo_obs_entry {   /* 32 bytes, one per float of the policy observation */
+  int32_t src;                            /* index into the raw 45-float observation of the row (field off_obs) */
+  uint32_t flags;                         /* bit 0 bias, bit 1 noise, bit 2 clip */
+  float bias, noise_lo, noise_width, clip_lo, clip_hi, scale;
+} catppo_servo_obs_entry;
+typedef struct catppo_servo_obs {
+  int32_t width;                          /* P in 1 .. CATPPO_SERVO_OBS_MAX_WIDTH: floats of the policy observation */
+  int32_t off_policy_obs;                 /* row offset of the policy observation, multiple of 4 */
+  const catppo_servo_obs_entry* table;    /* DEVICE array [P], 16-byte aligned */
+} catppo_servo_obs;
+typedef struct catppo_servo_sim_obs {
+  catppo_servo_sim sim;                   /* sim.reserved = CATPPO_SERVO_EXT_OBS */
+  catppo_servo_obs obs;
+} catppo_servo_sim_obs;
 
 /* ---- test hook (ABI 0.6) ------------------------------------------------------------------------------------------
  * buf != NULL ([2][M] int32, device): the head / loss kernel of every following catppo_ppo_minibatch_* call writes the clip

@@ -60,6 +60,8 @@ def main(argv=None):
     parser.add_argument("--eval_segment_steps", type=int, default=100, help="Control steps per segment of --eval_schedule.")
     parser.add_argument("--trace_envs", type=int, default=0, help="Record the first K envs step by step (0: off).")
     parser.add_argument("--stochastic", action="store_true", default=False, help="Evaluate with sampled actions.")
+    parser.add_argument("--obs_noise", choices=("on", "off"), default=None,
+                        help="Observation noise of a task with cfg.observations (default: what the task's cfg says).")
     cli_args.add_clean_rl_args(parser)
     args_cli = parser.parse_args(argv)
     if args_cli.eval_schedule is not None:
@@ -78,6 +80,10 @@ def main(argv=None):
         env_cfg.scene.num_envs = args_cli.num_envs
     if args_cli.device is not None:
         env_cfg.sim.device = args_cli.device
+    if args_cli.obs_noise is not None:
+        if getattr(env_cfg, "observations", None) is None:
+            parser.error("--obs_noise needs a task with cfg.observations")
+        env_cfg.observations.policy.enable_corruption = args_cli.obs_noise == "on"
     agent_cfg = cli_args.parse_clean_rl_cfg(args_cli.task, args_cli)
     log_root_path = os.path.abspath(os.path.join("logs", "clean_rl", agent_cfg.experiment_name))
     print(f"[INFO] Loading experiment from directory: {log_root_path}")
@@ -90,9 +96,13 @@ def main(argv=None):
     actor.eval()
 
     from cat_envs.tasks.utils.cleanrl.export import export_policy
-    exported = export_policy(actor.state_dict(), os.path.join(os.path.dirname(resume_path), "exported"))
+    om = getattr(env.unwrapped, "observation_manager", None)
+    exported = export_policy(actor.state_dict(), os.path.join(os.path.dirname(resume_path), "exported"),
+                             observation_spec=None if om is None else om.spec())
     print(f"[INFO] Exported ONNX model to {exported['onnx']}")
     print(f"[INFO] Exported .pt model to {exported['jit']}")
+    if om is not None:
+        print(f"[INFO] Wrote the policy's input contract to {exported['observations']}")
 
     obs = env.reset()[0]["policy"]
     ret = 0.0

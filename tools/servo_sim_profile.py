@@ -12,6 +12,9 @@ with --trace.
 --rewards runs the task with a reward block (Isaac-Velocity-CaT-Flat-Solo12-Servo-Rewards-v0 with ShapedRewardsCfg: nine terms,
 the two exp ones among them), so that the simulator's launch is the rewards-on training instance; without the flag it is the
 rewards-off one.  profiles/servo_reward_kernel_stats.csv: the two arms alternating in one session, every run listed.
+--obs runs the task with the reference's observation block (Isaac-Velocity-CaT-Flat-Solo12-Servo-Obs-v0, noise on), so that the
+simulator's launch is the obs-on training instance.  profiles/servo_obs_kernel_stats.csv: the parent's library, this library
+without the flag and this library with --obs, alternating in one session, every run listed.
 
 Per env step the trace shows servo_sim_kernel (the simulator), the two launches of catppo_rollout_pre, the one of
 catppo_rollout_post and the policy forward."""
@@ -33,11 +36,15 @@ def main():
     ap.add_argument("--eval", action="store_true", help="attach the evaluation record and fixed commands")
     ap.add_argument("--trace", action="store_true", help="attach the record, a schedule of 4 segments and a trace of 32 envs")
     ap.add_argument("--rewards", action="store_true", help="the task with ShapedRewardsCfg: reward terms inside the simulator launch")
+    ap.add_argument("--obs", action="store_true", help="the task with ObservationsCfg: observation terms inside the simulator launch")
     a = ap.parse_args()
+    if a.obs and a.rewards:
+        ap.error("--obs and --rewards are separate arms")
     import cat_envs.tasks  # noqa: F401
     from cat_envs.shim import load_cfg_from_registry, make
     from cat_envs.tasks.utils.cleanrl.ppo import PPOTrainer
-    task = "Isaac-Velocity-CaT-Flat-Solo12-Servo-Rewards-v0" if a.rewards else "Isaac-Velocity-CaT-Flat-Solo12-Servo-v0"
+    task = ("Isaac-Velocity-CaT-Flat-Solo12-Servo-Rewards-v0" if a.rewards else
+            "Isaac-Velocity-CaT-Flat-Solo12-Servo-Obs-v0" if a.obs else "Isaac-Velocity-CaT-Flat-Solo12-Servo-v0")
     env_cfg = load_cfg_from_registry(task, "env_cfg_entry_point")
     if a.rewards:
         from cat_envs.tasks.locomotion.velocity.config.solo12.cat_flat_env_cfg import ShapedRewardsCfg
@@ -72,6 +79,10 @@ def main():
     if a.rewards:
         log = env_u.reward_manager.pop_log()
         print("reward record:", {k: round(v, 5) for k, v in (log or {}).items()})
+    if a.obs:
+        sim = env_u.sim
+        diff = (sim.view("policy_obs")[:, 0:3] != sim.view("obs")[:, 0:3] * 0.25).float().mean()
+        print(f"policy observation: {env_u.obs_dim} floats, row of {sim.F} floats, noisy share of base_ang_vel {float(diff):.3f}")
     if a.eval or a.trace:
         steps = record[:, 0].cpu()
         assert float(steps.min()) == float(steps.max()) == a.rollouts * trainer.T, (float(steps.min()), float(steps.max()))
