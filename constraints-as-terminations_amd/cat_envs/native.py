@@ -175,6 +175,26 @@ class ServoSimObs(ServoSimRewards):
     _fields_ = [("obs", ServoObs)]
 
 
+SERVO_EXT_EVENTS = 0x45565431           # CATPPO_SERVO_EXT_EVENTS: ``reserved`` of a descriptor followed by ServoObs and ServoEvents
+SERVO_EVENT_FLOATS = 32                 # CATPPO_SERVO_EVENT_FLOATS: words of the device-resident event block
+SERVO_EVENT_PUSH, SERVO_EVENT_JOINT_SCALE, SERVO_EVENT_JOINT_OFFSET, SERVO_EVENT_ROOT, SERVO_EVENT_FRICTION = 1, 2, 4, 8, 16
+#: word offsets of the event block (include/catppo.h, "Events"); every range is a (lo, width) pair
+SERVO_EVENT_WORDS = {"flags": 0, "p": 1, "num_buckets": 2, "push": 4, "joint_pos": 14, "joint_vel": 16, "root_pos": 18,
+                     "root_vel": 22, "friction": 28}
+SERVO_TRACE_PUSHED = 14                 # float of a trace row: 1.f in a step whose env was pushed (events on)
+
+
+class ServoEvents(C.Structure):
+    """catppo_servo_events: the event descriptor; ``block`` is a device array of ``SERVO_EVENT_FLOATS`` fp32 words"""
+    _fields_ = [("block", C.c_void_p), ("floats", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ServoSimEvents(ServoSimObs):
+    """catppo_servo_sim_events: catppo_servo_sim, a ``ServoObs`` (width 0 and a NULL table: no observation table) and a
+    ``ServoEvents`` behind it; the library reads both while ``reserved`` is ``SERVO_EXT_EVENTS``"""
+    _fields_ = [("ev", ServoEvents)]
+
+
 F32, F16, F64 = 0, 1, 2                 # CATPPO_F32 / _F16 / _F64
 SUM, MAX = 0, 1                         # CATPPO_SUM / _MAX
 LR_FIXED, LR_LINEAR, LR_KEEP = 0, 1, 2
@@ -779,6 +799,8 @@ class Native:
             raise TypeError("servo_sim_step takes a native.ServoSimRewards (the whole catppo_servo_sim)")
         if desc.reserved and not isinstance(desc, ServoSimObs):   # the library would read a catppo_servo_obs behind it
             raise TypeError("servo_sim_step: a descriptor whose 'reserved' announces observations must be a native.ServoSimObs")
+        if desc.reserved == SERVO_EXT_EVENTS and not isinstance(desc, ServoSimEvents):   # ... and a catppo_servo_events
+            raise TypeError("servo_sim_step: a descriptor whose 'reserved' announces events must be a native.ServoSimEvents")
         rc = self.lib.catppo_servo_sim_step(self.h, C.byref(desc), self._stream())
         if rc:
             self._ok(rc)

@@ -13,6 +13,7 @@ try:  # pragma: no cover
     from isaaclab.managers.manager_term_cfg import CurriculumTermCfg, ManagerTermBaseCfg  # type: ignore
     from isaaclab.managers.manager_term_cfg import RewardTermCfg  # type: ignore
     from isaaclab.managers.manager_term_cfg import ObservationGroupCfg, ObservationTermCfg  # type: ignore
+    from isaaclab.managers.manager_term_cfg import EventTermCfg  # type: ignore
     from isaaclab.utils.noise import AdditiveUniformNoiseCfg  # type: ignore
     HAVE_ISAACLAB = True
 except Exception:
@@ -38,6 +39,13 @@ except Exception:
         noise: Any = None
         clip: Any = None              # (lo, hi) or None
         scale: Any = None             # a number, one per element, or None
+
+    @configclass
+    class EventTermCfg(ManagerTermBaseCfg):
+        """IsaacLab's EventTerm: ``mode`` is "startup", "reset" or "interval" (the latter with ``interval_range_s``)"""
+        mode: str = MISSING
+        interval_range_s: Any = None
+        is_global_time: bool = False
 
     @configclass
     class ObservationGroupCfg:

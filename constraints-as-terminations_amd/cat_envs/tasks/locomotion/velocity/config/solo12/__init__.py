@@ -68,3 +68,19 @@ register(
     disable_env_checker=True,
     kwargs={"env_cfg_entry_point": f"{__name__}.cat_flat_env_cfg:Solo12ServoObsFlatEnvCfg_PLAY", **_KW},
 )
+
+# the servo task with an EventCfg: pushes, reset ranges and traction inside the simulator's launch (DESIGN section 9,
+# "Events"); "Full" is rewards, observations and events together.  The play cfgs run with pushes off
+for _name, _cfg in (("Events", "Solo12ServoEventsFlatEnvCfg"), ("Full", "Solo12ServoFullFlatEnvCfg")):
+    register(
+        id=f"Isaac-Velocity-CaT-Flat-Solo12-Servo-{_name}-v0",
+        entry_point=CaTEnv,
+        disable_env_checker=True,
+        kwargs={"env_cfg_entry_point": f"{__name__}.cat_flat_env_cfg:{_cfg}", **_KW},
+    )
+    register(
+        id=f"Isaac-Velocity-CaT-Flat-Solo12-Servo-{_name}-Play-v0",
+        entry_point=CaTEnv,
+        disable_env_checker=True,
+        kwargs={"env_cfg_entry_point": f"{__name__}.cat_flat_env_cfg:{_cfg}_PLAY", **_KW},
+    )

@@ -9,19 +9,22 @@ a pre-generated stream; on the servo surrogate ``RewardsCfg`` (the reference's t
 or any other block of ``mdp.rewards`` terms is evaluated inside the simulator's launch
 (``Solo12ServoRewardsFlatEnvCfg``, DESIGN section 9 "Rewards").  Observations: likewise, ``ObservationsCfg``
 (the reference's six terms, order, scales and noise ranges) is evaluated inside the servo simulator's launch
-(``Solo12ServoObsFlatEnvCfg``, DESIGN section 9 "Observations").
+(``Solo12ServoObsFlatEnvCfg``, DESIGN section 9 "Observations").  Events: ``EventCfg`` (the reference's four terms and
+values) likewise (``Solo12ServoEventsFlatEnvCfg``, DESIGN section 9 "Events"); ``Solo12ServoFullFlatEnvCfg`` puts the three
+blocks together.
 """
 import math
 
 from cat_envs.shim import AdditiveUniformNoiseCfg as Unoise
 from cat_envs.shim import CurriculumTermCfg as CurrTerm
+from cat_envs.shim import EventTermCfg as EventTerm
 from cat_envs.shim import ObservationGroupCfg as ObsGroup
 from cat_envs.shim import ObservationTermCfg as ObsTerm
 from cat_envs.shim import RewardTermCfg as RewTerm
 from cat_envs.shim import SceneEntityCfg, configclass
 from cat_envs.tasks.utils.cat import constraints, curriculums
 from cat_envs.tasks.utils.cat.manager_constraint_cfg import ConstraintTermCfg as ConstraintTerm
-from cat_envs.tasks.utils.mdp import observations, rewards
+from cat_envs.tasks.utils.mdp import events, observations, rewards
 
 ALL_JOINTS = [".*_HAA", ".*_HFE", ".*_KFE"]
 
@@ -281,6 +284,57 @@ class Solo12ServoObsFlatEnvCfg(Solo12ServoFlatEnvCfg):
 class Solo12ServoObsFlatEnvCfg_PLAY(Solo12ServoObsFlatEnvCfg):
     scene: SceneCfg = SceneCfg(num_envs=50, env_spacing=3.0)
     curriculum: object = None
+
+    def __post_init__(self):
+        self.observations.policy.enable_corruption = False
+
+
+@configclass
+class EventCfg:
+    """the reference's event block (solo12/cat_flat_env_cfg.py EventCfg): traction at start-up, two reset terms, the push"""
+    physics_material = EventTerm(func=events.randomize_rigid_body_material, mode="startup",
+                                 params={"asset_cfg": SceneEntityCfg("robot", body_names=".*"),
+                                         "static_friction_range": (0.5, 1.25), "dynamic_friction_range": (0.5, 1.25),
+                                         "restitution_range": (0.0, 0.0), "num_buckets": 100})
+    reset_base = EventTerm(func=events.reset_root_state_uniform, mode="reset",
+                           params={"pose_range": {"x": (-0.05, 0.05), "y": (-0.05, 0.05), "yaw": (-1.57, 1.57)},
+                                   "velocity_range": {"x": (-0.0, 0.0), "y": (-0.0, 0.0), "z": (-0.0, 0.0),
+                                                      "roll": (-0.0, 0.0), "pitch": (-0.0, 0.0), "yaw": (-0.0, 0.0)}})
+    reset_robot_joints = EventTerm(func=events.reset_joints_by_scale, mode="reset",
+                                   params={"position_range": (0.95, 1.05), "velocity_range": (-0.05, 0.05)})
+    # every step, each env with probability physics_dt / (2 * max_episode_length_s)
+    push_robot = EventTerm(func=events.push_by_setting_velocity_with_random_envs, mode="interval", is_global_time=True,
+                           interval_range_s=(0.0, 0.005),
+                           params={"velocity_range": {"x": (-0.5, 0.5), "y": (-0.5, 0.5)}})
+
+
+@configclass
+class Solo12ServoEventsFlatEnvCfg(Solo12ServoFlatEnvCfg):
+    """the servo task with a configurable event block: the simulator's launch evaluates ``events`` term by term"""
+    events: EventCfg = EventCfg()
+
+
+@configclass
+class Solo12ServoEventsFlatEnvCfg_PLAY(Solo12ServoEventsFlatEnvCfg):
+    """reset and startup terms stay (they define the task); the env runs with pushes off (``event_manager``)"""
+    scene: SceneCfg = SceneCfg(num_envs=50, env_spacing=3.0)
+    curriculum: object = None
+    pushes: bool = False
+
+
+@configclass
+class Solo12ServoFullFlatEnvCfg(Solo12ServoFlatEnvCfg):
+    """rewards, observations and events together: the reference's whole MDP block on the surrogate"""
+    rewards: RewardsCfg = RewardsCfg()
+    observations: ObservationsCfg = ObservationsCfg()
+    events: EventCfg = EventCfg()
+
+
+@configclass
+class Solo12ServoFullFlatEnvCfg_PLAY(Solo12ServoFullFlatEnvCfg):
+    scene: SceneCfg = SceneCfg(num_envs=50, env_spacing=3.0)
+    curriculum: object = None
+    pushes: bool = False
 
     def __post_init__(self):
         self.observations.policy.enable_corruption = False

@@ -184,9 +184,10 @@ class Solo12ServoSim(SyntheticSolo12Sim):
 
     def __init__(self, num_envs: int, obs_dim: int, device, seed: int, syn, dt: float, decimation: int,
                  max_episode_length: int, episode_length: torch.Tensor, reset: torch.Tensor, env_offset: int = 0,
-                 policy_obs_dim: int = 0):
+                 policy_obs_dim: int = 0, events: bool = False):
         """``policy_obs_dim`` = P > 0: the row gets a second observation field ``policy_obs`` of P floats (padded to a
-        multiple of 4) that ``set_observation_table`` configures; the raw field ``obs`` stays what it is"""
+        multiple of 4) that ``set_observation_table`` configures; the raw field ``obs`` stays what it is.
+        ``events``: the descriptor carries the event descriptor, too, and ``set_event_block`` configures it"""
         self.N, self.D, self.device = num_envs, obs_dim, torch.device(device)
         self.P = int(policy_obs_dim)
         if self.P and not (1 <= self.P <= native.SERVO_OBS_MAX_WIDTH and obs_dim == native.SERVO_OBS_RAW):
@@ -213,7 +214,7 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         self._episode_length, self._reset = episode_length, reset       # referenced by the descriptor: keep alive
         self._nat = native.get(self.device)
         # with a policy observation the descriptor carries the observation descriptor behind its 368 bytes
-        d = self._desc = native.ServoSimObs() if self.P else native.ServoSimRewards()
+        d = self._desc = native.ServoSimEvents() if events else native.ServoSimObs() if self.P else native.ServoSimRewards()
         d.N, d.env_offset, d.row_stride, d.row_floats = num_envs, int(env_offset), self.F, self.F
         d.obs_dim, d.H, d.B = obs_dim, H, B
         names = {"projected_gravity": "projected_gravity_b", "root_pos": "root_pos_w"}
@@ -232,6 +233,8 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         self._reward_entries = []
         self._obs_table = None                                          # device table of the observation descriptor
         self._obs_entries = []
+        self._events = bool(events)
+        self._event_block, self._event_words = None, None               # device block of the event descriptor, its host copy
         self._build_scene()
 
     def _table(self, t, width, what, lead=()):
@@ -351,9 +354,58 @@ class Solo12ServoSim(SyntheticSolo12Sim):
             self._obs_table = torch.zeros(C.sizeof(host), dtype=torch.uint8, device=self.device)
             d = self._desc
             d.obs.width, d.obs.off_policy_obs, d.obs.table = self.P, self.off["policy_obs"][0], self._obs_table.data_ptr()
-            d.reserved = native.SERVO_EXT_OBS                           # from now on every launch fills the field
+            # from now on every launch fills the field
+            d.reserved = native.SERVO_EXT_EVENTS if self._event_block is not None else native.SERVO_EXT_OBS
         self._obs_table.copy_(torch.frombuffer(bytearray(host), dtype=torch.uint8))
         self._obs_entries = entries
+
+    def set_event_block(self, words):
+        """``words``: the ``native.SERVO_EVENT_FLOATS`` fp32 words of the event block (``mdp.event_manager.pack``; words 0
+        and 2 hold the flags and the bucket count as integers).  Every following launch, init launches included, applies
+        the events the flags name.  The block lives on the device and is rewritten here and nowhere else, in stream order:
+        a new flag word is in the next launch (when nothing but word 0 changed, that word alone is copied).  The values are
+        checked here - the library cannot read them."""
+        import numpy as np
+        if not self._events:
+            raise ValueError("this simulator was built without an event descriptor (events = False)")
+        words = np.ascontiguousarray(words, np.float32)
+        if words.shape != (native.SERVO_EVENT_FLOATS,):
+            raise ValueError(f"the event block has {native.SERVO_EVENT_FLOATS} words, got shape {words.shape}")
+        W = native.SERVO_EVENT_WORDS
+        ints = words.view(np.int32)
+        flags, buckets = int(ints[W["flags"]]), int(ints[W["num_buckets"]])
+        both = native.SERVO_EVENT_JOINT_SCALE | native.SERVO_EVENT_JOINT_OFFSET
+        if flags & ~31 or flags & both == both:
+            raise ValueError(f"event block: flags {flags:#x} (known bits 1 .. 16; at most one joint-reset mode)")
+        if buckets < 1:
+            raise ValueError(f"event block: num_buckets must be >= 1, got {buckets}")
+        vals = np.delete(words, [W["flags"], W["num_buckets"]])
+        if not np.isfinite(vals).all():
+            raise ValueError("event block: every range and the probability must be finite")
+        if not 0.0 <= float(words[W["p"]]) <= 1.0:
+            raise ValueError(f"event block: the push probability must be in [0, 1], got {float(words[W['p']])}")
+        if (words[5:30:2] < 0).any() or words[[3, 30, 31]].any():
+            raise ValueError("event block: every width must be >= 0 and the spare words zero")
+        if flags & native.SERVO_EVENT_FRICTION and float(words[W["friction"]]) < 0.0:
+            raise ValueError("event block: the friction range must be >= 0")
+        if int(self._desc.max_episode_length) >= 2 ** 27:
+            raise ValueError("events need max_episode_length < 2^27: the step index is part of a Philox counter word")
+        if self._event_block is None:
+            self._event_block = torch.zeros(native.SERVO_EVENT_FLOATS, dtype=torch.float32, device=self.device)
+            d = self._desc
+            d.ev.block, d.ev.floats, d.ev.reserved = self._event_block.data_ptr(), native.SERVO_EVENT_FLOATS, 0
+            d.reserved = native.SERVO_EXT_EVENTS                        # from now on every launch reads the block
+        old = self._event_words
+        if old is not None and (old.view(np.int32)[1:] == ints[1:]).all():
+            self._event_block[:1].copy_(torch.from_numpy(words[:1].copy()))
+        else:
+            self._event_block.copy_(torch.from_numpy(words.copy()))
+        self._event_words = words.copy()
+
+    @property
+    def event_words(self):
+        """the host copy of the event block as last written (fp32 [32]) or None"""
+        return None if self._event_words is None else self._event_words.copy()
 
     def reset(self):
         """the first state of episode 0 in the state buffer"""
@@ -502,6 +554,15 @@ class CaTEnv:
             from cat_envs.tasks.utils.mdp import observation_manager as OM
             self._obs_table = OM.build_table(OM.policy_group(cfg.observations), SOLO12_JOINTS, DEFAULT_JOINT_POS)
             self._obs_field, self.obs_dim = "policy_obs", len(self._obs_table[0])
+        # cfg.events: pushes, reset ranges and traction are evaluated inside the simulator's launch, too (DESIGN section 9,
+        # "Events"); the block is built before the simulator because an error in the cfg should cost no device memory
+        self._event_block = None
+        if getattr(cfg, "events", None) is not None:
+            if kind != "servo":
+                raise TypeError("cfg.events needs the closed-loop simulator (SyntheticCfg.kind = 'servo'): the events are "
+                                "evaluated inside its launch; the stream simulator is a pre-generated stream")
+            from cat_envs.tasks.utils.mdp import event_manager as EM
+            self._event_block = EM.build_block(cfg.events, cfg.sim.dt, cfg.episode_length_s)
         if kind == "stream":
             self.sim = SyntheticSolo12Sim(self.num_envs, self.obs_dim, self.device, seed + int(syn.seed_offset),
                                           int(syn.stream_steps))
@@ -527,7 +588,8 @@ class CaTEnv:
             self.sim = Solo12ServoSim(self.num_envs, int(syn.obs_dim), self.device, seed + int(syn.seed_offset), syn,
                                       cfg.sim.dt, cfg.decimation, self.max_episode_length, self.episode_length_buf,
                                       self.reset_buf, env_offset=int(getattr(cfg.scene, "env_offset", 0) or 0),
-                                      policy_obs_dim=self.obs_dim if self._obs_table is not None else 0)
+                                      policy_obs_dim=self.obs_dim if self._obs_table is not None else 0,
+                                      events=self._event_block is not None)
             self.scene = self.sim.scene
         self.obs_buf = {"policy": self.sim.view(self._obs_field)}
         self._rstep = None
@@ -567,6 +629,12 @@ class CaTEnv:
             from cat_envs.tasks.utils.mdp.observation_manager import ObservationManager
             self.observation_manager = ObservationManager(self.cfg.observations, self, *self._obs_table)
             print("[INFO] Observation Manager: ", self.observation_manager)
+        if self._event_block is not None:
+            from cat_envs.tasks.utils.mdp.event_manager import EventManager
+            # cfg.pushes = False (the play cfgs): reset and startup terms as configured, interval events off
+            self.event_manager = EventManager(self.cfg.events, self, self._event_block,
+                                              interval_enabled=bool(getattr(self.cfg, "pushes", True)))
+            print("[INFO] Event Manager: ", self.event_manager)
 
     # evaluation ------------------------------------------------------------------------------
     def _servo_sim(self) -> Solo12ServoSim:
@@ -589,6 +657,12 @@ class CaTEnv:
         if not hasattr(self, "observation_manager"):
             raise TypeError("observation corruption needs cfg.observations")
         self.observation_manager.set_corruption(on)
+
+    def set_pushes(self, on: bool):
+        """interval events (the pushes) on or off from the next step on (needs cfg.events)"""
+        if not hasattr(self, "event_manager"):
+            raise TypeError("pushes need cfg.events")
+        self.event_manager.set_interval_enabled(on)
 
     def set_eval_record(self, record: torch.Tensor | None):
         """attach (or, with None, detach) the simulator's per-env evaluation record [N, 12]"""
@@ -635,6 +709,8 @@ class CaTEnv:
             fp["reward_terms"] = self.reward_manager.fingerprint()
         if hasattr(self, "observation_manager"):     # likewise
             fp["observation_terms"] = self.observation_manager.fingerprint()
+        if hasattr(self, "event_manager"):           # likewise
+            fp["event_terms"] = self.event_manager.fingerprint()
         return fp
 
     def state_dict(self) -> dict:
@@ -650,6 +726,8 @@ class CaTEnv:
             sd["rewards"] = self.reward_manager.state_dict()
         if hasattr(self, "observation_manager"):     # the policy field is part of the simulator's ``cur``; the switch is not
             sd["observations"] = self.observation_manager.state_dict()
+        if hasattr(self, "event_manager"):           # the draws are stateless; the interval switch is the state
+            sd["events"] = self.event_manager.state_dict()
         return sd
 
     def check_state_dict(self, sd: dict):
@@ -665,6 +743,10 @@ class CaTEnv:
             keys.append("observations")
         elif "observations" in sd:
             raise ValueError("run state: it carries observation terms, this env has no cfg.observations")
+        if hasattr(self, "event_manager"):
+            keys.append("events")
+        elif "events" in sd:
+            raise ValueError("run state: it carries events, this env has no cfg.events")
         missing = [k for k in keys if k not in sd]
         if missing:
             raise ValueError(f"run state: the env's part lacks {missing}")
@@ -684,6 +766,8 @@ class CaTEnv:
             self.reward_manager.check_state_dict(sd["rewards"])
         if hasattr(self, "observation_manager"):
             self.observation_manager.check_state_dict(sd["observations"])
+        if hasattr(self, "event_manager"):
+            self.event_manager.check_state_dict(sd["events"])
 
     def load_state_dict(self, sd: dict):
         """IN PLACE (``copy_`` into the existing tensors, never a rebound attribute): the fused step's argument block, the
@@ -701,6 +785,8 @@ class CaTEnv:
             self.reward_manager.load_state_dict(sd["rewards"])
         if hasattr(self, "observation_manager"):
             self.observation_manager.load_state_dict(sd["observations"])
+        if hasattr(self, "event_manager"):
+            self.event_manager.load_state_dict(sd["events"])
         self.curriculum_manager.load_state_dict(sd["curriculum"])      # through set_term_cfg: the next launch carries it
 
     # episode control -------------------------------------------------------------------------

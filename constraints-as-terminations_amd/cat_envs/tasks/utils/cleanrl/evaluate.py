@@ -22,6 +22,7 @@ import numpy as np
 from cat_envs.native import SERVO_EVAL_FIELDS as FIELDS
 from cat_envs.native import SERVO_TRACE_FIELDS as TRACE_FIELDS
 from cat_envs.native import SERVO_TRACE_FLOATS as TRACE_FLOATS
+from cat_envs.native import SERVO_TRACE_PUSHED as TRACE_PUSHED
 
 #: the ranges the servo simulator draws its commands from (csrc/servo_sim.hip, command_of): vx, vy, wz
 COMMAND_RANGES = ((-0.3, 1.0), (-0.7, 0.7), (-0.78, 0.78))
@@ -124,6 +125,47 @@ def summarise_step_response(responses) -> dict:
     return summary
 
 
+def push_recovery(trace, tol: float = 0.1) -> list:
+    """How the traced envs take their pushes, from a trace ``[T, K, 72]`` taken with events on (float 14 of a row is 1 in a
+    step whose env was pushed).  Pure numpy, fp64, like ``step_response``.  One dict per (env, pushed step), in env then
+    step order.  The window of a push starts at the pushed step and ends with its episode (the row whose ``ends`` is set,
+    inclusive), with the trace, or before the env's next push, whichever comes first.
+    ``recover_steps``: the smallest k >= 0 such that ``|v - command| <= tol`` on all three axes in every step from window
+    step k to the window's end; None if there is none.  ``peak_error``: the largest ``|v - command|`` over axes and window.
+    ``fell``: the episode ended in a fall inside the window at or before the step recovery would have needed, i.e. the
+    window's last row has ``fallen`` set and the env had not recovered before it."""
+    tr = np.asarray(trace, np.float64)
+    if tr.ndim != 3 or tr.shape[2] != TRACE_FLOATS:
+        raise ValueError(f"push_recovery wants a trace [T, K, {TRACE_FLOATS}], got {tr.shape}")
+    steps, envs = tr.shape[:2]
+    out = []
+    for e in range(envs):
+        pushed = np.nonzero(tr[:, e, TRACE_PUSHED] > 0.5)[0]
+        for s in pushed:
+            later = pushed[pushed > s]
+            end = int(later[0]) if len(later) else steps                  # exclusive
+            done = np.nonzero(tr[s:end, e, 1] > 0.5)[0]
+            if len(done):
+                end = s + int(done[0]) + 1
+            err = np.abs(tr[s:end, e, 7:10] - tr[s:end, e, 4:7])
+            ok = (err <= tol).all(1)
+            bad = np.nonzero(~ok)[0]
+            k = 0 if not len(bad) else int(bad[-1]) + 1
+            recover = k if k < len(ok) else None
+            fell = bool(tr[end - 1, e, 2] > 0.5) and (recover is None)
+            out.append({"env": int(e), "step": int(s), "t": int(tr[s, e, 0]), "window": int(end - s),
+                        "recover_steps": recover, "peak_error": float(err.max()), "fell": fell})
+    return out
+
+
+def summarise_push_recovery(rows) -> dict:
+    """counts and medians over ``push_recovery``'s rows; JSON-serialisable"""
+    rec = [r["recover_steps"] for r in rows if r["recover_steps"] is not None]
+    return {"pushes": len(rows), "recovered": len(rec), "fell": sum(1 for r in rows if r["fell"]),
+            "recover_steps_median": float(np.median(rec)) if rec else None,
+            "peak_error_median": float(np.median([r["peak_error"] for r in rows])) if rows else None}
+
+
 def aggregate(record, cat_reward=None, termination_prob=None, violations=None, term_names=()) -> dict:
     """metrics of a set of envs, in fp64, from their per-env tables: ``record`` [n, 12] (``FIELDS``), the per-env sums of
     the CaT-scaled reward and of the termination probability [n], and the per-env counts of steps with a violated
@@ -170,6 +212,13 @@ class EvalResult:
     trace: np.ndarray | None = None               # [steps, K, 72] fp32: the simulator's step trace of envs 0 .. K - 1
     trace_fields: tuple = TRACE_FIELDS
     segment_steps: int | None = None              # control steps per segment when ``commands`` is a schedule
+    pushes: bool = False                          # the env has cfg.events and ran with its interval events on
+
+    def push_recovery(self, tolerance: float = 0.1) -> list:
+        """``push_recovery`` of this evaluation's trace (needs a trace)"""
+        if self.trace is None:
+            raise ValueError("push recovery needs a trace (trace_envs > 0)")
+        return push_recovery(self.trace, tolerance)
 
     def step_response(self, tolerance: float = 0.1) -> list:
         """``step_response`` of this evaluation's trace (needs a schedule and a trace)"""
@@ -204,12 +253,15 @@ class EvalResult:
             responses = self.step_response()
             d["segment_steps"] = int(self.segment_steps)
             d["step_response"] = {"summary": summarise_step_response(responses), "responses": responses}
+        if self.trace is not None and self.pushes:
+            rows = self.push_recovery()
+            d["push_recovery"] = {"summary": summarise_push_recovery(rows), "pushes": rows}
         return json.dumps(d)
 
 
 def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool = True,
                     fresh_cat_state: bool = False, segment_steps: int | None = None, trace_envs: int = 0,
-                    corruption: bool | None = None) -> EvalResult:
+                    corruption: bool | None = None, pushes: bool | None = None) -> EvalResult:
     """Roll ``policy`` out for ``steps`` control steps from a fresh reset and measure it.
 
     ``policy`` is an ``Agent`` - its observations are normalised by the frozen ``obs_rms`` and the action is the mean
@@ -233,7 +285,10 @@ def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool 
 
     ``corruption`` (envs with ``cfg.observations``): None leaves the env's observation-noise switch as it is; a bool sets it
     for the evaluation and puts it back afterwards, also when the roll-out raises.  The record and the trace read state,
-    not observations: the noise reaches them only through the actions the policy takes on what it sees."""
+    not observations: the noise reaches them only through the actions the policy takes on what it sees.
+
+    ``pushes`` (envs with ``cfg.events``): None leaves the env's interval-event switch as it is; a bool sets it for the
+    evaluation and puts it back afterwards, also when the roll-out raises.  Reset and startup terms stay as configured."""
     import contextlib
     import torch
     from cat_envs.tasks.utils.cleanrl.ppo import Agent
@@ -286,6 +341,13 @@ def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool 
         u.set_eval_record(None)
         raise TypeError("evaluate_policy(corruption=...) needs an env with cfg.observations")
     corruption_before = None if om is None else om.corruption
+    em = getattr(u, "event_manager", None)
+    if pushes is not None and em is None:
+        u.set_eval_record(None)
+        raise TypeError("evaluate_policy(pushes=...) needs an env with cfg.events")
+    pushes_before = None if em is None else em.interval_enabled
+    pushes_on = bool(em is not None and (pushes_before if pushes is None else pushes)
+                     and em.block["flags"] & 1)        # the env has a push term and it is on for this evaluation
     frozen = contextlib.ExitStack()
     if fresh_cat_state:
         u.fresh_cat_state()
@@ -293,6 +355,8 @@ def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool 
     try:
         if corruption is not None:
             om.set_corruption(corruption)
+        if pushes is not None:
+            em.set_interval_enabled(pushes)
         if lead:
             u.set_fixed_commands(table, segment_steps)
         else:
@@ -323,9 +387,11 @@ def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool 
         u.set_fixed_commands(None)
         if corruption is not None:
             om.set_corruption(corruption_before)
+        if pushes is not None:
+            em.set_interval_enabled(pushes_before)
     res = EvalResult(per_env=record.cpu().numpy(), commands=None if table is None else table.cpu().numpy(),
                      cat_reward=cat_reward.cpu().numpy(), termination_prob=term_prob.cpu().numpy(),
                      violations=viol.cpu().numpy(), term_names=names, trace=None if trace is None else trace.cpu().numpy(),
-                     segment_steps=segment_steps if lead else None)
+                     segment_steps=segment_steps if lead else None, pushes=pushes_on)
     res.metrics = res._aggregate()
     return res

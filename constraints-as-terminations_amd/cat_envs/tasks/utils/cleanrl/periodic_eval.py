@@ -253,6 +253,8 @@ def make_eval_env_cfg(env_cfg, eval_envs: int):
             group["enable_corruption"] = False
         else:
             group.enable_corruption = False
+    if getattr(cfg, "events", None) is not None:  # ... and without pushes, randomised first states or traction, likewise
+        cfg.events = None
     return cfg
 
 

@@ -1,0 +1,179 @@
+"""Event manager of the servo task ("Events").
+
+IsaacLab's ``EventManager`` calls torch functions at start-up, at every reset and on interval timers.  This one calls
+none: it turns an ``EventCfg`` into the 32-word block the simulator's kernel reads inside its own launch
+(``Solo12ServoSim.set_event_block``; include/catppo.h, catppo_servo_events).  Every draw is stateless (Philox keyed on
+seed, global env id, episode and step), so there is nothing to reset and nothing to save but the interval switch.
+``set_interval_enabled`` rewrites the flag word on the device, in stream order: the next launch - a replayed graph's,
+too - reads it.  Reset and startup terms stay on: they define the task.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from cat_envs import native
+from cat_envs.shim import EventTermCfg
+
+W = native.SERVO_EVENT_WORDS
+FLAG = {"push": native.SERVO_EVENT_PUSH, "joint_scale": native.SERVO_EVENT_JOINT_SCALE,
+        "joint_offset": native.SERVO_EVENT_JOINT_OFFSET, "root": native.SERVO_EVENT_ROOT,
+        "friction": native.SERVO_EVENT_FRICTION}
+MODES = ("startup", "reset", "interval")
+#: kind -> what a second term collides with: at most one term per slot
+_SLOT = {"push": "push", "joint_scale": "joint reset", "joint_offset": "joint reset", "root": "root reset", "friction": "material"}
+
+
+def _f32(x) -> float:
+    return float(np.float32(x))
+
+
+def lo_width(a, b):
+    """a uniform sample from (a, b) is ``lo + u * width``: lo = f32(a), width = f32(b - a)"""
+    return _f32(a), _f32(float(b) - float(a))
+
+
+def term_items(cfg):
+    items = cfg.items() if isinstance(cfg, dict) else cfg.__dict__.items()
+    return [(n, t) for n, t in items if t is not None]
+
+
+def build_block(cfg, sim_dt, max_episode_length_s):
+    """an ``EventCfg`` -> ``{"flags", "p", "num_buckets", "ranges": {group: [(lo, width), ...]}, "terms": {mode: [names]},
+    "kinds": {name: kind}, "inert": [...]}``; pure, needs no device, every float already rounded to fp32.  Errors name
+    the term: a func without ``describe`` or an unknown mode, an interval term other than the push, a term configured with
+    another mode than its own, a second term of a kind."""
+    block = {"flags": 0, "p": 0.0, "num_buckets": 1,
+             "ranges": {"push": [(0.0, 0.0)] * 5, "joint_pos": [(0.0, 0.0)], "joint_vel": [(0.0, 0.0)],
+                        "root_pos": [(0.0, 0.0)] * 2, "root_vel": [(0.0, 0.0)] * 3, "friction": [(0.0, 0.0)]},
+             "terms": {m: [] for m in MODES}, "kinds": {}, "inert": []}
+    taken = {}
+    for name, term in term_items(cfg):
+        if not isinstance(term, EventTermCfg):
+            raise TypeError(f"Configuration for event term '{name}' is not EventTermCfg. Received: '{type(term)}'.")
+        describe = getattr(term.func, "describe", None)
+        if describe is None:
+            raise ValueError(f"event term '{name}': {getattr(term.func, '__name__', term.func)!r} has no describe(); the servo "
+                             f"task evaluates events inside the simulator launch and runs no Python event function")
+        if term.mode not in MODES:
+            raise ValueError(f"event term '{name}': unknown mode {term.mode!r} (known: {list(MODES)})")
+        spec = describe(name, sim_dt, max_episode_length_s, **(term.params or {}))
+        kind = spec["kind"]
+        if term.mode == "interval" and kind != "push":
+            raise ValueError(f"event term '{name}': the only interval event the simulator evaluates is "
+                             f"push_by_setting_velocity_with_random_envs (interval events with per-env timers are out of scope)")
+        if term.mode != spec["mode"]:
+            raise ValueError(f"event term '{name}': {term.func.__name__} is a {spec['mode']!r} event, configured as {term.mode!r}")
+        slot = _SLOT[kind]
+        if slot in taken:
+            raise ValueError(f"event term '{name}': a second {slot} term (the first is '{taken[slot]}'); at most one is evaluated")
+        taken[slot] = name
+        block["flags"] |= FLAG[kind]
+        pairs = [lo_width(a, b) for a, b in spec["ranges"]]
+        r = block["ranges"]
+        if kind == "push":
+            block["p"], r["push"] = _f32(spec["p"]), pairs
+        elif kind in ("joint_scale", "joint_offset"):
+            r["joint_pos"], r["joint_vel"] = [pairs[0]], [pairs[1]]
+        elif kind == "root":
+            r["root_pos"], r["root_vel"] = pairs[:2], pairs[2:]
+        else:
+            r["friction"], block["num_buckets"] = pairs, int(spec["num_buckets"])
+        block["terms"][term.mode].append(name)
+        block["kinds"][name] = kind
+        block["inert"] += [f"{name}.{k}" for k in spec["inert"]]
+    if not block["kinds"]:
+        raise ValueError("the event cfg has no term: nothing to evaluate (leave cfg.events unset)")
+    return block
+
+
+def pack(block, interval_enabled: bool = True) -> np.ndarray:
+    """the block's ``native.SERVO_EVENT_FLOATS`` words as the device reads them (fp32 array; words 0 and 2 hold integers)"""
+    words = np.zeros(native.SERVO_EVENT_FLOATS, np.float32)
+    ints = words.view(np.int32)
+    flags = int(block["flags"])
+    if not interval_enabled:
+        flags &= ~native.SERVO_EVENT_PUSH
+    ints[W["flags"]], ints[W["num_buckets"]] = flags, int(block["num_buckets"])
+    words[W["p"]] = block["p"]
+    for group, pairs in block["ranges"].items():
+        for i, (lo, width) in enumerate(pairs):
+            words[W[group] + 2 * i], words[W[group] + 2 * i + 1] = lo, width
+    return words
+
+
+class EventManager:
+    def __init__(self, cfg: object, env, block=None, interval_enabled: bool = True):
+        self.cfg, self._env = cfg, env
+        self._block = block if block is not None else build_block(cfg, env.cfg.sim.dt, env.max_episode_length_s)
+        self._interval = bool(interval_enabled)
+        self._push()
+
+    def _push(self):
+        self._env.sim.set_event_block(pack(self._block, self._interval))
+
+    # ------------------------------------------------------------------ IsaacLab's names
+    @property
+    def active_terms(self) -> dict:
+        return {m: list(v) for m, v in self._block["terms"].items() if v}
+
+    @property
+    def available_modes(self) -> list:
+        return [m for m, v in self._block["terms"].items() if v]
+
+    @property
+    def inert(self) -> list:
+        """params that are accepted and have no effect on the surrogate (``term.param``)"""
+        return list(self._block["inert"])
+
+    @property
+    def block(self) -> dict:
+        return self._block
+
+    @property
+    def interval_enabled(self) -> bool:
+        return self._interval
+
+    def set_interval_enabled(self, on: bool):
+        """pushes on or off from the next launch on: one stream-ordered copy of the flag word; reset and startup terms stay"""
+        on = bool(on)
+        if on != self._interval:
+            self._interval = on
+            self._push()                       # only word 0 differs: the simulator copies that word alone
+
+    def apply(self, mode: str, env_ids=None, dt=None, global_env_step_count=None):
+        """launches nothing: the simulator's own launch evaluates every mode"""
+        if mode not in MODES:
+            raise ValueError(f"unknown event mode {mode!r}")
+
+    def reset(self, env_ids=None):
+        return {}
+
+    def __str__(self) -> str:
+        b = self._block
+        msg = f"<EventManager> contains {len(b['kinds'])} terms (pushes {'on' if self._interval else 'off'}).\n"
+        for mode, names in b["terms"].items():
+            for n in names:
+                extra = f" p = {b['p']:g}" if b["kinds"][n] == "push" else ""
+                msg += f"  {mode:<9s} {n:<22s} {b['kinds'][n]}{extra}\n"
+        if b["inert"]:
+            msg += f"  without effect on the surrogate: {', '.join(b['inert'])}\n"
+        return msg
+
+    # ------------------------------------------------------------------ run state
+    def fingerprint(self) -> list:
+        """names, kinds and every word of the block (pushes as configured): what a loaded state was made with"""
+        b = self._block
+        words = pack(b, True)
+        return [[n, b["kinds"][n]] for n in b["kinds"]] + [[int(w) for w in words.view(np.int32)]]
+
+    def state_dict(self) -> dict:
+        return {"interval": bool(self._interval)}
+
+    def check_state_dict(self, sd: dict):
+        if "interval" not in sd:
+            raise ValueError("run state: the events' part lacks 'interval'")
+
+    def load_state_dict(self, sd: dict):
+        self.check_state_dict(sd)
+        self._interval = bool(sd["interval"])
+        self._push()

@@ -1,0 +1,131 @@
+"""Event terms of the servo task (the reference's ``mdp/`` path; DESIGN section 9, "Events").
+
+The names and signatures are IsaacLab's ``isaaclab.envs.mdp.events`` and, for the push, the reference's own
+``mdp/events.py`` - PARITY UNPINNED: the rules are restated from their published form, IsaacLab is not installed next to
+this package and nothing here is compared with it.
+
+No term does anything in Python.  Each carries ``describe(name, sim_dt, max_episode_length_s, **params) -> dict``: its
+``kind`` (which words of the simulator's event block it fills), the mode it must be configured with, its ranges as
+``(a, b)`` pairs and the params it accepts without effect (``inert``).  The event manager turns that into the block the
+simulator's kernel reads inside its own launch (include/catppo.h, catppo_servo_events).  Calling a term directly raises
+``TypeError``; an event function without ``describe`` is an error of the manager, not a slow path.
+"""
+from __future__ import annotations
+
+import math
+
+AXES6 = ("x", "y", "z", "roll", "pitch", "yaw")
+ZERO = (0.0, 0.0)
+
+
+def _refuse(name):
+    raise TypeError(f"{name}: the servo task evaluates events inside the simulator launch; the term only describes itself "
+                    f"to the event manager (describe(...)) and is never called")
+
+
+def _pair(term, key, value):
+    try:
+        a, b = (float(v) for v in value)
+    except (TypeError, ValueError):
+        raise ValueError(f"event term '{term}': range '{key}' must be a pair (lo, hi), got {value!r}") from None
+    if not (math.isfinite(a) and math.isfinite(b)) or b < a:
+        raise ValueError(f"event term '{term}': range '{key}' must be finite with lo <= hi, got {value!r}")
+    return a, b
+
+
+def _axes(term, what, ranges, allowed, inert=()):
+    """the ranges of ``allowed`` axes out of an IsaacLab range dict (an absent key is (0, 0)); any other axis must be zero"""
+    ranges = dict(ranges or {})
+    unknown = [k for k in ranges if k not in AXES6]
+    if unknown:
+        raise ValueError(f"event term '{term}': {what} has unknown keys {unknown} (known: {list(AXES6)})")
+    out = {}
+    for k in AXES6:
+        a, b = _pair(term, f"{what}.{k}", ranges.get(k, ZERO))
+        if k in allowed:
+            out[k] = (a, b)
+        elif k not in inert and (a != 0.0 or b != 0.0):
+            raise ValueError(f"event term '{term}': {what}['{k}'] = {(a, b)} is not modelled by the servo surrogate "
+                             f"(only {list(allowed)} of {what} have an effect); it must be (0, 0)")
+    return out
+
+
+def _term(describe):
+    def wrap(func):
+        func.describe = describe
+        return func
+    return wrap
+
+
+def _describe_push(name, sim_dt, max_episode_length_s, velocity_range=None, asset_cfg=None, probability=None):
+    r = _axes(name, "velocity_range", velocity_range, ("x", "y", "yaw", "roll", "pitch"))
+    p = float(sim_dt) / (2.0 * float(max_episode_length_s)) if probability is None else float(probability)
+    if not (math.isfinite(p) and 0.0 <= p <= 1.0):
+        raise ValueError(f"event term '{name}': the push probability must be in [0, 1], got {p}")
+    return {"kind": "push", "mode": "interval", "p": p, "ranges": [r[k] for k in ("x", "y", "yaw", "roll", "pitch")], "inert": []}
+
+
+@_term(_describe_push)
+def push_by_setting_velocity_with_random_envs(env, env_ids, velocity_range, asset_cfg=None):
+    """every step, each env is pushed with probability ``physics_dt / (2 * max_episode_length_s)``: its planar and yaw
+    velocities are SET to samples of ``velocity_range`` (an absent key is (0, 0)), roll / pitch rates kick the tilt"""
+    _refuse("push_by_setting_velocity_with_random_envs")
+
+
+def _describe_joints(kind):
+    def describe(name, sim_dt, max_episode_length_s, position_range=None, velocity_range=None, asset_cfg=None):
+        if position_range is None or velocity_range is None:
+            raise ValueError(f"event term '{name}': position_range and velocity_range are required")
+        pos, vel = _pair(name, "position_range", position_range), _pair(name, "velocity_range", velocity_range)
+        # by scale the velocity is default_joint_vel * s, and the model's default joint velocity is zero: nothing is drawn
+        return {"kind": kind, "mode": "reset", "ranges": [pos, vel if kind == "joint_offset" else ZERO],
+                "inert": ["velocity_range"] if kind == "joint_scale" and vel != ZERO else []}
+    return describe
+
+
+@_term(_describe_joints("joint_scale"))
+def reset_joints_by_scale(env, env_ids, position_range, velocity_range, asset_cfg=None):
+    """first pose = default * U(position_range); first joint velocity = default (zero) * U(velocity_range)"""
+    _refuse("reset_joints_by_scale")
+
+
+@_term(_describe_joints("joint_offset"))
+def reset_joints_by_offset(env, env_ids, position_range, velocity_range, asset_cfg=None):
+    """first pose = default + U(position_range); first joint velocity = U(velocity_range)"""
+    _refuse("reset_joints_by_offset")
+
+
+def _describe_root(name, sim_dt, max_episode_length_s, pose_range=None, velocity_range=None, asset_cfg=None):
+    pose = _axes(name, "pose_range", pose_range, ("x", "y"), inert=("yaw",))
+    vel = _axes(name, "velocity_range", velocity_range, ("x", "y", "yaw"))
+    yaw = _pair(name, "pose_range.yaw", dict(pose_range or {}).get("yaw", ZERO))
+    return {"kind": "root", "mode": "reset", "ranges": [pose["x"], pose["y"], vel["x"], vel["y"], vel["yaw"]],
+            "inert": ["pose_range.yaw"] if yaw != ZERO else []}       # no heading in the model, flat ground is isotropic
+
+
+@_term(_describe_root)
+def reset_root_state_uniform(env, env_ids, pose_range, velocity_range, asset_cfg=None):
+    """first root position x y and first velocities vx vy wz from uniform ranges"""
+    _refuse("reset_root_state_uniform")
+
+
+def _describe_material(name, sim_dt, max_episode_length_s, static_friction_range=None, dynamic_friction_range=ZERO,
+                       restitution_range=ZERO, num_buckets=None, asset_cfg=None, make_consistent=False):
+    if static_friction_range is None or num_buckets is None:
+        raise ValueError(f"event term '{name}': static_friction_range and num_buckets are required")
+    if int(num_buckets) != num_buckets or int(num_buckets) < 1:
+        raise ValueError(f"event term '{name}': num_buckets must be an integer >= 1, got {num_buckets!r}")
+    mu = _pair(name, "static_friction_range", static_friction_range)
+    if mu[0] < 0.0:
+        raise ValueError(f"event term '{name}': static_friction_range must be >= 0, got {mu}")
+    inert = [k for k, v in (("dynamic_friction_range", dynamic_friction_range), ("restitution_range", restitution_range))
+             if _pair(name, k, v) is not None]
+    return {"kind": "friction", "mode": "startup", "ranges": [mu], "num_buckets": int(num_buckets), "inert": inert}
+
+
+@_term(_describe_material)
+def randomize_rigid_body_material(env, env_ids, static_friction_range, dynamic_friction_range, restitution_range, num_buckets,
+                                  asset_cfg=None, make_consistent=False):
+    """each env draws one of ``num_buckets`` shared materials once; its static friction against the ground's 1.0 is the
+    env's traction"""
+    _refuse("randomize_rigid_body_material")

@@ -8,6 +8,8 @@
 // whole base state redundantly (the joint sums are butterflies, all lanes end up with the same bits), so no lane waits
 // for another except through the shuffles.  The next row is assembled in LDS and leaves as coalesced 16-byte stores.
 //   tree16: x += xor-shuffle 8, 4, 2, 1 (width 16)     tree4 (feet): x += xor-shuffle 1, 2
+#include <type_traits>
+
 #include "common.h"
 #include "rng.h"
 
@@ -17,6 +19,8 @@ constexpr int kEnvsPerBlock = 16, kThreads = 256, kJoints = 12, kPrivate = 14;
 constexpr uint32_t kTagCommand = 0x434D4453u, kTagInit = 0x494E4954u;   // "CMDS", "INIT": fourth Philox counter word
 constexpr uint32_t kTagObs = 0x4F42534Eu;                                // "OBSN": the observation noise
 constexpr int kRawObs = 45;                                              // the raw observation a policy observation reads
+// "PUSH", "JVEL", "ROOT", "FRIC": the events ("Events")
+constexpr uint32_t kTagPush = 0x50555348u, kTagJvel = 0x4A56454Cu, kTagRoot = 0x524F4F54u, kTagFric = 0x46524943u;
 
 // G[k][lane]: the fixed 5 x 12 matrix of the base model (rows vx, vy, wz, roll, pitch)
 __device__ __forceinline__ float gain(int k, int lane) {
@@ -46,7 +50,12 @@ __device__ __forceinline__ float tree4(float x) {
   return x;
 }
 
-__device__ __forceinline__ const catppo_servo_obs& first_of(const catppo_servo_obs& o) { return o; }
+// the descriptor of type T in the kernel's pack of extensions
+template <typename T, typename U, typename... R>
+__device__ __forceinline__ const T& ext_of(const U& u, const R&... r) {
+  if constexpr (std::is_same_v<T, U>) return u;
+  else return ext_of<T>(r...);
+}
 
 __device__ __forceinline__ float pick(const rng::u32x4& r, int w) { return rng::uniform_open(w == 0 ? r.x : w == 1 ? r.y : w == 2 ? r.z : r.w); }
 
@@ -59,6 +68,9 @@ static_assert(sizeof(catppo_servo_reward_term) == 16 && CATPPO_SERVO_REWARD_FLOA
 static_assert(sizeof(catppo_servo_obs_entry) == 32 && CATPPO_SERVO_OBS_MAX_WIDTH == 64, "observation table entry: two 16-byte loads");
 static_assert(offsetof(catppo_servo_sim_obs, obs) == sizeof(catppo_servo_sim) && sizeof(catppo_servo_obs) == 16,
               "catppo_servo_sim_obs: the observation descriptor lies right behind the 368 bytes");
+static_assert(offsetof(catppo_servo_sim_events, obs) == 368 && offsetof(catppo_servo_sim_events, ev) == 384 &&
+                  sizeof(catppo_servo_events) == 16 && sizeof(catppo_servo_sim_events) == 400 && CATPPO_SERVO_EVENT_FLOATS == 32,
+              "catppo_servo_sim_events: observation and event descriptors behind the 368 bytes");
 
 // command of (env, episode, resample index): uniform in the reference ranges, dead zone, standing fraction; with a
 // fixed-command table the caller's row `e` as it stands, for every episode and resample index - in the step-response
@@ -97,6 +109,78 @@ __device__ __forceinline__ float init_q(const catppo_servo_sim& d, uint32_t gid,
   return def + (pick(r, lane & 3) - 0.5f) * d.init_noise;
 }
 
+// the event block as the wave holds it: wave lane k < 32 has loaded word k, every lane reads word k through readlane, so
+// all of this is wave-uniform (scalar registers)
+struct Events {
+  uint32_t flags;
+  float p;
+  int buckets;
+  float push[10], jpos[2], jvel[2], rpos[4], rvel[6], fric[2];      // (lo, width) pairs
+};
+
+__device__ __forceinline__ float ev_word(float mine, int k) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine), k));
+}
+
+__device__ __forceinline__ Events events_of(float mine) {
+  Events E;
+  E.flags = (uint32_t)__float_as_int(ev_word(mine, 0));
+  E.p = ev_word(mine, 1);
+  E.buckets = __float_as_int(ev_word(mine, 2));
+#pragma unroll
+  for (int i = 0; i < 10; ++i) E.push[i] = ev_word(mine, 4 + i);
+#pragma unroll
+  for (int i = 0; i < 2; ++i) E.jpos[i] = ev_word(mine, 14 + i), E.jvel[i] = ev_word(mine, 16 + i), E.fric[i] = ev_word(mine, 28 + i);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) E.rpos[i] = ev_word(mine, 18 + i);
+#pragma unroll
+  for (int i = 0; i < 6; ++i) E.rvel[i] = ev_word(mine, 22 + i);
+  return E;
+}
+
+__device__ __forceinline__ rng::u32x4 ev_block(const catppo_servo_sim& d, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t tag) {
+  return rng::philox4x32_10(rng::u32x4{c0, c1, c2, tag}, (uint32_t)d.seed, (uint32_t)(d.seed >> 32));
+}
+
+// joint `lane` of the first state of (env, episode) under the events: the built-in pose, or the joint-reset term's
+__device__ __forceinline__ void first_joint(const catppo_servo_sim& d, const Events& E, uint32_t gid, uint32_t ep, int lane,
+                                            float def, float& q0, float& qd0) {
+  const float u = pick(ev_block(d, gid, ep, (uint32_t)(lane >> 2), kTagInit), lane & 3);
+  qd0 = 0.f;
+  if (E.flags & (CATPPO_SERVO_EVENT_JOINT_SCALE | CATPPO_SERVO_EVENT_JOINT_OFFSET)) {
+    const float s = E.jpos[0] + u * E.jpos[1];
+    q0 = (E.flags & CATPPO_SERVO_EVENT_JOINT_SCALE) ? def * s : def + s;
+    if (E.flags & CATPPO_SERVO_EVENT_JOINT_OFFSET)
+      qd0 = E.jvel[0] + pick(ev_block(d, gid, ep, (uint32_t)(lane >> 2), kTagJvel), lane & 3) * E.jvel[1];
+  } else {
+    q0 = def + (u - 0.5f) * d.init_noise;
+  }
+}
+
+// root of the first state of (env, episode): position x y and velocities vx vy wz (zeros without the root-reset term)
+__device__ __forceinline__ void first_root(const catppo_servo_sim& d, const Events& E, uint32_t gid, uint32_t ep, float xy[2],
+                                           float v0[3]) {
+  xy[0] = xy[1] = v0[0] = v0[1] = v0[2] = 0.f;
+  if (E.flags & CATPPO_SERVO_EVENT_ROOT) {
+    const rng::u32x4 a = ev_block(d, gid, ep, 0u, kTagRoot), b = ev_block(d, gid, ep, 1u, kTagRoot);
+    xy[0] = E.rpos[0] + rng::uniform_open(a.x) * E.rpos[1];
+    xy[1] = E.rpos[2] + rng::uniform_open(a.y) * E.rpos[3];
+    v0[0] = E.rvel[0] + rng::uniform_open(b.x) * E.rvel[1];
+    v0[1] = E.rvel[2] + rng::uniform_open(b.y) * E.rvel[3];
+    v0[2] = E.rvel[4] + rng::uniform_open(b.z) * E.rvel[5];
+  }
+}
+
+// traction of env `gid`: the friction of its bucket against the ground's 1.0, at most 1
+__device__ __forceinline__ float traction_of(const catppo_servo_sim& d, const Events& E, uint32_t gid) {
+  if (!(E.flags & CATPPO_SERVO_EVENT_FRICTION)) return 1.f;
+  int bucket = (int)(rng::uniform_open(ev_block(d, gid, 0u, 0u, kTagFric).x) * (float)E.buckets);
+  bucket = bucket < E.buckets - 1 ? bucket : E.buckets - 1;
+  bucket = bucket > 0 ? bucket : 0;
+  const float mu = E.fric[0] + rng::uniform_open(ev_block(d, (uint32_t)bucket, 0u, 1u, kTagFric).x) * E.fric[1];
+  return mu < 1.f ? mu : 1.f;
+}
+
 // kMode = kTrain is the launch with all three evaluation pointers NULL: everything they add is compiled out of it, so
 // that a training step runs the code it ran before the fields existed.  kEvaluate: a fixed-command table [N, 3] or an
 // evaluation record, and nothing else - the evaluation that runs inside training keeps the code it had, too.
@@ -110,14 +194,22 @@ __device__ __forceinline__ float init_q(const catppo_servo_sim& d, uint32_t gid,
 // over the finished LDS row fills the row's second observation field.  Orthogonal to both; only the obs-on launch carries
 // the second kernel argument, and with the pack empty every line it adds is compiled out.  LDS (16 rows of about 356
 // floats) admits 7 workgroups of the obs-on instances per CU, so they are not held to 64 VGPRs either.
-template <int kMode, bool kRew, typename... Obs>
-__global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeof...(Obs) == 0) ? 8 : 1) void servo_sim_kernel(
-    const catppo_servo_sim d, const Obs... obs_desc) {
-  constexpr bool kObs = sizeof...(Obs) != 0;
+// The pack may also hold catppo_servo_events, alone or behind catppo_servo_obs ("Events"): pushes, the
+// first state's reset terms and the traction.  Orthogonal to the rest; only the events-on launch carries that kernel
+// argument, and without it every line it adds is compiled out.  24 instances in all.
+template <int kMode, bool kRew, typename... Ext>
+__global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeof...(Ext) == 0) ? 8 : 1) void servo_sim_kernel(
+    const catppo_servo_sim d, const Ext... ext) {
+  constexpr bool kObs = (std::is_same_v<Ext, catppo_servo_obs> || ...);
+  constexpr bool kEv = (std::is_same_v<Ext, catppo_servo_events> || ...);
   constexpr bool kEval = kMode != kTrain;
   extern __shared__ float4 lds4[];
   float* lds = reinterpret_cast<float*>(lds4);
   const int tid = threadIdx.x, lane = tid & 15, grp = tid >> 4;
+  // wave lane k < 32 loads word k of the event block, long before the first use
+  float ev_mine = 0.f;
+  if constexpr (kEv)
+    if ((tid & 63) < CATPPO_SERVO_EVENT_FLOATS) ev_mine = ext_of<catppo_servo_events>(ext...).block[tid & 63];
   const int F = d.row_floats, D = d.obs_dim, B3 = d.B * 3;
   const int64_t e0 = (int64_t)blockIdx.x * kEnvsPerBlock;
   // rows past N recompute the last env and are dropped at the store: no divergence around the shuffles and barriers
@@ -138,6 +230,8 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
   const float def = isj ? d.default_joint_pos[lane] : 0.f;
   float cmd[3];
   command_of<kMode>(d, e, gid, ep, (uint32_t)(t / d.resample_steps), t, cmd);
+  Events E = {};
+  if constexpr (kEv) E = events_of(ev_mine);
   float* obs = row + d.off_obs;
   // (episode, episode length) of the state the observation describes: the key of its noise
   uint32_t obs_ep = 0u, obs_t = 0u;
@@ -164,17 +258,38 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
 
   if (init) {
     // the first state of episode 0: default pose + noise, at rest, four feet on the ground
-    const float q0 = isj ? init_q(d, gid, 0u, lane, def) : 0.f;
-    if (isj) {
-      row[d.off_joint_pos + lane] = q0;
-      if (9 + lane < D) obs[9 + lane] = q0 - def;
+    if constexpr (kEv) {
+      // with events the first state may move: the joint-reset term's pose and velocity
+      if (isj) {
+        float q0 = 0.f, qd0 = 0.f;
+        first_joint(d, E, gid, 0u, lane, def, q0, qd0);
+        row[d.off_joint_pos + lane] = q0;
+        row[d.off_joint_vel + lane] = qd0;
+        if (9 + lane < D) obs[9 + lane] = q0 - def;
+        if (21 + lane < D) obs[21 + lane] = qd0;
+      } else {
+        row[d.off_servo + 9 + f] = 1.f;
+      }
     } else {
-      row[d.off_servo + 9 + f] = 1.f;
+      const float q0 = isj ? init_q(d, gid, 0u, lane, def) : 0.f;
+      if (isj) {
+        row[d.off_joint_pos + lane] = q0;
+        if (9 + lane < D) obs[9 + lane] = q0 - def;
+      } else {
+        row[d.off_servo + 9 + f] = 1.f;
+      }
     }
     if (lane == 12) {
       row[d.off_projected_gravity + 2] = -1.f;
       row[d.off_root_pos + 2] = d.stand_height;
       if (5 < D) obs[5] = -1.f;
+      if constexpr (kEv) {
+        float xy[2], fv[3];
+        first_root(d, E, gid, 0u, xy, fv);
+        row[d.off_root_pos] = xy[0], row[d.off_root_pos + 1] = xy[1];
+        for (int k = 0; k < 3; ++k) row[d.off_servo + k] = fv[k];
+        if (2 < D) obs[2] = fv[2];
+      }
     }
     if (lane == 13) {
       for (int k = 0; k < 3; ++k) {
@@ -190,8 +305,13 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
     // ---- the state this step starts from: the row, or the first state of episode `ep` re-derived from the counter
     float q = 0.f, qd = 0.f, a = 0.f;
     if (isj) {
-      q = rst ? init_q(d, gid, ep, lane, def) : in[d.off_joint_pos + lane];
-      qd = rst ? 0.f : in[d.off_joint_vel + lane];
+      if constexpr (kEv) {
+        q = in[d.off_joint_pos + lane], qd = in[d.off_joint_vel + lane];
+        if (rst) first_joint(d, E, gid, ep, lane, def, q, qd);
+      } else {
+        q = rst ? init_q(d, gid, ep, lane, def) : in[d.off_joint_pos + lane];
+        qd = rst ? 0.f : in[d.off_joint_vel + lane];
+      }
       a = d.action[e * kJoints + lane];
     }
     // ---- joints: `decimation` substeps of the clamped PD servo, semi-implicit Euler; the substep of largest |tau| is reported
@@ -208,18 +328,48 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
     const float dq = q - def;
     // ---- base: five joint reductions, first-order lags
     float red[5];
+    if constexpr (kEv) {
+      // the velocity rows feel the env's traction: one more rounded multiply
+      const float m = traction_of(d, E, gid);
 #pragma unroll
-    for (int k = 0; k < 5; ++k) red[k] = tree16(gain(k, lane) * dq);
+      for (int k = 0; k < 5; ++k) red[k] = k < 3 ? tree16((gain(k, lane) * m) * dq) : tree16(gain(k, lane) * dq);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 5; ++k) red[k] = tree16(gain(k, lane) * dq);
+    }
     const float step_dt = d.dt * (float)d.decimation;
+    // events: the root of a first state, and the push of this step on the state the step starts from (after the reset
+    // select).  roll_k, pitch_k: the kicked tilt the lags start from; the rates keep differentiating against roll0, pitch0
+    float first_xy[2] = {0.f, 0.f}, first_v[3] = {0.f, 0.f, 0.f}, push_v[3] = {0.f, 0.f, 0.f}, kick[2] = {0.f, 0.f};
+    bool pushed = false;
+    if constexpr (kEv) {
+      if (rst) first_root(d, E, gid, ep, first_xy, first_v);
+      if (E.flags & CATPPO_SERVO_EVENT_PUSH) {
+        const rng::u32x4 r = ev_block(d, gid, ep, (uint32_t)t << 1, kTagPush);
+        pushed = rng::uniform_open(r.x) < E.p;
+        if (pushed) {
+          push_v[0] = E.push[0] + rng::uniform_open(r.y) * E.push[1];
+          push_v[1] = E.push[2] + rng::uniform_open(r.z) * E.push[3];
+          push_v[2] = E.push[4] + rng::uniform_open(r.w) * E.push[5];
+          const rng::u32x4 r1 = ev_block(d, gid, ep, ((uint32_t)t << 1) | 1u, kTagPush);
+          kick[0] = (E.push[6] + rng::uniform_open(r1.x) * E.push[7]) * step_dt;
+          kick[1] = (E.push[8] + rng::uniform_open(r1.y) * E.push[9]) * step_dt;
+        }
+      }
+    }
     float v[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-      const float v0 = rst ? 0.f : xin[k];
+      float v0 = rst ? 0.f : xin[k];
+      if constexpr (kEv) v0 = pushed ? push_v[k] : rst ? first_v[k] : xin[k];
       v[k] = v0 + d.vel_alpha * (red[k] - v0);
     }
     const float roll0 = rst ? 0.f : xin[3], pitch0 = rst ? 0.f : xin[4];
-    const float roll = roll0 + d.tilt_beta * (red[3] - roll0);
-    const float pitch = pitch0 + d.tilt_beta * (red[4] - pitch0);
+    float roll_k = roll0, pitch_k = pitch0;
+    if constexpr (kEv)
+      if (pushed) roll_k = roll0 + kick[0], pitch_k = pitch0 + kick[1];
+    const float roll = roll_k + d.tilt_beta * (red[3] - roll_k);
+    const float pitch = pitch_k + d.tilt_beta * (red[4] - pitch_k);
     const float ang[3] = {(roll - roll0) / step_dt, (pitch - pitch0) / step_dt, v[2]};
     const float tilt2 = roll * roll + pitch * pitch;
     const bool fallen = tilt2 > d.tilt_max * d.tilt_max;
@@ -242,7 +392,9 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
     const float last_air = touch ? air0 : last_air0;
     const float air = con > 0.f ? 0.f : air0 + step_dt;
     const float fbase = z < d.min_height ? d.base_stiffness * (d.min_height - z) : 0.f;
-    const float x0 = rst ? 0.f : in[d.off_root_pos], y0 = rst ? 0.f : in[d.off_root_pos + 1];
+    float x0 = rst ? 0.f : in[d.off_root_pos], y0 = rst ? 0.f : in[d.off_root_pos + 1];
+    if constexpr (kEv)
+      if (rst) x0 = first_xy[0], y0 = first_xy[1];
     // ---- reward: rational stand-ins for the two exp tracking rewards
     const float ex = cmd[0] - v[0], ey = cmd[1] - v[1], ew = cmd[2] - v[2];
     const float reward = 1.f / (1.f + (ex * ex + ey * ey) / d.reward_scale) + 0.5f / (1.f + (ew * ew) / d.reward_scale);
@@ -320,6 +472,8 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
           case 13: head = ncon; break;
           default: break;
         }
+        if constexpr (kEv)
+          if (lane == 14) head = pushed ? 1.f : 0.f;
         tr[lane] = head;
         if (lane < 8) tr[16 + lane] = lane < 4 ? con : fz;      // lanes 0..3 and 4..7 both carry feet 0..3
         if (isj) {
@@ -338,7 +492,14 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
       row[d.off_joint_acc + lane] = tau_w / d.inertia;
       row[d.off_applied_torque + lane] = tau_w;
       float o_q = dq, o_v = qd, o_a = a;
-      if (ends) o_q = init_q(d, gid, ep_out, lane, def) - def, o_v = 0.f, o_a = 0.f;
+      if constexpr (kEv) {
+        if (ends) {
+          first_joint(d, E, gid, ep_out, lane, def, o_q, o_v);
+          o_q = o_q - def, o_a = 0.f;
+        }
+      } else {
+        if (ends) o_q = init_q(d, gid, ep_out, lane, def) - def, o_v = 0.f, o_a = 0.f;
+      }
       if (9 + lane < D) obs[9 + lane] = o_q;
       if (21 + lane < D) obs[21 + lane] = o_v;
       if (33 + lane < D) obs[33 + lane] = o_a;
@@ -374,6 +535,11 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
         command_of<kMode>(d, e, gid, ep_out, 0u, 0, cn);
         head[0] = head[1] = head[2] = head[3] = head[4] = 0.f;
         head[5] = -1.f, head[6] = cn[0], head[7] = cn[1], head[8] = cn[2];
+        if constexpr (kEv) {
+          float nxy[2], nv[3];
+          first_root(d, E, gid, ep_out, nxy, nv);
+          head[2] = nv[2];
+        }
       }
       for (int k = 0; k < 9; ++k)
         if (k < D) obs[k] = head[k];
@@ -411,7 +577,7 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
   // of the env's group produces floats 4 l .. 4 l + 3 from one Philox block and writes one float4; the floats past `width`
   // of the padded field stay the zeros the row was filled with
   if constexpr (kObs) {
-    const catppo_servo_obs& o = first_of(obs_desc...);
+    const catppo_servo_obs& o = ext_of<catppo_servo_obs>(ext...);
     if (4 * lane < o.width) {
       float x[4] = {0.f, 0.f, 0.f, 0.f};
       catppo_servo_obs_entry en[4];
@@ -454,15 +620,29 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
   }
 }
 
+// the launch: the pack of extensions decides the kernel's signature, (mode, rewards) the instance among its six
+template <typename... Ext>
+void launch(int mode, bool rew, unsigned nblk, size_t lds_bytes, hipStream_t stream, const catppo_servo_sim& d, const Ext&... ext) {
+  using Kernel = void (*)(const catppo_servo_sim, const Ext...);
+  const Kernel table[3][2] = {{servo_sim_kernel<kTrain, false, Ext...>, servo_sim_kernel<kTrain, true, Ext...>},
+                              {servo_sim_kernel<kEvaluate, false, Ext...>, servo_sim_kernel<kEvaluate, true, Ext...>},
+                              {servo_sim_kernel<kStepResponse, false, Ext...>, servo_sim_kernel<kStepResponse, true, Ext...>}};
+  hipLaunchKernelGGL(table[mode][rew ? 1 : 0], dim3(nblk), dim3(kThreads), lds_bytes, stream, d, ext...);
+}
+
 }  // namespace
 
 extern "C" int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* desc, void* stream) {
   CATPPO_CHECK_ARG(ctx, ctx != nullptr);
   CATPPO_CHECK_ARG(ctx, desc != nullptr);
   const catppo_servo_sim& d = *desc;
-  // reserved names what lies behind the descriptor: nothing, or the observation descriptor of a catppo_servo_sim_obs
-  CATPPO_CHECK_ARG(ctx, d.reserved == 0 || d.reserved == CATPPO_SERVO_EXT_OBS);
-  const catppo_servo_obs* obs = d.reserved == CATPPO_SERVO_EXT_OBS ? &reinterpret_cast<const catppo_servo_sim_obs*>(desc)->obs : nullptr;
+  // reserved names what lies behind the descriptor: nothing, the observation descriptor of a catppo_servo_sim_obs, or the
+  // observation and event descriptors of a catppo_servo_sim_events (whose observation descriptor may be empty)
+  CATPPO_CHECK_ARG(ctx, d.reserved == 0 || d.reserved == CATPPO_SERVO_EXT_OBS || d.reserved == CATPPO_SERVO_EXT_EVENTS);
+  const catppo_servo_obs* obs = d.reserved != 0 ? &reinterpret_cast<const catppo_servo_sim_obs*>(desc)->obs : nullptr;
+  const catppo_servo_events* ev =
+      d.reserved == CATPPO_SERVO_EXT_EVENTS ? &reinterpret_cast<const catppo_servo_sim_events*>(desc)->ev : nullptr;
+  if (ev && obs->width == 0 && obs->table == nullptr) obs = nullptr;
   CATPPO_CHECK_ARG(ctx, d.N >= 1 && d.N < (int64_t(1) << 31) && d.env_offset >= 0 && d.env_offset + d.N < (int64_t(1) << 32));
   CATPPO_CHECK_ARG(ctx, d.state_in && d.state_out && d.episode_length);
   CATPPO_CHECK_ARG(ctx, d.init || (d.action && d.reset && d.state_in != d.state_out));
@@ -512,22 +692,24 @@ extern "C" int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* de
     CATPPO_CHECK_ARG(ctx, tb != d.state_in && tb != d.state_out && tb != d.eval && tb != d.trace && tb != d.fixed_command &&
                               tb != d.reward_rec && tb != (const void*)d.reward_table);
   }
+  if (ev) {
+    CATPPO_CHECK_ARG(ctx, d.max_episode_length < (int64_t(1) << 27));
+    CATPPO_CHECK_ARG(ctx, ev->floats == CATPPO_SERVO_EVENT_FLOATS && ev->reserved == 0);
+    // the block is device memory: its writer checks the values (Solo12ServoSim.set_event_block); they are never addresses
+    const void* bl = ev->block;
+    CATPPO_CHECK_ARG(ctx, bl != nullptr && ((uintptr_t)bl % 16) == 0);
+    CATPPO_CHECK_ARG(ctx, bl != d.state_in && bl != d.state_out && bl != d.eval && bl != d.trace && bl != d.fixed_command &&
+                              bl != d.reward_rec && bl != (const void*)d.reward_table && (!obs || bl != (const void*)obs->table));
+  }
   const unsigned nblk = (unsigned)cdiv64(d.N, kEnvsPerBlock);
   const size_t lds_bytes = (size_t)d.row_floats * kEnvsPerBlock * sizeof(float);
   const int mode = (d.trace || d.fixed_segments > 1) ? kStepResponse : (d.fixed_command || d.eval) ? kEvaluate : kTrain;
   const bool rew = d.reward_terms > 0;
-  const auto kernel = mode == kStepResponse ? (rew ? servo_sim_kernel<kStepResponse, true> : servo_sim_kernel<kStepResponse, false>)
-                      : mode == kEvaluate   ? (rew ? servo_sim_kernel<kEvaluate, true> : servo_sim_kernel<kEvaluate, false>)
-                                            : (rew ? servo_sim_kernel<kTrain, true> : servo_sim_kernel<kTrain, false>);
-  if (obs) {
-    const auto okernel =
-        mode == kStepResponse ? (rew ? servo_sim_kernel<kStepResponse, true, catppo_servo_obs> : servo_sim_kernel<kStepResponse, false, catppo_servo_obs>)
-        : mode == kEvaluate   ? (rew ? servo_sim_kernel<kEvaluate, true, catppo_servo_obs> : servo_sim_kernel<kEvaluate, false, catppo_servo_obs>)
-                              : (rew ? servo_sim_kernel<kTrain, true, catppo_servo_obs> : servo_sim_kernel<kTrain, false, catppo_servo_obs>);
-    hipLaunchKernelGGL(okernel, dim3(nblk), dim3(kThreads), lds_bytes, static_cast<hipStream_t>(stream), d, *obs);
-  } else {
-    hipLaunchKernelGGL(kernel, dim3(nblk), dim3(kThreads), lds_bytes, static_cast<hipStream_t>(stream), d);
-  }
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  if (obs && ev) launch(mode, rew, nblk, lds_bytes, st, d, *obs, *ev);
+  else if (ev) launch(mode, rew, nblk, lds_bytes, st, d, *ev);
+  else if (obs) launch(mode, rew, nblk, lds_bytes, st, d, *obs);
+  else launch(mode, rew, nblk, lds_bytes, st, d);
   CATPPO_CHECK_LAUNCH(ctx);
   return CATPPO_OK;
 }

@@ -729,7 +729,7 @@ typedef struct catppo_servo_sim {
   const uint8_t* reset;                  /* [N] */
   const int64_t* episode_length;         /* [N], before this step's increment */
   int64_t max_episode_length;
-  int32_t decimation, resample_steps, init, reserved;   /* reserved: 0, or CATPPO_SERVO_EXT_OBS (see "Observations" below) */
+  int32_t decimation, resample_steps, init, reserved;   /* reserved: 0, CATPPO_SERVO_EXT_OBS or CATPPO_SERVO_EXT_EVENTS (see below) */
   uint64_t seed;
   float default_joint_pos[12];
   float dt, kp, kd, inertia, tau_max, action_scale, vel_alpha, tilt_beta, tilt_max, reward_scale, foot_clearance,
@@ -785,6 +785,52 @@ typedef struct catppo_servo_sim_obs {
   catppo_servo_sim sim;                   /* sim.reserved = CATPPO_SERVO_EXT_OBS */
   catppo_servo_obs obs;
 } catppo_servo_sim_obs;
+
+/* Events ("Events").  desc->reserved == CATPPO_SERVO_EXT_EVENTS: `desc` is the head of a
+ * catppo_servo_sim_events, i.e. the observation descriptor and an event descriptor lie behind the 368 bytes.  Under this
+ * value obs.width == 0 with a NULL table means "no observation table" (the row has no policy field); otherwise `obs` is
+ * checked and used exactly as under CATPPO_SERVO_EXT_OBS.  0 and CATPPO_SERVO_EXT_OBS keep their meaning.
+ * ev.block is a DEVICE array of CATPPO_SERVO_EVENT_FLOATS fp32 words, 16-byte aligned, read by every launch (a flag the host
+ * rewrites in stream order is in the next launch, under graph replay too).  It may alias none of the state buffers, the
+ * records, the trace, the command table, the reward table or the observation table.  max_episode_length < 2^27.  Words:
+ *   0 flags (uint32 bits: 1 push, 2 joint reset by scale, 4 joint reset by offset, 8 root reset, 16 friction)
+ *   1 p (push probability per step)    2 num_buckets (int32)    3 zero
+ *   4..13  push (lo, width) of vx vy wz roll-rate pitch-rate        14 15 joint position (lo, width)
+ *   16 17  joint velocity (lo, width; offset mode)                  18..21 root pose (lo, width) of x y
+ *   22..27 root velocity (lo, width) of x y yaw                     28 29 friction (lo, width)        30 31 zero
+ * A sample is s = lo + u * width (two rounded fp32 operations), u = uniform in (0, 1) from a word of Philox4x32-10 with
+ * key = seed and counter {global env id, episode, third, tag}:
+ *   push         tag "PUSH", third = (t << 1) | b, t = episode length the step starts from.  Block 0: word 0 decides
+ *                (pushed = u < p), words 1..3 sample vx vy wz; block 1 (pushed envs only): words 0 1 the roll and pitch rates.
+ *                A push replaces the three velocities the step starts from (after the reset select) and adds rate * step_dt
+ *                to roll and pitch; ang[0], ang[1] keep differentiating against the un-kicked values.
+ *   joint reset  position from tag "INIT", block j / 4, word j % 4 (the built-in pose's words): q0 = def * s (scale) or
+ *                def + s (offset); velocity 0.f (scale) or s from tag "JVEL", same block and word (offset).
+ *   root reset   tag "ROOT": block 0 words 0 1 the first state's root x y, block 1 words 0 1 2 its vx vy wz.
+ *   friction     tag "FRIC": bucket = clamp((int)(u * (float)num_buckets), 0, num_buckets - 1) from {gid, 0, 0, tag} word 0;
+ *                mu = lo + u * width from {bucket, 0, 1, tag} word 0; m = mu < 1.f ? mu : 1.f; the three velocity rows of
+ *                the base model become tree16((gain * m) * dq).  Recomputed by every launch, no state in the row.
+ * The first state (joint and root terms) serves the init launch, the start of a step whose reset flag is set and the
+ * post-reset observation of a step that ends its episode (obs 9..20, 21..32 and wz at obs 2) alike.
+ * With the push flag set, float 14 of a trace row is 1.f in a step whose env was pushed.  The block's writer checks its
+ * values (Solo12ServoSim.set_event_block); whatever it holds the launch stays inside its row. */
+#define CATPPO_SERVO_EXT_EVENTS 0x45565431   /* "EVT1": value of catppo_servo_sim.reserved that announces catppo_servo_sim_events */
+#define CATPPO_SERVO_EVENT_FLOATS 32
+#define CATPPO_SERVO_EVENT_PUSH 1u
+#define CATPPO_SERVO_EVENT_JOINT_SCALE 2u
+#define CATPPO_SERVO_EVENT_JOINT_OFFSET 4u
+#define CATPPO_SERVO_EVENT_ROOT 8u
+#define CATPPO_SERVO_EVENT_FRICTION 16u
+typedef struct catppo_servo_events {
+  const float* block;                     /* DEVICE array [CATPPO_SERVO_EVENT_FLOATS], 16-byte aligned */
+  int32_t floats;                         /* CATPPO_SERVO_EVENT_FLOATS */
+  int32_t reserved;                       /* 0 */
+} catppo_servo_events;
+typedef struct catppo_servo_sim_events {
+  catppo_servo_sim sim;                   /* sim.reserved = CATPPO_SERVO_EXT_EVENTS */
+  catppo_servo_obs obs;                   /* width 0 and table NULL: no observation table */
+  catppo_servo_events ev;
+} catppo_servo_sim_events;
 
 /* ---- test hook (ABI 0.6) ------------------------------------------------------------------------------------------
  * buf != NULL ([2][M] int32, device): the head / loss kernel of every following catppo_ppo_minibatch_* call writes the clip

@@ -62,6 +62,10 @@ def main(argv=None):
     parser.add_argument("--stochastic", action="store_true", default=False, help="Evaluate with sampled actions.")
     parser.add_argument("--obs_noise", choices=("on", "off"), default=None,
                         help="Observation noise of a task with cfg.observations (default: what the task's cfg says).")
+    parser.add_argument("--pushes", choices=("on", "off"), default=None,
+                        help="Interval events (pushes) of a task with cfg.events (default: what the task's cfg says).")
+    parser.add_argument("--push_probability", type=float, default=None, metavar="P",
+                        help="Push probability per env and control step of a task with a push term (default: the reference's).")
     cli_args.add_clean_rl_args(parser)
     args_cli = parser.parse_args(argv)
     if args_cli.eval_schedule is not None:
@@ -84,6 +88,18 @@ def main(argv=None):
         if getattr(env_cfg, "observations", None) is None:
             parser.error("--obs_noise needs a task with cfg.observations")
         env_cfg.observations.policy.enable_corruption = args_cli.obs_noise == "on"
+    if args_cli.pushes is not None or args_cli.push_probability is not None:
+        if getattr(env_cfg, "events", None) is None:
+            parser.error("--pushes and --push_probability need a task with cfg.events")
+        if args_cli.pushes is not None:
+            env_cfg.pushes = args_cli.pushes == "on"
+        if args_cli.push_probability is not None:
+            from cat_envs.tasks.utils.mdp import events as _events
+            terms = [t for t in vars(env_cfg.events).values()
+                     if getattr(t, "func", None) is _events.push_by_setting_velocity_with_random_envs]
+            if not terms:
+                parser.error("--push_probability needs a task whose cfg.events has a push term")
+            terms[0].params = {**terms[0].params, "probability": args_cli.push_probability}
     agent_cfg = cli_args.parse_clean_rl_cfg(args_cli.task, args_cli)
     log_root_path = os.path.abspath(os.path.join("logs", "clean_rl", agent_cfg.experiment_name))
     print(f"[INFO] Loading experiment from directory: {log_root_path}")

@@ -15,6 +15,11 @@ rewards-off one.  profiles/servo_reward_kernel_stats.csv: the two arms alternati
 --obs runs the task with the reference's observation block (Isaac-Velocity-CaT-Flat-Solo12-Servo-Obs-v0, noise on), so that the
 simulator's launch is the obs-on training instance.  profiles/servo_obs_kernel_stats.csv: the parent's library, this library
 without the flag and this library with --obs, alternating in one session, every run listed.
+--events runs the task with the reference's event block (Isaac-Velocity-CaT-Flat-Solo12-Servo-Events-v0), so that the simulator's
+launch is the events-on training instance.  The reference's push probability is 0.00025 per env and step; the arm raises it to
+0.01 (the term's ``probability`` param) so that every one of the 240 launches pushes some envs - about 41 of 4096, 328 of
+32768 - and the pushed branch is part of what is timed.  profiles/servo_events_kernel_stats.csv: the parent's library, this
+library without the flag and this library with --events, alternating in one session, every run listed.
 
 Per env step the trace shows servo_sim_kernel (the simulator), the two launches of catppo_rollout_pre, the one of
 catppo_rollout_post and the policy forward."""
@@ -37,18 +42,23 @@ def main():
     ap.add_argument("--trace", action="store_true", help="attach the record, a schedule of 4 segments and a trace of 32 envs")
     ap.add_argument("--rewards", action="store_true", help="the task with ShapedRewardsCfg: reward terms inside the simulator launch")
     ap.add_argument("--obs", action="store_true", help="the task with ObservationsCfg: observation terms inside the simulator launch")
+    ap.add_argument("--events", action="store_true", help="the task with EventCfg (push probability 0.01): events inside the simulator launch")
     a = ap.parse_args()
-    if a.obs and a.rewards:
-        ap.error("--obs and --rewards are separate arms")
+    if a.obs + a.rewards + a.events > 1:
+        ap.error("--obs, --rewards and --events are separate arms")
     import cat_envs.tasks  # noqa: F401
     from cat_envs.shim import load_cfg_from_registry, make
     from cat_envs.tasks.utils.cleanrl.ppo import PPOTrainer
     task = ("Isaac-Velocity-CaT-Flat-Solo12-Servo-Rewards-v0" if a.rewards else
-            "Isaac-Velocity-CaT-Flat-Solo12-Servo-Obs-v0" if a.obs else "Isaac-Velocity-CaT-Flat-Solo12-Servo-v0")
+            "Isaac-Velocity-CaT-Flat-Solo12-Servo-Obs-v0" if a.obs else
+            "Isaac-Velocity-CaT-Flat-Solo12-Servo-Events-v0" if a.events else "Isaac-Velocity-CaT-Flat-Solo12-Servo-v0")
     env_cfg = load_cfg_from_registry(task, "env_cfg_entry_point")
     if a.rewards:
         from cat_envs.tasks.locomotion.velocity.config.solo12.cat_flat_env_cfg import ShapedRewardsCfg
         env_cfg.rewards = ShapedRewardsCfg()
+    if a.events:
+        push = env_cfg.events.push_robot
+        push.params = {**push.params, "probability": 0.01}
     agent_cfg = load_cfg_from_registry(task, "clean_rl_cfg_entry_point")
     env_cfg.scene.num_envs = a.num_envs
     agent_cfg.minibatch_size = min(agent_cfg.minibatch_size, a.num_envs * agent_cfg.num_steps)
@@ -83,6 +93,9 @@ def main():
         sim = env_u.sim
         diff = (sim.view("policy_obs")[:, 0:3] != sim.view("obs")[:, 0:3] * 0.25).float().mean()
         print(f"policy observation: {env_u.obs_dim} floats, row of {sim.F} floats, noisy share of base_ang_vel {float(diff):.3f}")
+    if a.events:
+        em = env_u.event_manager
+        print(f"events: {em.active_terms}, push probability {em.block['p']:g}, |v| mean {float(env_u.sim.view('servo')[:, 0:3].abs().mean()):.4f}")
     if a.eval or a.trace:
         steps = record[:, 0].cpu()
         assert float(steps.min()) == float(steps.max()) == a.rollouts * trainer.T, (float(steps.min()), float(steps.max()))
