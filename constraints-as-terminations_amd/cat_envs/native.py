@@ -195,6 +195,27 @@ class ServoSimEvents(ServoSimObs):
     _fields_ = [("ev", ServoEvents)]
 
 
+SERVO_EXT_COMMANDS = 0x434D4431         # CATPPO_SERVO_EXT_COMMANDS: ``reserved`` of a descriptor followed by obs, events and commands
+SERVO_COMMAND_FLOATS = 16               # CATPPO_SERVO_COMMAND_FLOATS: words of the device-resident command block
+SERVO_COMMAND_DEADZONE, SERVO_COMMAND_RANDOM_RESAMPLE, SERVO_COMMAND_YAW_FLIP, SERVO_COMMAND_STANDING = 1, 2, 4, 8
+#: word offsets of the command block (include/catppo.h, "Commands"); ``ranges`` is three (lo, width) pairs x y wz
+SERVO_COMMAND_WORDS = {"flags": 0, "dz": 1, "p_still": 2, "p_move": 3, "ranges": 4, "rel_standing": 10, "T_lo": 11,
+                       "T_width": 12}
+SERVO_TRACE_COMMAND = 15                # float of a trace row: 1.f the command was redrawn in the step, + 2.f the yaw flipped
+
+
+class ServoCommands(C.Structure):
+    """catppo_servo_commands: the command descriptor; ``block`` is a device array of ``SERVO_COMMAND_FLOATS`` fp32 words,
+    ``off_cmd_state`` the row's 4-float field (time left until the timed resample | 0 0 0)"""
+    _fields_ = [("block", C.c_void_p), ("floats", C.c_int32), ("off_cmd_state", C.c_int32)]
+
+
+class ServoSimCommands(ServoSimEvents):
+    """catppo_servo_sim_commands: catppo_servo_sim, a ``ServoObs``, a ``ServoEvents`` (a NULL block and ``floats`` 0: no
+    events) and a ``ServoCommands`` behind it; the library reads all three while ``reserved`` is ``SERVO_EXT_COMMANDS``"""
+    _fields_ = [("cmd", ServoCommands)]
+
+
 F32, F16, F64 = 0, 1, 2                 # CATPPO_F32 / _F16 / _F64
 SUM, MAX = 0, 1                         # CATPPO_SUM / _MAX
 LR_FIXED, LR_LINEAR, LR_KEEP = 0, 1, 2
@@ -801,6 +822,8 @@ class Native:
             raise TypeError("servo_sim_step: a descriptor whose 'reserved' announces observations must be a native.ServoSimObs")
         if desc.reserved == SERVO_EXT_EVENTS and not isinstance(desc, ServoSimEvents):   # ... and a catppo_servo_events
             raise TypeError("servo_sim_step: a descriptor whose 'reserved' announces events must be a native.ServoSimEvents")
+        if desc.reserved == SERVO_EXT_COMMANDS and not isinstance(desc, ServoSimCommands):   # ... and a catppo_servo_commands
+            raise TypeError("servo_sim_step: a descriptor whose 'reserved' announces commands must be a native.ServoSimCommands")
         rc = self.lib.catppo_servo_sim_step(self.h, C.byref(desc), self._stream())
         if rc:
             self._ok(rc)

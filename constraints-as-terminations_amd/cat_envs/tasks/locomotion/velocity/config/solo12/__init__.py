@@ -84,3 +84,19 @@ for _name, _cfg in (("Events", "Solo12ServoEventsFlatEnvCfg"), ("Full", "Solo12S
         disable_env_checker=True,
         kwargs={"env_cfg_entry_point": f"{__name__}.cat_flat_env_cfg:{_cfg}_PLAY", **_KW},
     )
+
+# the servo task with a CommandsCfg: the reference's velocity command term inside the simulator's launch (DESIGN section 9,
+# "Commands"); "Reference" is rewards, observations, events and commands together
+for _name, _cfg in (("Commands", "Solo12ServoCommandsFlatEnvCfg"), ("Reference", "Solo12ServoReferenceFlatEnvCfg")):
+    register(
+        id=f"Isaac-Velocity-CaT-Flat-Solo12-Servo-{_name}-v0",
+        entry_point=CaTEnv,
+        disable_env_checker=True,
+        kwargs={"env_cfg_entry_point": f"{__name__}.cat_flat_env_cfg:{_cfg}", **_KW},
+    )
+    register(
+        id=f"Isaac-Velocity-CaT-Flat-Solo12-Servo-{_name}-Play-v0",
+        entry_point=CaTEnv,
+        disable_env_checker=True,
+        kwargs={"env_cfg_entry_point": f"{__name__}.cat_flat_env_cfg:{_cfg}_PLAY", **_KW},
+    )

@@ -11,7 +11,8 @@ or any other block of ``mdp.rewards`` terms is evaluated inside the simulator's 
 (the reference's six terms, order, scales and noise ranges) is evaluated inside the servo simulator's launch
 (``Solo12ServoObsFlatEnvCfg``, DESIGN section 9 "Observations").  Events: ``EventCfg`` (the reference's four terms and
 values) likewise (``Solo12ServoEventsFlatEnvCfg``, DESIGN section 9 "Events"); ``Solo12ServoFullFlatEnvCfg`` puts the three
-blocks together.
+blocks together.  Commands: ``CommandsCfg`` (the reference's ``UniformVelocityCommandWithDeadzoneCfg`` and values) likewise
+(``Solo12ServoCommandsFlatEnvCfg``, DESIGN section 9 "Commands"); ``Solo12ServoReferenceFlatEnvCfg`` is all four blocks.
 """
 import math
 
@@ -24,7 +25,7 @@ from cat_envs.shim import RewardTermCfg as RewTerm
 from cat_envs.shim import SceneEntityCfg, configclass
 from cat_envs.tasks.utils.cat import constraints, curriculums
 from cat_envs.tasks.utils.cat.manager_constraint_cfg import ConstraintTermCfg as ConstraintTerm
-from cat_envs.tasks.utils.mdp import events, observations, rewards
+from cat_envs.tasks.utils.mdp import commands, events, observations, rewards
 
 ALL_JOINTS = [".*_HAA", ".*_HFE", ".*_KFE"]
 
@@ -181,6 +182,8 @@ class SyntheticCfg:
     servo_weight: float = 25.0           # shared between the stance feet
     servo_impact_gain: float = 8.0       # touch-down impulse [N] per rad/s of knee velocity
     servo_init_noise: float = 0.1        # width of the uniform joint noise of an episode's first pose
+    # the built-in command generator; with cfg.commands (a CommandsCfg) the simulator runs that command term instead and
+    # these three fields are unused
     servo_resample_steps: int = 250      # a new command every so many control steps
     servo_standing_fraction: float = 0.02
     servo_command_deadzone: float = 0.1
@@ -332,6 +335,46 @@ class Solo12ServoFullFlatEnvCfg(Solo12ServoFlatEnvCfg):
 
 @configclass
 class Solo12ServoFullFlatEnvCfg_PLAY(Solo12ServoFullFlatEnvCfg):
+    scene: SceneCfg = SceneCfg(num_envs=50, env_spacing=3.0)
+    curriculum: object = None
+    pushes: bool = False
+
+    def __post_init__(self):
+        self.observations.policy.enable_corruption = False
+
+
+@configclass
+class CommandsCfg:
+    """the reference's command block (solo12/cat_flat_env_cfg.py CommandsCfg): one velocity command with a dead zone"""
+    base_velocity = commands.UniformVelocityCommandWithDeadzoneCfg(
+        asset_name="robot", resampling_time_range=(10.0, 10.0), rel_standing_envs=0.02, rel_heading_envs=1.0,
+        heading_command=False, debug_vis=True, velocity_deadzone=0.1,
+        ranges=commands.UniformVelocityCommandCfg.Ranges(lin_vel_x=(-0.3, 1.0), lin_vel_y=(-0.7, 0.7), ang_vel_z=(-0.78, 0.78)))
+
+
+@configclass
+class Solo12ServoCommandsFlatEnvCfg(Solo12ServoFlatEnvCfg):
+    """the servo task with a configurable command block: the simulator's launch runs ``commands``' velocity command term"""
+    commands: CommandsCfg = CommandsCfg()
+
+
+@configclass
+class Solo12ServoCommandsFlatEnvCfg_PLAY(Solo12ServoCommandsFlatEnvCfg):
+    scene: SceneCfg = SceneCfg(num_envs=50, env_spacing=3.0)
+    curriculum: object = None
+
+
+@configclass
+class Solo12ServoReferenceFlatEnvCfg(Solo12ServoFlatEnvCfg):
+    """rewards, observations, events and commands: the four configurable parts of the reference's MDP block together"""
+    rewards: RewardsCfg = RewardsCfg()
+    observations: ObservationsCfg = ObservationsCfg()
+    events: EventCfg = EventCfg()
+    commands: CommandsCfg = CommandsCfg()
+
+
+@configclass
+class Solo12ServoReferenceFlatEnvCfg_PLAY(Solo12ServoReferenceFlatEnvCfg):
     scene: SceneCfg = SceneCfg(num_envs=50, env_spacing=3.0)
     curriculum: object = None
     pushes: bool = False

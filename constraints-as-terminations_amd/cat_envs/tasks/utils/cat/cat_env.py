@@ -184,10 +184,12 @@ class Solo12ServoSim(SyntheticSolo12Sim):
 
     def __init__(self, num_envs: int, obs_dim: int, device, seed: int, syn, dt: float, decimation: int,
                  max_episode_length: int, episode_length: torch.Tensor, reset: torch.Tensor, env_offset: int = 0,
-                 policy_obs_dim: int = 0, events: bool = False):
+                 policy_obs_dim: int = 0, events: bool = False, commands: bool = False):
         """``policy_obs_dim`` = P > 0: the row gets a second observation field ``policy_obs`` of P floats (padded to a
         multiple of 4) that ``set_observation_table`` configures; the raw field ``obs`` stays what it is.
-        ``events``: the descriptor carries the event descriptor, too, and ``set_event_block`` configures it"""
+        ``events``: the descriptor carries the event descriptor, too, and ``set_event_block`` configures it.
+        ``commands``: the row gets one more 16-byte field ``cmd_state`` behind everything else (float 0: the time left until
+        the timed resample), the descriptor carries the command descriptor and ``set_command_block`` configures it"""
         self.N, self.D, self.device = num_envs, obs_dim, torch.device(device)
         self.P = int(policy_obs_dim)
         if self.P and not (1 <= self.P <= native.SERVO_OBS_MAX_WIDTH and obs_dim == native.SERVO_OBS_RAW):
@@ -207,6 +209,9 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         if self.P:                                                      # behind everything else, on a 16-byte boundary
             self.off["policy_obs"] = (self.F, self.P)
             self.F += (self.P + 3) // 4 * 4
+        if commands:
+            self.off["cmd_state"] = (self.F, 4)
+            self.F += 4
         self.cur = torch.zeros(num_envs, self.F, device=self.device)
         self._slabs = [torch.zeros(num_envs, self.F, device=self.device) for _ in range(2)]
         self.cursor = -1
@@ -214,7 +219,8 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         self._episode_length, self._reset = episode_length, reset       # referenced by the descriptor: keep alive
         self._nat = native.get(self.device)
         # with a policy observation the descriptor carries the observation descriptor behind its 368 bytes
-        d = self._desc = native.ServoSimEvents() if events else native.ServoSimObs() if self.P else native.ServoSimRewards()
+        d = self._desc = (native.ServoSimCommands() if commands else native.ServoSimEvents() if events
+                          else native.ServoSimObs() if self.P else native.ServoSimRewards())
         d.N, d.env_offset, d.row_stride, d.row_floats = num_envs, int(env_offset), self.F, self.F
         d.obs_dim, d.H, d.B = obs_dim, H, B
         names = {"projected_gravity": "projected_gravity_b", "root_pos": "root_pos_w"}
@@ -235,6 +241,8 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         self._obs_entries = []
         self._events = bool(events)
         self._event_block, self._event_words = None, None               # device block of the event descriptor, its host copy
+        self._commands = bool(commands)
+        self._command_block, self._command_words = None, None           # likewise, of the command descriptor
         self._build_scene()
 
     def _table(self, t, width, what, lead=()):
@@ -354,8 +362,7 @@ class Solo12ServoSim(SyntheticSolo12Sim):
             self._obs_table = torch.zeros(C.sizeof(host), dtype=torch.uint8, device=self.device)
             d = self._desc
             d.obs.width, d.obs.off_policy_obs, d.obs.table = self.P, self.off["policy_obs"][0], self._obs_table.data_ptr()
-            # from now on every launch fills the field
-            d.reserved = native.SERVO_EXT_EVENTS if self._event_block is not None else native.SERVO_EXT_OBS
+            self._announce()                                            # from now on every launch fills the field
         self._obs_table.copy_(torch.frombuffer(bytearray(host), dtype=torch.uint8))
         self._obs_entries = entries
 
@@ -394,13 +401,62 @@ class Solo12ServoSim(SyntheticSolo12Sim):
             self._event_block = torch.zeros(native.SERVO_EVENT_FLOATS, dtype=torch.float32, device=self.device)
             d = self._desc
             d.ev.block, d.ev.floats, d.ev.reserved = self._event_block.data_ptr(), native.SERVO_EVENT_FLOATS, 0
-            d.reserved = native.SERVO_EXT_EVENTS                        # from now on every launch reads the block
+            self._announce()                                            # from now on every launch reads the block
         old = self._event_words
         if old is not None and (old.view(np.int32)[1:] == ints[1:]).all():
             self._event_block[:1].copy_(torch.from_numpy(words[:1].copy()))
         else:
             self._event_block.copy_(torch.from_numpy(words.copy()))
         self._event_words = words.copy()
+
+    def _announce(self):
+        """``reserved`` names the descriptors behind the 368 bytes that are configured by now"""
+        self._desc.reserved = (native.SERVO_EXT_COMMANDS if self._command_block is not None
+                               else native.SERVO_EXT_EVENTS if self._event_block is not None
+                               else native.SERVO_EXT_OBS if self._obs_table is not None else 0)
+
+    def set_command_block(self, words):
+        """``words``: the ``native.SERVO_COMMAND_FLOATS`` fp32 words of the command block (``mdp.command_manager.pack``; word 0
+        holds the flags as an integer).  Every following launch, init launches included, runs the configured command process
+        instead of the built-in generator.  The block lives on the device and is rewritten here and nowhere else, in stream
+        order: new ranges are in the next launch (when only the ranges changed, those six words alone are copied).  The
+        values are checked here - the library cannot read them."""
+        import numpy as np
+        if not self._commands:
+            raise ValueError("this simulator was built without a command descriptor (commands = False)")
+        words = np.ascontiguousarray(words, np.float32)
+        if words.shape != (native.SERVO_COMMAND_FLOATS,):
+            raise ValueError(f"the command block has {native.SERVO_COMMAND_FLOATS} words, got shape {words.shape}")
+        W = native.SERVO_COMMAND_WORDS
+        flags = int(words.view(np.int32)[W["flags"]])
+        if flags & ~15:
+            raise ValueError(f"command block: flags {flags:#x} (known bits 1 .. 8)")
+        if not np.isfinite(words[1:]).all():
+            raise ValueError("command block: every range, probability and time must be finite")
+        if float(words[W["dz"]]) < 0.0 or any(not 0.0 <= float(words[W[k]]) <= 1.0 for k in ("p_still", "p_move", "rel_standing")):
+            raise ValueError("command block: the dead zone must be >= 0 and p_still, p_move, rel_standing in [0, 1]")
+        if (words[W["ranges"] + 1:W["ranges"] + 6:2] < 0).any() or float(words[W["T_width"]]) < 0.0 or words[13:].any():
+            raise ValueError("command block: every width must be >= 0 and the spare words zero")
+        if not float(words[W["T_lo"]]) > 0.0:
+            raise ValueError("command block: the resampling time must be > 0")
+        if int(self._desc.max_episode_length) >= 2 ** 27:
+            raise ValueError("commands need max_episode_length < 2^27: the step index is part of a Philox counter word")
+        if self._command_block is None:
+            self._command_block = torch.zeros(native.SERVO_COMMAND_FLOATS, dtype=torch.float32, device=self.device)
+            c = self._desc.cmd
+            c.block, c.floats, c.off_cmd_state = self._command_block.data_ptr(), native.SERVO_COMMAND_FLOATS, self.off["cmd_state"][0]
+            self._announce()                                            # from now on every launch reads the block
+        old, a = self._command_words, W["ranges"]
+        if old is not None and (np.delete(old, range(a, a + 6)).view(np.int32) == np.delete(words, range(a, a + 6)).view(np.int32)).all():
+            self._command_block[a:a + 6].copy_(torch.from_numpy(words[a:a + 6].copy()))
+        else:
+            self._command_block.copy_(torch.from_numpy(words.copy()))
+        self._command_words = words.copy()
+
+    @property
+    def command_words(self):
+        """the host copy of the command block as last written (fp32 [16]) or None"""
+        return None if self._command_words is None else self._command_words.copy()
 
     @property
     def event_words(self):
@@ -563,6 +619,17 @@ class CaTEnv:
                                 "evaluated inside its launch; the stream simulator is a pre-generated stream")
             from cat_envs.tasks.utils.mdp import event_manager as EM
             self._event_block = EM.build_block(cfg.events, cfg.sim.dt, cfg.episode_length_s)
+        # cfg.commands: the velocity command is IsaacLab's command term, evaluated inside the simulator's launch as a stateful
+        # process on the row ("Commands"); the servo_resample_steps / servo_standing_fraction /
+        # servo_command_deadzone fields of SyntheticCfg are then unused
+        self._command_block = None
+        if getattr(cfg, "commands", None) is not None:
+            if kind != "servo":
+                raise TypeError("cfg.commands needs the closed-loop simulator (SyntheticCfg.kind = 'servo'): the command term "
+                                "is evaluated inside its launch; the stream simulator's command is a pre-generated stream")
+            from cat_envs.tasks.utils.mdp import command_manager as KM
+            self._command_block = KM.build_block(cfg.commands, cfg.sim.dt, cfg.episode_length_s)
+            self._check_command_names(self._command_block["name"])
         if kind == "stream":
             self.sim = SyntheticSolo12Sim(self.num_envs, self.obs_dim, self.device, seed + int(syn.seed_offset),
                                           int(syn.stream_steps))
@@ -589,7 +656,7 @@ class CaTEnv:
                                       cfg.sim.dt, cfg.decimation, self.max_episode_length, self.episode_length_buf,
                                       self.reset_buf, env_offset=int(getattr(cfg.scene, "env_offset", 0) or 0),
                                       policy_obs_dim=self.obs_dim if self._obs_table is not None else 0,
-                                      events=self._event_block is not None)
+                                      events=self._event_block is not None, commands=self._command_block is not None)
             self.scene = self.sim.scene
         self.obs_buf = {"policy": self.sim.view(self._obs_field)}
         self._rstep = None
@@ -607,6 +674,22 @@ class CaTEnv:
     def seed(self, seed: int = -1) -> int:
         return seed
 
+    def _check_command_names(self, known: str):
+        """every ``command_name`` of a reward or observation term names the command term"""
+        groups = []
+        if getattr(self.cfg, "rewards", None) is not None:
+            groups.append(("reward", self.cfg.rewards))
+        obs = getattr(self.cfg, "observations", None)
+        if obs is not None and getattr(obs, "policy", None) is not None:
+            groups.append(("observation", obs.policy))
+        for what, group in groups:
+            items = group.items() if isinstance(group, dict) else group.__dict__.items()
+            for name, term in items:
+                wanted = (getattr(term, "params", None) or {}).get("command_name")
+                if wanted is not None and wanted != known:
+                    raise ValueError(f"{what} term '{name}': command_name '{wanted}' names no command term of cfg.commands "
+                                     f"(the command term is '{known}')")
+
     # managers --------------------------------------------------------------------------------
     def load_managers(self):
         """reference: cat_env.py:18-40 (constraint manager created after the base managers)"""
@@ -614,6 +697,10 @@ class CaTEnv:
         cmd = self.sim.view("command")
         self.command_manager = types.SimpleNamespace(get_command=lambda name: cmd, reset=lambda ids=None: {},
                                                      compute=lambda dt: None)
+        if self._command_block is not None:
+            from cat_envs.tasks.utils.mdp.command_manager import CommandManager
+            self.command_manager = CommandManager(self.cfg.commands, self, self._command_block)
+            print("[INFO] Command Manager: ", self.command_manager)
         self.curriculum_manager = _CurriculumManager(getattr(self.cfg, "curriculum", None), self)
         if hasattr(self.cfg, "constraints"):
             self.constraint_manager = ConstraintManager(self.cfg.constraints, self)
@@ -711,6 +798,8 @@ class CaTEnv:
             fp["observation_terms"] = self.observation_manager.fingerprint()
         if hasattr(self, "event_manager"):           # likewise
             fp["event_terms"] = self.event_manager.fingerprint()
+        if getattr(self, "_command_block", None) is not None:          # likewise
+            fp["command_terms"] = self.command_manager.fingerprint()
         return fp
 
     def state_dict(self) -> dict:
@@ -728,6 +817,8 @@ class CaTEnv:
             sd["observations"] = self.observation_manager.state_dict()
         if hasattr(self, "event_manager"):           # the draws are stateless; the interval switch is the state
             sd["events"] = self.event_manager.state_dict()
+        if getattr(self, "_command_block", None) is not None:          # command and time left are part of the simulator's ``cur``; the ranges are not
+            sd["commands"] = self.command_manager.state_dict()
         return sd
 
     def check_state_dict(self, sd: dict):
@@ -747,6 +838,10 @@ class CaTEnv:
             keys.append("events")
         elif "events" in sd:
             raise ValueError("run state: it carries events, this env has no cfg.events")
+        if getattr(self, "_command_block", None) is not None:
+            keys.append("commands")
+        elif "commands" in sd:
+            raise ValueError("run state: it carries commands, this env has no cfg.commands")
         missing = [k for k in keys if k not in sd]
         if missing:
             raise ValueError(f"run state: the env's part lacks {missing}")
@@ -768,6 +863,8 @@ class CaTEnv:
             self.observation_manager.check_state_dict(sd["observations"])
         if hasattr(self, "event_manager"):
             self.event_manager.check_state_dict(sd["events"])
+        if getattr(self, "_command_block", None) is not None:
+            self.command_manager.check_state_dict(sd["commands"])
 
     def load_state_dict(self, sd: dict):
         """IN PLACE (``copy_`` into the existing tensors, never a rebound attribute): the fused step's argument block, the
@@ -787,6 +884,8 @@ class CaTEnv:
             self.observation_manager.load_state_dict(sd["observations"])
         if hasattr(self, "event_manager"):
             self.event_manager.load_state_dict(sd["events"])
+        if getattr(self, "_command_block", None) is not None:
+            self.command_manager.load_state_dict(sd["commands"])
         self.curriculum_manager.load_state_dict(sd["curriculum"])      # through set_term_cfg: the next launch carries it
 
     # episode control -------------------------------------------------------------------------

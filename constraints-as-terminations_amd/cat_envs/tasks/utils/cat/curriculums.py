@@ -29,3 +29,16 @@ def modify_reward_weight(env, env_ids: Sequence[int], term_name: str, weight: fl
         term_cfg.weight = weight
         manager.set_term_cfg(term_name, term_cfg)
     return float(term_cfg.weight)
+
+
+def modify_command_ranges(env, env_ids: Sequence[int], term_name: str, ranges: dict, num_steps: int):
+    """The command-side counterpart of ``modify_reward_weight`` - this project's own rule, not IsaacLab's or the
+    reference's: once more than ``num_steps`` env steps have run, the command term's ranges are ``ranges`` (a dict with any
+    of ``lin_vel_x``, ``lin_vel_y``, ``ang_vel_z`` -> (lo, hi)).  The new ranges are in the simulator's block before the
+    next launch; a command in flight stays until its next resample.  Returns the upper bound of ``lin_vel_x``, which the
+    curriculum manager logs as ``Curriculum/<name>``."""
+    manager = env.command_manager
+    manager.get_term_cfg(term_name)                 # names the term: an unknown name is an error
+    if env.common_step_counter > num_steps:
+        manager.set_ranges(**{k: tuple(v) for k, v in ranges.items()})
+    return float(manager.ranges["lin_vel_x"][1])

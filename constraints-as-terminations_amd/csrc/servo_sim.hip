@@ -21,6 +21,8 @@ constexpr uint32_t kTagObs = 0x4F42534Eu;                                // "OBS
 constexpr int kRawObs = 45;                                              // the raw observation a policy observation reads
 // "PUSH", "JVEL", "ROOT", "FRIC": the events ("Events")
 constexpr uint32_t kTagPush = 0x50555348u, kTagJvel = 0x4A56454Cu, kTagRoot = 0x524F4F54u, kTagFric = 0x46524943u;
+// "CMDD", "CMDT": command draws and resampling times of the configured command process ("Commands")
+constexpr uint32_t kTagCmdDraw = 0x434D4444u, kTagCmdTime = 0x434D4454u;
 
 // G[k][lane]: the fixed 5 x 12 matrix of the base model (rows vx, vy, wz, roll, pitch)
 __device__ __forceinline__ float gain(int k, int lane) {
@@ -71,6 +73,11 @@ static_assert(offsetof(catppo_servo_sim_obs, obs) == sizeof(catppo_servo_sim) &&
 static_assert(offsetof(catppo_servo_sim_events, obs) == 368 && offsetof(catppo_servo_sim_events, ev) == 384 &&
                   sizeof(catppo_servo_events) == 16 && sizeof(catppo_servo_sim_events) == 400 && CATPPO_SERVO_EVENT_FLOATS == 32,
               "catppo_servo_sim_events: observation and event descriptors behind the 368 bytes");
+static_assert(offsetof(catppo_servo_sim_commands, obs) == 368 && offsetof(catppo_servo_sim_commands, ev) == 384 &&
+                  offsetof(catppo_servo_sim_commands, cmd) == 400 && sizeof(catppo_servo_commands) == 16 &&
+                  offsetof(catppo_servo_commands, floats) == 8 && offsetof(catppo_servo_commands, off_cmd_state) == 12 &&
+                  sizeof(catppo_servo_sim_commands) == 416 && CATPPO_SERVO_COMMAND_FLOATS == 16,
+              "catppo_servo_sim_commands: observation, event and command descriptors behind the 368 bytes");
 
 // command of (env, episode, resample index): uniform in the reference ranges, dead zone, standing fraction; with a
 // fixed-command table the caller's row `e` as it stands, for every episode and resample index - in the step-response
@@ -181,6 +188,50 @@ __device__ __forceinline__ float traction_of(const catppo_servo_sim& d, const Ev
   return mu < 1.f ? mu : 1.f;
 }
 
+// the command block as the wave holds it: wave lane k < 16 has loaded word k, every lane reads word k through readlane, so
+// every branch on a flag is wave-uniform
+struct Commands {
+  uint32_t flags;
+  float dz, p_still, p_move, range[6], rel_standing, T[2];
+};
+
+__device__ __forceinline__ Commands commands_of(float mine) {
+  Commands C;
+  C.flags = (uint32_t)__float_as_int(ev_word(mine, 0));
+  C.dz = ev_word(mine, 1), C.p_still = ev_word(mine, 2), C.p_move = ev_word(mine, 3);
+#pragma unroll
+  for (int i = 0; i < 6; ++i) C.range[i] = ev_word(mine, 4 + i);
+  C.rel_standing = ev_word(mine, 10);
+  C.T[0] = ev_word(mine, 11), C.T[1] = ev_word(mine, 12);
+  return C;
+}
+
+// draw(third): the three commands from words 0..2, the standing decision from word 3
+__device__ __forceinline__ void cmd_draw(const catppo_servo_sim& d, const Commands& C, uint32_t gid, uint32_t ep, uint32_t third,
+                                         float c[3], bool& standing) {
+  const rng::u32x4 r = ev_block(d, gid, ep, third, kTagCmdDraw);
+  c[0] = C.range[0] + rng::uniform_open(r.x) * C.range[1];
+  c[1] = C.range[2] + rng::uniform_open(r.y) * C.range[3];
+  c[2] = C.range[4] + rng::uniform_open(r.z) * C.range[5];
+  standing = rng::uniform_open(r.w) <= C.rel_standing;
+}
+
+// the dead-zone rule: no |c_i| above the dead zone zeroes the command
+__device__ __forceinline__ void cmd_deadzone(const Commands& C, float c[3]) {
+  if (C.flags & CATPPO_SERVO_COMMAND_DEADZONE) {
+    const bool any = fabsf(c[0]) > C.dz || fabsf(c[1]) > C.dz || fabsf(c[2]) > C.dz;
+    if (!any) c[0] = c[1] = c[2] = 0.f;
+  }
+}
+
+// the first command of (env, episode): draw, dead zone, standing
+__device__ __forceinline__ void first_command(const catppo_servo_sim& d, const Commands& C, uint32_t gid, uint32_t ep, float c[3]) {
+  bool standing;
+  cmd_draw(d, C, gid, ep, 0u, c, standing);
+  cmd_deadzone(C, c);
+  if ((C.flags & CATPPO_SERVO_COMMAND_STANDING) && standing) c[0] = c[1] = c[2] = 0.f;
+}
+
 // kMode = kTrain is the launch with all three evaluation pointers NULL: everything they add is compiled out of it, so
 // that a training step runs the code it ran before the fields existed.  kEvaluate: a fixed-command table [N, 3] or an
 // evaluation record, and nothing else - the evaluation that runs inside training keeps the code it had, too.
@@ -197,11 +248,15 @@ __device__ __forceinline__ float traction_of(const catppo_servo_sim& d, const Ev
 // The pack may also hold catppo_servo_events, alone or behind catppo_servo_obs ("Events"): pushes, the
 // first state's reset terms and the traction.  Orthogonal to the rest; only the events-on launch carries that kernel
 // argument, and without it every line it adds is compiled out.  24 instances in all.
+// catppo_servo_commands, last in the pack ("Commands"): the velocity command is the stateful process of the
+// command block instead of command_of's draws, at its three call sites.  Orthogonal to the rest, compiled out without it:
+// 24 more instances, none of which is held to 64 VGPRs.
 template <int kMode, bool kRew, typename... Ext>
 __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeof...(Ext) == 0) ? 8 : 1) void servo_sim_kernel(
     const catppo_servo_sim d, const Ext... ext) {
   constexpr bool kObs = (std::is_same_v<Ext, catppo_servo_obs> || ...);
   constexpr bool kEv = (std::is_same_v<Ext, catppo_servo_events> || ...);
+  constexpr bool kCmd = (std::is_same_v<Ext, catppo_servo_commands> || ...);
   constexpr bool kEval = kMode != kTrain;
   extern __shared__ float4 lds4[];
   float* lds = reinterpret_cast<float*>(lds4);
@@ -210,6 +265,10 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
   float ev_mine = 0.f;
   if constexpr (kEv)
     if ((tid & 63) < CATPPO_SERVO_EVENT_FLOATS) ev_mine = ext_of<catppo_servo_events>(ext...).block[tid & 63];
+  // wave lane k < 16 loads word k of the command block
+  float cmd_mine = 0.f;
+  if constexpr (kCmd)
+    if ((tid & 63) < CATPPO_SERVO_COMMAND_FLOATS) cmd_mine = ext_of<catppo_servo_commands>(ext...).block[tid & 63];
   const int F = d.row_floats, D = d.obs_dim, B3 = d.B * 3;
   const int64_t e0 = (int64_t)blockIdx.x * kEnvsPerBlock;
   // rows past N recompute the last env and are dropped at the store: no divergence around the shuffles and barriers
@@ -229,7 +288,52 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
   const int f = lane & 3, foot_body = 4 * f + 4;
   const float def = isj ? d.default_joint_pos[lane] : 0.f;
   float cmd[3];
-  command_of<kMode>(d, e, gid, ep, (uint32_t)(t / d.resample_steps), t, cmd);
+  // commands on: the time left until the timed resample, what the trace says of this step's update, and whether the
+  // generator runs at all (a fixed-command table wins)
+  Commands CM = {};
+  float cmd_tl = 0.f, cmd_mark = 0.f;
+  bool cmd_gen = true;
+  if constexpr (kCmd) {
+    CM = commands_of(cmd_mine);
+    if constexpr (kMode != kTrain) cmd_gen = d.fixed_command == nullptr;
+    if (!cmd_gen) {
+      if constexpr (kMode != kTrain) command_of<kMode>(d, e, gid, ep, 0u, t, cmd);
+    } else if (rst) {
+      first_command(d, CM, gid, ep, cmd);
+      cmd_tl = CM.T[0] + rng::uniform_open(ev_block(d, gid, ep, 0u, kTagCmdTime).x) * CM.T[1];
+    } else {
+      // the update of IsaacLab's command term, at the start of the step it applies to; D: the step's time block, whose
+      // words 2 and 3 are its two decisions
+      for (int i = 0; i < 3; ++i) cmd[i] = in[d.off_command + i];
+      cmd_tl = in[ext_of<catppo_servo_commands>(ext...).off_cmd_state];
+      const uint32_t third = ((uint32_t)t + 1u) << 1;
+      const rng::u32x4 D = ev_block(d, gid, ep, third, kTagCmdTime);
+      cmd_tl = cmd_tl - d.dt * (float)d.decimation;
+      if (cmd_tl <= 0.f) {
+        bool standing;
+        cmd_draw(d, CM, gid, ep, third, cmd, standing);
+        if ((CM.flags & CATPPO_SERVO_COMMAND_STANDING) && standing) cmd[0] = cmd[1] = cmd[2] = 0.f;
+        cmd_tl = CM.T[0] + rng::uniform_open(D.x) * CM.T[1];
+        cmd_mark = 1.f;
+      }
+      cmd_deadzone(CM, cmd);
+      if (CM.flags & CATPPO_SERVO_COMMAND_RANDOM_RESAMPLE) {
+        const bool still = sqrtf((cmd[0] * cmd[0] + cmd[1] * cmd[1]) + cmd[2] * cmd[2]) < CM.dz;
+        if (rng::uniform_open(D.z) < (still ? CM.p_still : CM.p_move)) {
+          bool standing;
+          cmd_draw(d, CM, gid, ep, third | 1u, cmd, standing);       // meets the dead zone in the next step
+          cmd_tl = CM.T[0] + rng::uniform_open(ev_block(d, gid, ep, third | 1u, kTagCmdTime).x) * CM.T[1];
+          cmd_mark = 1.f;
+        }
+      }
+      if ((CM.flags & CATPPO_SERVO_COMMAND_YAW_FLIP) && rng::uniform_open(D.w) < CM.p_move) {
+        cmd[2] = -cmd[2];
+        cmd_mark = cmd_mark + 2.f;
+      }
+    }
+  } else {
+    command_of<kMode>(d, e, gid, ep, (uint32_t)(t / d.resample_steps), t, cmd);
+  }
   Events E = {};
   if constexpr (kEv) E = events_of(ev_mine);
   float* obs = row + d.off_obs;
@@ -296,6 +400,7 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
         row[d.off_command + k] = cmd[k];
         if (6 + k < D) obs[6 + k] = cmd[k];
       }
+      if constexpr (kCmd) row[ext_of<catppo_servo_commands>(ext...).off_cmd_state] = cmd_gen ? cmd_tl : 0.f;
     }
     if constexpr (kEval)
       if (rec) d.eval[rec_at] = 0.f;
@@ -474,6 +579,8 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
         }
         if constexpr (kEv)
           if (lane == 14) head = pushed ? 1.f : 0.f;
+        if constexpr (kCmd)
+          if (lane == 15) head = cmd_mark;
         tr[lane] = head;
         if (lane < 8) tr[16 + lane] = lane < 4 ? con : fz;      // lanes 0..3 and 4..7 both carry feet 0..3
         if (isj) {
@@ -521,6 +628,7 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
       for (int k = 0; k < 3; ++k) row[d.off_command + k] = cmd[k];
       row[d.off_reward] = kRew ? rsum : reward;
       row[d.off_hard_reset] = fallen ? 1.f : 0.f;
+      if constexpr (kCmd) row[ext_of<catppo_servo_commands>(ext...).off_cmd_state] = cmd_gen ? cmd_tl : 0.f;
     }
     if (lane == 14) {
       for (int k = 0; k < 3; ++k) row[d.off_servo + k] = v[k];
@@ -532,7 +640,12 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
       float head[9] = {ang[0], ang[1], ang[2], grav[0], grav[1], grav[2], cmd[0], cmd[1], cmd[2]};
       if (ends) {
         float cn[3];
-        command_of<kMode>(d, e, gid, ep_out, 0u, 0, cn);
+        if constexpr (kCmd) {
+          if (cmd_gen) first_command(d, CM, gid, ep_out, cn);
+          else if constexpr (kMode != kTrain) command_of<kMode>(d, e, gid, ep_out, 0u, 0, cn);
+        } else {
+          command_of<kMode>(d, e, gid, ep_out, 0u, 0, cn);
+        }
         head[0] = head[1] = head[2] = head[3] = head[4] = 0.f;
         head[5] = -1.f, head[6] = cn[0], head[7] = cn[1], head[8] = cn[2];
         if constexpr (kEv) {
@@ -638,11 +751,15 @@ extern "C" int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* de
   const catppo_servo_sim& d = *desc;
   // reserved names what lies behind the descriptor: nothing, the observation descriptor of a catppo_servo_sim_obs, or the
   // observation and event descriptors of a catppo_servo_sim_events (whose observation descriptor may be empty)
-  CATPPO_CHECK_ARG(ctx, d.reserved == 0 || d.reserved == CATPPO_SERVO_EXT_OBS || d.reserved == CATPPO_SERVO_EXT_EVENTS);
+  // ... or all three of a catppo_servo_sim_commands (whose event descriptor may be empty, too)
+  const bool ext_cmd = d.reserved == CATPPO_SERVO_EXT_COMMANDS;
+  CATPPO_CHECK_ARG(ctx, d.reserved == 0 || d.reserved == CATPPO_SERVO_EXT_OBS || d.reserved == CATPPO_SERVO_EXT_EVENTS || ext_cmd);
   const catppo_servo_obs* obs = d.reserved != 0 ? &reinterpret_cast<const catppo_servo_sim_obs*>(desc)->obs : nullptr;
-  const catppo_servo_events* ev =
-      d.reserved == CATPPO_SERVO_EXT_EVENTS ? &reinterpret_cast<const catppo_servo_sim_events*>(desc)->ev : nullptr;
+  const catppo_servo_events* ev = d.reserved == CATPPO_SERVO_EXT_EVENTS || ext_cmd
+                                      ? &reinterpret_cast<const catppo_servo_sim_events*>(desc)->ev : nullptr;
+  const catppo_servo_commands* cm = ext_cmd ? &reinterpret_cast<const catppo_servo_sim_commands*>(desc)->cmd : nullptr;
   if (ev && obs->width == 0 && obs->table == nullptr) obs = nullptr;
+  if (cm && ev->block == nullptr && ev->floats == 0) ev = nullptr;
   CATPPO_CHECK_ARG(ctx, d.N >= 1 && d.N < (int64_t(1) << 31) && d.env_offset >= 0 && d.env_offset + d.N < (int64_t(1) << 32));
   CATPPO_CHECK_ARG(ctx, d.state_in && d.state_out && d.episode_length);
   CATPPO_CHECK_ARG(ctx, d.init || (d.action && d.reset && d.state_in != d.state_out));
@@ -701,12 +818,34 @@ extern "C" int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* de
     CATPPO_CHECK_ARG(ctx, bl != d.state_in && bl != d.state_out && bl != d.eval && bl != d.trace && bl != d.fixed_command &&
                               bl != d.reward_rec && bl != (const void*)d.reward_table && (!obs || bl != (const void*)obs->table));
   }
+  if (cm) {
+    CATPPO_CHECK_ARG(ctx, d.max_episode_length < (int64_t(1) << 27));
+    CATPPO_CHECK_ARG(ctx, cm->floats == CATPPO_SERVO_COMMAND_FLOATS);
+    // the block is device memory: its writer checks the values (Solo12ServoSim.set_command_block); they are never addresses
+    const void* bl = cm->block;
+    CATPPO_CHECK_ARG(ctx, bl != nullptr && ((uintptr_t)bl % 16) == 0);
+    CATPPO_CHECK_ARG(ctx, bl != d.state_in && bl != d.state_out && bl != d.eval && bl != d.trace && bl != d.fixed_command &&
+                              bl != d.reward_rec && bl != (const void*)d.reward_table && (!obs || bl != (const void*)obs->table) &&
+                              (!ev || bl != (const void*)ev->block));
+    // the state field: four floats of the row on a 16-byte boundary that no other field the kernel writes touches
+    const int64_t cs = cm->off_cmd_state;
+    CATPPO_CHECK_ARG(ctx, cs >= 0 && cs % 4 == 0 && cs + 4 <= d.row_floats);
+    for (const auto& fl : fields) CATPPO_CHECK_ARG(ctx, cs + 4 <= fl.off || cs >= (int64_t)fl.off + fl.width);
+    if (obs) {
+      const int64_t padded = (obs->width + 3) / 4 * 4;
+      CATPPO_CHECK_ARG(ctx, cs + 4 <= obs->off_policy_obs || cs >= obs->off_policy_obs + padded);
+    }
+  }
   const unsigned nblk = (unsigned)cdiv64(d.N, kEnvsPerBlock);
   const size_t lds_bytes = (size_t)d.row_floats * kEnvsPerBlock * sizeof(float);
   const int mode = (d.trace || d.fixed_segments > 1) ? kStepResponse : (d.fixed_command || d.eval) ? kEvaluate : kTrain;
   const bool rew = d.reward_terms > 0;
   const hipStream_t st = static_cast<hipStream_t>(stream);
-  if (obs && ev) launch(mode, rew, nblk, lds_bytes, st, d, *obs, *ev);
+  if (cm && obs && ev) launch(mode, rew, nblk, lds_bytes, st, d, *obs, *ev, *cm);
+  else if (cm && ev) launch(mode, rew, nblk, lds_bytes, st, d, *ev, *cm);
+  else if (cm && obs) launch(mode, rew, nblk, lds_bytes, st, d, *obs, *cm);
+  else if (cm) launch(mode, rew, nblk, lds_bytes, st, d, *cm);
+  else if (obs && ev) launch(mode, rew, nblk, lds_bytes, st, d, *obs, *ev);
   else if (ev) launch(mode, rew, nblk, lds_bytes, st, d, *ev);
   else if (obs) launch(mode, rew, nblk, lds_bytes, st, d, *obs);
   else launch(mode, rew, nblk, lds_bytes, st, d);

@@ -729,7 +729,7 @@ typedef struct catppo_servo_sim {
   const uint8_t* reset;                  /* [N] */
   const int64_t* episode_length;         /* [N], before this step's increment */
   int64_t max_episode_length;
-  int32_t decimation, resample_steps, init, reserved;   /* reserved: 0, CATPPO_SERVO_EXT_OBS or CATPPO_SERVO_EXT_EVENTS (see below) */
+  int32_t decimation, resample_steps, init, reserved;   /* reserved: 0 or one of CATPPO_SERVO_EXT_OBS / _EVENTS / _COMMANDS (see below) */
   uint64_t seed;
   float default_joint_pos[12];
   float dt, kp, kd, inertia, tau_max, action_scale, vel_alpha, tilt_beta, tilt_max, reward_scale, foot_clearance,
@@ -831,6 +831,58 @@ typedef struct catppo_servo_sim_events {
   catppo_servo_obs obs;                   /* width 0 and table NULL: no observation table */
   catppo_servo_events ev;
 } catppo_servo_sim_events;
+
+/* Commands ("Commands").  desc->reserved == CATPPO_SERVO_EXT_COMMANDS: `desc` is the head of a
+ * catppo_servo_sim_commands, i.e. the observation, event and command descriptors lie behind the 368 bytes.  Under this
+ * value obs.width == 0 with a NULL table means "no observation table" and ev.block == NULL with ev.floats == 0 means "no
+ * events"; otherwise both are checked and used exactly as under CATPPO_SERVO_EXT_EVENTS.  0, CATPPO_SERVO_EXT_OBS and
+ * CATPPO_SERVO_EXT_EVENTS keep their meaning.
+ * cmd.block is a DEVICE array of CATPPO_SERVO_COMMAND_FLOATS fp32 words, 16-byte aligned, read by every launch (ranges the
+ * host rewrites in stream order are in the next launch, under graph replay too).  It may alias none of the state buffers,
+ * the records, the trace, the command table or the other tables and blocks.  max_episode_length < 2^27.  Words:
+ *   0 flags (uint32 bits: 1 dead zone, 2 random resample, 4 yaw flip, 8 standing)      1 dz (dead zone)
+ *   2 p_still    3 p_move    4..9 (lo, width) of the commands x y wz    10 rel_standing    11 12 T_lo T_width (seconds)
+ *   13..15 zero
+ * cmd.off_cmd_state names one more 16-byte field of the row (a multiple of 4, disjoint from every other field the kernel
+ * writes): float 0 the time left until the timed resample in seconds, floats 1..3 zero.  The velocity command becomes a
+ * stateful process on (off_command, off_cmd_state) of the input row; the built-in generator ("CMDS", resample_steps,
+ * standing_fraction, command_deadzone) is not evaluated.  A sample is s = lo + u * width (two rounded fp32 operations),
+ * u = uniform in (0, 1) from a word of Philox4x32-10 with key = seed and counter {global env id, episode, third, tag}:
+ *   draw(third)  tag "CMDD": words 0..2 sample x y wz, word 3 gives standing = u <= rel_standing
+ *   time(third)  tag "CMDT": word 0 samples T_lo + u * T_width; words 2 and 3 are the step's two decisions (below)
+ * Rules: dead zone = no |c_i| > dz zeroes the command (+0.f); standing = `standing` zeroes it; each only with its flag.
+ * First command of episode ep (third = 0): c = draw(0), dead zone, standing, tl = time(0).  It serves the init launch
+ * (row, raw observation, cmd_state), a step whose reset flag is set (which runs no update) and the post-reset observation
+ * of a step that ends its episode alike.
+ * Update of a step that starts at episode length t and is not a reset step, third = ((t + 1) << 1) | b, c and tl from the
+ * input row; D = time(b = 0), which every such step draws:
+ *   1. tl = tl - step_dt; if tl <= 0: c = draw(b = 0), standing, tl = D word 0's sample
+ *   2. dead zone
+ *   3. (random resample) still = sqrt((c0 c0 + c1 c1) + c2 c2) < dz; p = still ? p_still : p_move; if u(D word 2) < p:
+ *      c = draw(b = 1), tl = time(b = 1); this command meets the dead zone in the next step
+ *   4. (yaw flip) if u(D word 3) < p_move: c2 = -c2
+ * The update runs at the start of the step it applies to: reward, records, trace and observation of the step see it.
+ * With a fixed-command table the generator is bypassed as without commands and cmd_state is written as zeros.
+ * Float 15 of a trace row is 1.f when the command was redrawn in the step (1. or 3.) plus 2.f when the yaw flipped.
+ * The block's writer checks its values (Solo12ServoSim.set_command_block); whatever it holds the launch stays inside its
+ * row: the words are floats and one flag word, never addresses. */
+#define CATPPO_SERVO_EXT_COMMANDS 0x434D4431   /* "CMD1": value of catppo_servo_sim.reserved that announces catppo_servo_sim_commands */
+#define CATPPO_SERVO_COMMAND_FLOATS 16
+#define CATPPO_SERVO_COMMAND_DEADZONE 1u
+#define CATPPO_SERVO_COMMAND_RANDOM_RESAMPLE 2u
+#define CATPPO_SERVO_COMMAND_YAW_FLIP 4u
+#define CATPPO_SERVO_COMMAND_STANDING 8u
+typedef struct catppo_servo_commands {
+  const float* block;                     /* DEVICE array [CATPPO_SERVO_COMMAND_FLOATS], 16-byte aligned */
+  int32_t floats;                         /* CATPPO_SERVO_COMMAND_FLOATS */
+  int32_t off_cmd_state;                  /* the row's 4-float field: time left | 0 0 0 */
+} catppo_servo_commands;
+typedef struct catppo_servo_sim_commands {
+  catppo_servo_sim sim;                   /* sim.reserved = CATPPO_SERVO_EXT_COMMANDS */
+  catppo_servo_obs obs;                   /* width 0 and table NULL: no observation table */
+  catppo_servo_events ev;                 /* block NULL and floats 0: no events */
+  catppo_servo_commands cmd;
+} catppo_servo_sim_commands;
 
 /* ---- test hook (ABI 0.6) ------------------------------------------------------------------------------------------
  * buf != NULL ([2][M] int32, device): the head / loss kernel of every following catppo_ppo_minibatch_* call writes the clip

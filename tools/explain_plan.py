@@ -6,7 +6,14 @@
 Runs ONE rollout forward (catppo_policy_step on `--envs` rows) and ONE optimiser step
 (catppo_ppo_minibatch_step_packed on `--minibatch` rows) on random data with catppo_plan_log switched on and prints what
 the library's dispatch code wrote at its decision sites: kernel, grid, and the rule that selected it.  `--all` walks the
-BASELINE shapes (profiles/r5_explain_plan.txt is this output)."""
+BASELINE shapes (profiles/r5_explain_plan.txt is this output).
+
+    python tools/explain_plan.py --task Isaac-Velocity-CaT-Flat-Solo12-Servo-Reference-v0        (needs no device)
+
+names the instance of the servo simulator's kernel a task's training step launches: which of ``cfg.rewards``,
+``cfg.observations``, ``cfg.events`` and ``cfg.commands`` (``RewardsCfg``, ``ObservationsCfg``, ``EventCfg``, ``CommandsCfg``) the
+cfg carries decides the kernel's template pack (csrc/servo_sim.hip).  The servo tasks are
+``...-Solo12-Servo-v0`` and its ``-Rewards``, ``-Obs``, ``-Events``, ``-Full``, ``-Commands`` and ``-Reference`` variants."""
 import argparse
 import os
 import sys
@@ -54,6 +61,28 @@ def explain(obs, act, hidden, envs, mb, precision="fp32"):
     return "\n".join(out)
 
 
+def explain_task(task):
+    """the servo simulator's kernel instance of a task's training step, from its cfg alone"""
+    import cat_envs.tasks  # noqa: F401
+    from cat_envs.shim import load_cfg_from_registry
+    cfg = load_cfg_from_registry(task, "env_cfg_entry_point")
+    if str(getattr(cfg.synthetic, "kind", "stream")) != "servo":
+        return f"== {task}: the stream simulator (no simulator kernel; the state is a pre-generated stream)"
+    has = {k: getattr(cfg, k, None) is not None for k in ("rewards", "observations", "events", "commands")}
+    pack = [name for key, name in (("observations", "catppo_servo_obs"), ("events", "catppo_servo_events"),
+                                   ("commands", "catppo_servo_commands")) if has[key]]
+    row = 308 + (48 if has["observations"] else 0) + (4 if has["commands"] else 0)
+    out = [f"== {task}: " + ", ".join(f"cfg.{k} {'set' if v else 'unset'}" for k, v in has.items()),
+           f"servo_sim_kernel<kTrain, {'true' if has['rewards'] else 'false'}{''.join(', ' + n for n in pack)}>: row of {row} floats "
+           f"(with the reference's 45-float policy observation), {row * 64} bytes of LDS per workgroup"]
+    if has["commands"]:
+        from cat_envs.tasks.utils.mdp import command_manager as KM
+        b = KM.build_block(cfg.commands, cfg.sim.dt, cfg.episode_length_s)
+        out.append(f"command term '{b['name']}' ({b['class']}): flags {b['flags']:#x}, p_still {b['p_still']:g}, p_move {b['p_move']:g}, "
+                   f"ranges {b['bounds']}, resampling {b['time']} s; inert: {', '.join(b['inert']) or 'none'}")
+    return "\n".join(out)
+
+
 BASELINE = [
     ("cfg1: 64 envs, 2 terms, reference MLP", 48, 12, (512, 256, 128), 64, 512, "fp32"),
     ("cfg2: the bench default", 48, 12, (256, 256, 256), 4096, 16384, "fp32"),
@@ -73,8 +102,11 @@ if __name__ == "__main__":
     ap.add_argument("--minibatch", type=int, default=16384)
     ap.add_argument("--precision", default="fp32", choices=("fp32", "bf16", "bf16x3"))
     ap.add_argument("--all", action="store_true")
+    ap.add_argument("--task", default=None, help="name the servo simulator's kernel instance of this task (needs no device)")
     a = ap.parse_args()
-    if a.all:
+    if a.task:
+        print(explain_task(a.task))
+    elif a.all:
         for name, *spec in BASELINE:
             print("#", name)
             print(explain(*spec))

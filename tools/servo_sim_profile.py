@@ -20,6 +20,12 @@ launch is the events-on training instance.  The reference's push probability is 
 0.01 (the term's ``probability`` param) so that every one of the 240 launches pushes some envs - about 41 of 4096, 328 of
 32768 - and the pushed branch is part of what is timed.  profiles/servo_events_kernel_stats.csv: the parent's library, this
 library without the flag and this library with --events, alternating in one session, every run listed.
+--commands runs the task with the reference's command block (Isaac-Velocity-CaT-Flat-Solo12-Servo-Commands-v0), so that the
+simulator's launch is the commands-on training instance.  The reference's p_move is 0.0005 per env and step; the arm raises it to
+0.01 (the term's ``p_move`` field) so that every one of the 240 launches redraws the command of some envs - about 41 of 4096, 328
+of 32768 - and flips the yaw of as many, and the redraw branch is part of what is timed.
+profiles/servo_commands_kernel_stats.csv: the parent's library, this library without the flag and this library with --commands,
+alternating in one session, every run listed.
 
 Per env step the trace shows servo_sim_kernel (the simulator), the two launches of catppo_rollout_pre, the one of
 catppo_rollout_post and the policy forward."""
@@ -43,15 +49,17 @@ def main():
     ap.add_argument("--rewards", action="store_true", help="the task with ShapedRewardsCfg: reward terms inside the simulator launch")
     ap.add_argument("--obs", action="store_true", help="the task with ObservationsCfg: observation terms inside the simulator launch")
     ap.add_argument("--events", action="store_true", help="the task with EventCfg (push probability 0.01): events inside the simulator launch")
+    ap.add_argument("--commands", action="store_true", help="the task with CommandsCfg (p_move 0.01): the command term inside the simulator launch")
     a = ap.parse_args()
-    if a.obs + a.rewards + a.events > 1:
-        ap.error("--obs, --rewards and --events are separate arms")
+    if a.obs + a.rewards + a.events + a.commands > 1:
+        ap.error("--obs, --rewards, --events and --commands are separate arms")
     import cat_envs.tasks  # noqa: F401
     from cat_envs.shim import load_cfg_from_registry, make
     from cat_envs.tasks.utils.cleanrl.ppo import PPOTrainer
     task = ("Isaac-Velocity-CaT-Flat-Solo12-Servo-Rewards-v0" if a.rewards else
             "Isaac-Velocity-CaT-Flat-Solo12-Servo-Obs-v0" if a.obs else
-            "Isaac-Velocity-CaT-Flat-Solo12-Servo-Events-v0" if a.events else "Isaac-Velocity-CaT-Flat-Solo12-Servo-v0")
+            "Isaac-Velocity-CaT-Flat-Solo12-Servo-Events-v0" if a.events else
+            "Isaac-Velocity-CaT-Flat-Solo12-Servo-Commands-v0" if a.commands else "Isaac-Velocity-CaT-Flat-Solo12-Servo-v0")
     env_cfg = load_cfg_from_registry(task, "env_cfg_entry_point")
     if a.rewards:
         from cat_envs.tasks.locomotion.velocity.config.solo12.cat_flat_env_cfg import ShapedRewardsCfg
@@ -59,6 +67,8 @@ def main():
     if a.events:
         push = env_cfg.events.push_robot
         push.params = {**push.params, "probability": 0.01}
+    if a.commands:
+        env_cfg.commands.base_velocity.p_move = 0.01
     agent_cfg = load_cfg_from_registry(task, "clean_rl_cfg_entry_point")
     env_cfg.scene.num_envs = a.num_envs
     agent_cfg.minibatch_size = min(agent_cfg.minibatch_size, a.num_envs * agent_cfg.num_steps)
@@ -96,6 +106,11 @@ def main():
     if a.events:
         em = env_u.event_manager
         print(f"events: {em.active_terms}, push probability {em.block['p']:g}, |v| mean {float(env_u.sim.view('servo')[:, 0:3].abs().mean()):.4f}")
+    if a.commands:
+        km, sim = env_u.command_manager, env_u.sim
+        zero = (sim.view("command") == 0).all(1).float().mean()
+        print(f"commands: {km.active_terms}, p_move {km.block['p_move']:g}, row of {sim.F} floats, zero commands {float(zero):.4f}, "
+              f"mean time left {float(sim.view('cmd_state')[:, 0].mean()):.3f} s")
     if a.eval or a.trace:
         steps = record[:, 0].cpu()
         assert float(steps.min()) == float(steps.max()) == a.rollouts * trainer.T, (float(steps.min()), float(steps.max()))
