@@ -216,6 +216,33 @@ class ServoSimCommands(ServoSimEvents):
     _fields_ = [("cmd", ServoCommands)]
 
 
+SERVO_EXT_TERMINATIONS = 0x54524D31     # CATPPO_SERVO_EXT_TERMINATIONS: ``reserved`` of a descriptor followed by obs, events, commands and terminations
+SERVO_TERM_FLOATS = 16                  # CATPPO_SERVO_TERM_FLOATS: per-term counts of the ended episodes 0..14 | their number
+SERVO_TERM_MAX_TERMS = 15               # CATPPO_SERVO_TERM_MAX_TERMS
+#: kinds of the servo surrogate's termination terms (include/catppo.h, "Terminations"): name -> catppo_servo_term_entry.kind
+SERVO_TERM_KINDS = {"time_out": 1, "illegal_contact": 2, "upside_down": 3, "bad_orientation": 4,
+                    "root_height_below_minimum": 5, "joint_pos_out_of_manual_limit": 6, "joint_vel_out_of_manual_limit": 7,
+                    "rolled_over": 8}
+
+
+class ServoTermEntry(C.Structure):
+    """catppo_servo_term_entry: one entry of the device-resident termination table"""
+    _fields_ = [("kind", C.c_int32), ("mask", C.c_uint32), ("p0", C.c_float), ("p1", C.c_float)]
+
+
+class ServoTerminations(C.Structure):
+    """catppo_servo_terminations: the termination descriptor; ``table`` is a device array of ``terms`` ``ServoTermEntry``,
+    ``rec`` the device record [N, ``SERVO_TERM_FLOATS``], ``off_term_state`` the row's 4-float field (fired terms | 0 0 0)"""
+    _fields_ = [("table", C.c_void_p), ("rec", C.c_void_p), ("terms", C.c_int32), ("off_term_state", C.c_int32)]
+
+
+class ServoSimTerminations(ServoSimCommands):
+    """catppo_servo_sim_terminations: catppo_servo_sim, a ``ServoObs``, a ``ServoEvents``, a ``ServoCommands`` (a NULL block
+    and ``floats`` 0: no commands) and a ``ServoTerminations`` behind it; the library reads all four while ``reserved`` is
+    ``SERVO_EXT_TERMINATIONS``"""
+    _fields_ = [("term", ServoTerminations)]
+
+
 F32, F16, F64 = 0, 1, 2                 # CATPPO_F32 / _F16 / _F64
 SUM, MAX = 0, 1                         # CATPPO_SUM / _MAX
 LR_FIXED, LR_LINEAR, LR_KEEP = 0, 1, 2
@@ -824,6 +851,8 @@ class Native:
             raise TypeError("servo_sim_step: a descriptor whose 'reserved' announces events must be a native.ServoSimEvents")
         if desc.reserved == SERVO_EXT_COMMANDS and not isinstance(desc, ServoSimCommands):   # ... and a catppo_servo_commands
             raise TypeError("servo_sim_step: a descriptor whose 'reserved' announces commands must be a native.ServoSimCommands")
+        if desc.reserved == SERVO_EXT_TERMINATIONS and not isinstance(desc, ServoSimTerminations):   # ... and a catppo_servo_terminations
+            raise TypeError("servo_sim_step: a descriptor whose 'reserved' announces terminations must be a native.ServoSimTerminations")
         rc = self.lib.catppo_servo_sim_step(self.h, C.byref(desc), self._stream())
         if rc:
             self._ok(rc)

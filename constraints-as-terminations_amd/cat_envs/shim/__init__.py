@@ -8,6 +8,6 @@ registry replacing ``gym.register`` / ``gym.make`` / ``load_cfg_from_registry``.
 """
 from .configclass import MISSING, configclass  # noqa: F401
 from .managers import (AdditiveUniformNoiseCfg, CurriculumTermCfg, EventTermCfg, ManagerBase, ManagerTermBase,  # noqa: F401
-                       ManagerTermBaseCfg, ObservationGroupCfg, ObservationTermCfg, RewardTermCfg, SceneEntityCfg)
+                       ManagerTermBaseCfg, ObservationGroupCfg, ObservationTermCfg, RewardTermCfg, SceneEntityCfg, TerminationTermCfg)
 from .registry import (apply_overrides, hydra_task_config, load_cfg_from_registry, make, register,  # noqa: F401
                        registry)

@@ -14,6 +14,7 @@ try:  # pragma: no cover
     from isaaclab.managers.manager_term_cfg import RewardTermCfg  # type: ignore
     from isaaclab.managers.manager_term_cfg import ObservationGroupCfg, ObservationTermCfg  # type: ignore
     from isaaclab.managers.manager_term_cfg import EventTermCfg  # type: ignore
+    from isaaclab.managers.manager_term_cfg import TerminationTermCfg  # type: ignore
     from isaaclab.utils.noise import AdditiveUniformNoiseCfg  # type: ignore
     HAVE_ISAACLAB = True
 except Exception:
@@ -46,6 +47,11 @@ except Exception:
         mode: str = MISSING
         interval_range_s: Any = None
         is_global_time: bool = False
+
+    @configclass
+    class TerminationTermCfg(ManagerTermBaseCfg):
+        """IsaacLab's DoneTerm: ``time_out`` marks the term whose firing is a truncation, not a termination"""
+        time_out: bool = False
 
     @configclass
     class ObservationGroupCfg:

@@ -100,3 +100,21 @@ for _name, _cfg in (("Commands", "Solo12ServoCommandsFlatEnvCfg"), ("Reference",
         disable_env_checker=True,
         kwargs={"env_cfg_entry_point": f"{__name__}.cat_flat_env_cfg:{_cfg}_PLAY", **_KW},
     )
+
+# the servo task with a TerminationsCfg: the reference's termination terms inside the simulator's launch (DESIGN section 9,
+# "Terminations"); "Reference-Terminations" is every MDP block of the reference's cfg together (the "Reference" task keeps its
+# four blocks and its row)
+for _name, _cfg in (("Terminations", "Solo12ServoTerminationsFlatEnvCfg"),
+                    ("Reference-Terminations", "Solo12ServoReferenceTerminationsFlatEnvCfg")):
+    register(
+        id=f"Isaac-Velocity-CaT-Flat-Solo12-Servo-{_name}-v0",
+        entry_point=CaTEnv,
+        disable_env_checker=True,
+        kwargs={"env_cfg_entry_point": f"{__name__}.cat_flat_env_cfg:{_cfg}", **_KW},
+    )
+    register(
+        id=f"Isaac-Velocity-CaT-Flat-Solo12-Servo-{_name}-Play-v0",
+        entry_point=CaTEnv,
+        disable_env_checker=True,
+        kwargs={"env_cfg_entry_point": f"{__name__}.cat_flat_env_cfg:{_cfg}_PLAY", **_KW},
+    )

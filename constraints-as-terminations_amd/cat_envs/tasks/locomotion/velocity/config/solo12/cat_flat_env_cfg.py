@@ -13,6 +13,8 @@ or any other block of ``mdp.rewards`` terms is evaluated inside the simulator's 
 values) likewise (``Solo12ServoEventsFlatEnvCfg``, DESIGN section 9 "Events"); ``Solo12ServoFullFlatEnvCfg`` puts the three
 blocks together.  Commands: ``CommandsCfg`` (the reference's ``UniformVelocityCommandWithDeadzoneCfg`` and values) likewise
 (``Solo12ServoCommandsFlatEnvCfg``, DESIGN section 9 "Commands"); ``Solo12ServoReferenceFlatEnvCfg`` is all four blocks.
+Terminations: ``TerminationsCfg`` (the reference's three terms and values) likewise (``Solo12ServoTerminationsFlatEnvCfg``,
+DESIGN section 9 "Terminations"); ``Solo12ServoReferenceTerminationsFlatEnvCfg`` is all five blocks.
 """
 import math
 
@@ -23,9 +25,10 @@ from cat_envs.shim import ObservationGroupCfg as ObsGroup
 from cat_envs.shim import ObservationTermCfg as ObsTerm
 from cat_envs.shim import RewardTermCfg as RewTerm
 from cat_envs.shim import SceneEntityCfg, configclass
+from cat_envs.shim import TerminationTermCfg as DoneTerm
 from cat_envs.tasks.utils.cat import constraints, curriculums
 from cat_envs.tasks.utils.cat.manager_constraint_cfg import ConstraintTermCfg as ConstraintTerm
-from cat_envs.tasks.utils.mdp import commands, events, observations, rewards
+from cat_envs.tasks.utils.mdp import commands, events, observations, rewards, terminations
 
 ALL_JOINTS = [".*_HAA", ".*_HFE", ".*_KFE"]
 
@@ -381,6 +384,46 @@ class Solo12ServoReferenceFlatEnvCfg_PLAY(Solo12ServoReferenceFlatEnvCfg):
 
     def __post_init__(self):
         self.observations.policy.enable_corruption = False
+
+
+@configclass
+class TerminationsCfg:
+    """the reference's termination block (solo12/cat_flat_env_cfg.py TerminationsCfg): three terms and their values"""
+    time_out = DoneTerm(func=terminations.time_out, time_out=True)
+    base_contact = DoneTerm(func=terminations.illegal_contact,
+                            params={"sensor_cfg": SceneEntityCfg("contact_forces", body_names=["base_link", ".*_UPPER_LEG"]),
+                                    "threshold": 1.0})
+    upside_down = DoneTerm(func=terminations.upside_down, params={"limit": 0.1})
+
+
+@configclass
+class BuiltinTerminationsCfg:
+    """what ends an episode of the servo task without a termination block, said as one: the time-out and the roll-over flag"""
+    time_out = DoneTerm(func=terminations.time_out, time_out=True)
+    rolled_over = DoneTerm(func=terminations.rolled_over)
+
+
+@configclass
+class Solo12ServoTerminationsFlatEnvCfg(Solo12ServoFlatEnvCfg):
+    """the servo task with a configurable termination block: the simulator's launch evaluates ``terminations``' terms"""
+    terminations: TerminationsCfg = TerminationsCfg()
+
+
+@configclass
+class Solo12ServoTerminationsFlatEnvCfg_PLAY(Solo12ServoTerminationsFlatEnvCfg):
+    scene: SceneCfg = SceneCfg(num_envs=50, env_spacing=3.0)
+    curriculum: object = None
+
+
+@configclass
+class Solo12ServoReferenceTerminationsFlatEnvCfg(Solo12ServoReferenceFlatEnvCfg):
+    """rewards, observations, events, commands and terminations: every MDP block of the reference's cfg"""
+    terminations: TerminationsCfg = TerminationsCfg()
+
+
+@configclass
+class Solo12ServoReferenceTerminationsFlatEnvCfg_PLAY(Solo12ServoReferenceFlatEnvCfg_PLAY):
+    terminations: TerminationsCfg = TerminationsCfg()
 
 
 @configclass

@@ -184,12 +184,15 @@ class Solo12ServoSim(SyntheticSolo12Sim):
 
     def __init__(self, num_envs: int, obs_dim: int, device, seed: int, syn, dt: float, decimation: int,
                  max_episode_length: int, episode_length: torch.Tensor, reset: torch.Tensor, env_offset: int = 0,
-                 policy_obs_dim: int = 0, events: bool = False, commands: bool = False):
+                 policy_obs_dim: int = 0, events: bool = False, commands: bool = False, terminations: bool = False):
         """``policy_obs_dim`` = P > 0: the row gets a second observation field ``policy_obs`` of P floats (padded to a
         multiple of 4) that ``set_observation_table`` configures; the raw field ``obs`` stays what it is.
         ``events``: the descriptor carries the event descriptor, too, and ``set_event_block`` configures it.
         ``commands``: the row gets one more 16-byte field ``cmd_state`` behind everything else (float 0: the time left until
-        the timed resample), the descriptor carries the command descriptor and ``set_command_block`` configures it"""
+        the timed resample), the descriptor carries the command descriptor and ``set_command_block`` configures it.
+        ``terminations``: the row gets one more 16-byte field ``term_state`` behind everything else (float 0: the terms that
+        fired in the step, bit k = term k), the descriptor carries the termination descriptor and
+        ``set_termination_table`` configures it"""
         self.N, self.D, self.device = num_envs, obs_dim, torch.device(device)
         self.P = int(policy_obs_dim)
         if self.P and not (1 <= self.P <= native.SERVO_OBS_MAX_WIDTH and obs_dim == native.SERVO_OBS_RAW):
@@ -212,6 +215,9 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         if commands:
             self.off["cmd_state"] = (self.F, 4)
             self.F += 4
+        if terminations:
+            self.off["term_state"] = (self.F, 4)
+            self.F += 4
         self.cur = torch.zeros(num_envs, self.F, device=self.device)
         self._slabs = [torch.zeros(num_envs, self.F, device=self.device) for _ in range(2)]
         self.cursor = -1
@@ -219,7 +225,8 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         self._episode_length, self._reset = episode_length, reset       # referenced by the descriptor: keep alive
         self._nat = native.get(self.device)
         # with a policy observation the descriptor carries the observation descriptor behind its 368 bytes
-        d = self._desc = (native.ServoSimCommands() if commands else native.ServoSimEvents() if events
+        d = self._desc = (native.ServoSimTerminations() if terminations
+                          else native.ServoSimCommands() if commands else native.ServoSimEvents() if events
                           else native.ServoSimObs() if self.P else native.ServoSimRewards())
         d.N, d.env_offset, d.row_stride, d.row_floats = num_envs, int(env_offset), self.F, self.F
         d.obs_dim, d.H, d.B = obs_dim, H, B
@@ -243,6 +250,9 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         self._event_block, self._event_words = None, None               # device block of the event descriptor, its host copy
         self._commands = bool(commands)
         self._command_block, self._command_words = None, None           # likewise, of the command descriptor
+        self._terminations = bool(terminations)
+        self._term_table = self._term_record = None                     # device table and record of the termination descriptor
+        self._term_entries = []
         self._build_scene()
 
     def _table(self, t, width, what, lead=()):
@@ -411,7 +421,8 @@ class Solo12ServoSim(SyntheticSolo12Sim):
 
     def _announce(self):
         """``reserved`` names the descriptors behind the 368 bytes that are configured by now"""
-        self._desc.reserved = (native.SERVO_EXT_COMMANDS if self._command_block is not None
+        self._desc.reserved = (native.SERVO_EXT_TERMINATIONS if self._term_table is not None
+                               else native.SERVO_EXT_COMMANDS if self._command_block is not None
                                else native.SERVO_EXT_EVENTS if self._event_block is not None
                                else native.SERVO_EXT_OBS if self._obs_table is not None else 0)
 
@@ -452,6 +463,49 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         else:
             self._command_block.copy_(torch.from_numpy(words.copy()))
         self._command_words = words.copy()
+
+    def set_termination_table(self, entries):
+        """``entries``: 1 to 15 ``(kind, mask, p0, p1)`` (``native.SERVO_TERM_KINDS``; what the terms of ``mdp.terminations``
+        describe).  Every following step decides with them when an episode is over, writes the fired terms into the row's
+        ``term_state`` and counts them at episode ends in ``termination_record`` [N, 16], inside the simulator's own launch.
+        The table lives on the device and is rewritten here and nowhere else, in stream order: new params are in the next
+        launch.  Kinds, masks and the number of entries are fixed by the first call.  The entries are checked here - the
+        library cannot read them."""
+        if not self._terminations:
+            raise ValueError("this simulator was built without a termination descriptor (terminations = False)")
+        entries = [(int(k), int(m), float(p0), float(p1)) for k, m, p0, p1 in (entries or [])]
+        if not 1 <= len(entries) <= native.SERVO_TERM_MAX_TERMS:
+            raise ValueError(f"{len(entries)} termination terms: the simulator evaluates 1 .. {native.SERVO_TERM_MAX_TERMS}")
+        for k, m, p0, p1 in entries:
+            if not 1 <= k <= 8:
+                raise ValueError(f"unknown termination kind {k}")
+            if not (math.isfinite(p0) and math.isfinite(p1)):
+                raise ValueError(f"termination kind {k}: params must be finite, got {p0}, {p1}")
+            if k == 2 and not (m != 0 and (m & ~0x1FFFF) == 0):
+                raise ValueError(f"termination kind {k} needs a body mask in 1 .. 0x1FFFF, got {m:#x}")
+            if k in (6, 7) and not (m != 0 and (m & ~0xFFF) == 0):
+                raise ValueError(f"termination kind {k} needs a joint mask in 1 .. 0xFFF, got {m:#x}")
+            if k == 6 and p1 < p0:
+                raise ValueError(f"termination kind 6 needs p0 <= p1, got {p0} > {p1}")
+        if self._term_entries and [e[:2] for e in entries] != [e[:2] for e in self._term_entries]:
+            raise ValueError("the termination table's kinds and masks are fixed by the first call; only params may change")
+        host = (native.ServoTermEntry * native.SERVO_TERM_MAX_TERMS)()
+        for i, (k, m, p0, p1) in enumerate(entries):
+            host[i].kind, host[i].mask, host[i].p0, host[i].p1 = k, m, p0, p1
+        if self._term_table is None:
+            self._term_table = torch.zeros(C.sizeof(host), dtype=torch.uint8, device=self.device)
+            self._term_record = torch.zeros(self.N, native.SERVO_TERM_FLOATS, device=self.device)
+            t = self._desc.term
+            t.table, t.rec = self._term_table.data_ptr(), self._term_record.data_ptr()
+            t.terms, t.off_term_state = len(entries), self.off["term_state"][0]
+            self._announce()                                            # from now on every launch evaluates the table
+        self._term_table.copy_(torch.frombuffer(bytearray(host), dtype=torch.uint8))
+        self._term_entries = entries
+
+    @property
+    def termination_record(self):
+        """[N, 16] fp32 or None: 0..14 how many ended episodes had term k set in their last step | 15 the ended episodes"""
+        return self._term_record
 
     @property
     def command_words(self):
@@ -630,6 +684,15 @@ class CaTEnv:
             from cat_envs.tasks.utils.mdp import command_manager as KM
             self._command_block = KM.build_block(cfg.commands, cfg.sim.dt, cfg.episode_length_s)
             self._check_command_names(self._command_block["name"])
+        # cfg.terminations: when an episode is over is IsaacLab's termination block, evaluated inside the simulator's launch
+        # ("Terminations"); without it the surrogate's own roll-over flag and the time-out end episodes
+        self._term_table = None
+        if getattr(cfg, "terminations", None) is not None:
+            if kind != "servo":
+                raise TypeError("cfg.terminations needs the closed-loop simulator (SyntheticCfg.kind = 'servo'): the termination "
+                                "terms are evaluated inside its launch; the stream simulator's resets are a pre-generated stream")
+            from cat_envs.tasks.utils.mdp import terminations as TM
+            self._term_table = TM.build_table(cfg.terminations, SOLO12_JOINTS, SOLO12_BODIES)
         if kind == "stream":
             self.sim = SyntheticSolo12Sim(self.num_envs, self.obs_dim, self.device, seed + int(syn.seed_offset),
                                           int(syn.stream_steps))
@@ -656,7 +719,8 @@ class CaTEnv:
                                       cfg.sim.dt, cfg.decimation, self.max_episode_length, self.episode_length_buf,
                                       self.reset_buf, env_offset=int(getattr(cfg.scene, "env_offset", 0) or 0),
                                       policy_obs_dim=self.obs_dim if self._obs_table is not None else 0,
-                                      events=self._event_block is not None, commands=self._command_block is not None)
+                                      events=self._event_block is not None, commands=self._command_block is not None,
+                                      terminations=self._term_table is not None)
             self.scene = self.sim.scene
         self.obs_buf = {"policy": self.sim.view(self._obs_field)}
         self._rstep = None
@@ -722,6 +786,10 @@ class CaTEnv:
             self.event_manager = EventManager(self.cfg.events, self, self._event_block,
                                               interval_enabled=bool(getattr(self.cfg, "pushes", True)))
             print("[INFO] Event Manager: ", self.event_manager)
+        if self._term_table is not None:
+            from cat_envs.tasks.utils.mdp.termination_manager import TerminationManager
+            self.termination_manager = TerminationManager(self.cfg.terminations, self, self._term_table)
+            print("[INFO] Termination Manager: ", self.termination_manager)
 
     # evaluation ------------------------------------------------------------------------------
     def _servo_sim(self) -> Solo12ServoSim:
@@ -800,6 +868,8 @@ class CaTEnv:
             fp["event_terms"] = self.event_manager.fingerprint()
         if getattr(self, "_command_block", None) is not None:          # likewise
             fp["command_terms"] = self.command_manager.fingerprint()
+        if getattr(self, "_term_table", None) is not None:             # likewise
+            fp["termination_terms"] = self.termination_manager.fingerprint()
         return fp
 
     def state_dict(self) -> dict:
@@ -819,6 +889,8 @@ class CaTEnv:
             sd["events"] = self.event_manager.state_dict()
         if getattr(self, "_command_block", None) is not None:          # command and time left are part of the simulator's ``cur``; the ranges are not
             sd["commands"] = self.command_manager.state_dict()
+        if getattr(self, "_term_table", None) is not None:             # the record of the ended episodes and the current params
+            sd["terminations"] = self.termination_manager.state_dict()
         return sd
 
     def check_state_dict(self, sd: dict):
@@ -842,6 +914,10 @@ class CaTEnv:
             keys.append("commands")
         elif "commands" in sd:
             raise ValueError("run state: it carries commands, this env has no cfg.commands")
+        if getattr(self, "_term_table", None) is not None:
+            keys.append("terminations")
+        elif "terminations" in sd:
+            raise ValueError("run state: it carries terminations, this env has no cfg.terminations")
         missing = [k for k in keys if k not in sd]
         if missing:
             raise ValueError(f"run state: the env's part lacks {missing}")
@@ -865,6 +941,8 @@ class CaTEnv:
             self.event_manager.check_state_dict(sd["events"])
         if getattr(self, "_command_block", None) is not None:
             self.command_manager.check_state_dict(sd["commands"])
+        if getattr(self, "_term_table", None) is not None:
+            self.termination_manager.check_state_dict(sd["terminations"])
 
     def load_state_dict(self, sd: dict):
         """IN PLACE (``copy_`` into the existing tensors, never a rebound attribute): the fused step's argument block, the
@@ -886,6 +964,8 @@ class CaTEnv:
             self.event_manager.load_state_dict(sd["events"])
         if getattr(self, "_command_block", None) is not None:
             self.command_manager.load_state_dict(sd["commands"])
+        if getattr(self, "_term_table", None) is not None:
+            self.termination_manager.load_state_dict(sd["terminations"])
         self.curriculum_manager.load_state_dict(sd["curriculum"])      # through set_term_cfg: the next launch carries it
 
     # episode control -------------------------------------------------------------------------

@@ -213,6 +213,7 @@ class EvalResult:
     trace_fields: tuple = TRACE_FIELDS
     segment_steps: int | None = None              # control steps per segment when ``commands`` is a schedule
     pushes: bool = False                          # the env has cfg.events and ran with its interval events on
+    termination_share: dict | None = None         # envs with cfg.terminations: {term: share of the ended episodes it ended}
 
     def push_recovery(self, tolerance: float = 0.1) -> list:
         """``push_recovery`` of this evaluation's trace (needs a trace)"""
@@ -256,6 +257,8 @@ class EvalResult:
         if self.trace is not None and self.pushes:
             rows = self.push_recovery()
             d["push_recovery"] = {"summary": summarise_push_recovery(rows), "pushes": rows}
+        if self.termination_share is not None:
+            d["termination_share"] = dict(self.termination_share)
         return json.dumps(d)
 
 
@@ -288,7 +291,11 @@ def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool 
     not observations: the noise reaches them only through the actions the policy takes on what it sees.
 
     ``pushes`` (envs with ``cfg.events``): None leaves the env's interval-event switch as it is; a bool sets it for the
-    evaluation and puts it back afterwards, also when the roll-out raises.  Reset and startup terms stay as configured."""
+    evaluation and puts it back afterwards, also when the roll-out raises.  Reset and startup terms stay as configured.
+
+    On an env with ``cfg.terminations`` the result carries ``termination_share``: per term, the share of the episodes that
+    ended during the evaluation whose last step had the term set (the termination manager's record, which the reset zeroes
+    and this call pops; empty when no episode ended).  Without the block the result is what it was."""
     import contextlib
     import torch
     from cat_envs.tasks.utils.cleanrl.ppo import Agent
@@ -394,4 +401,8 @@ def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool 
                      violations=viol.cpu().numpy(), term_names=names, trace=None if trace is None else trace.cpu().numpy(),
                      segment_steps=segment_steps if lead else None, pushes=pushes_on)
     res.metrics = res._aggregate()
+    tm = getattr(u, "termination_manager", None)
+    if tm is not None:
+        log = tm.pop_log() or {}
+        res.termination_share = {k.split("/", 1)[1]: float(v) for k, v in log.items()}
     return res

@@ -255,6 +255,8 @@ def make_eval_env_cfg(env_cfg, eval_envs: int):
             group.enable_corruption = False
     if getattr(cfg, "events", None) is not None:  # ... and without pushes, randomised first states or traction, likewise
         cfg.events = None
+    if getattr(cfg, "terminations", None) is not None:   # ... and with the built-in episode ends, whatever the block says
+        cfg.terminations = None
     return cfg
 
 

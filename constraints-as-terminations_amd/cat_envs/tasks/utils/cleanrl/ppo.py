@@ -1107,6 +1107,9 @@ class PPOTrainer:
         # runs log rank 0's shard; every rank pops, so that every shard's ended sums cover the same iterations)
         rm = getattr(self.envs.unwrapped, "reward_manager", None)
         reward_log = rm.pop_log() if rm is not None else None
+        # ... and how the ended episodes of a configured termination block ended, likewise
+        tm = getattr(self.envs.unwrapped, "termination_manager", None)
+        termination_log = tm.pop_log() if tm is not None else None
         if self.lr_schedule == "adaptive":
             self.lr = float(self.nat.iter_state_read(self.state).lr)
         n_upd = max(d[7], 1.0)
@@ -1122,6 +1125,8 @@ class PPOTrainer:
             w.add_scalar("Loss/mean_surrogate_loss", stats["mean_surrogate_loss"], it)
             w.add_scalar("Loss/learning_rate", self.lr, it)
             for key, value in (reward_log or {}).items():        # "Episode_Reward/<term>"
+                w.add_scalar(key, value, it)
+            for key, value in (termination_log or {}).items():   # "Episode_Termination/<term>"
                 w.add_scalar(key, value, it)
         if self.run_path is not None and self.rank == 0 and (it + 1) % c.save_interval == 0:
             torch.save(self.agent.state_dict(), f"{self.run_path}/model_{it}.pt")     # same off-by-one naming

@@ -78,6 +78,12 @@ static_assert(offsetof(catppo_servo_sim_commands, obs) == 368 && offsetof(catppo
                   offsetof(catppo_servo_commands, floats) == 8 && offsetof(catppo_servo_commands, off_cmd_state) == 12 &&
                   sizeof(catppo_servo_sim_commands) == 416 && CATPPO_SERVO_COMMAND_FLOATS == 16,
               "catppo_servo_sim_commands: observation, event and command descriptors behind the 368 bytes");
+static_assert(offsetof(catppo_servo_sim_terminations, cmd) == 400 && offsetof(catppo_servo_sim_terminations, term) == 416 &&
+                  sizeof(catppo_servo_term_entry) == 16 && sizeof(catppo_servo_terminations) == 24 &&
+                  offsetof(catppo_servo_terminations, rec) == 8 && offsetof(catppo_servo_terminations, terms) == 16 &&
+                  offsetof(catppo_servo_terminations, off_term_state) == 20 && sizeof(catppo_servo_sim_terminations) == 440 &&
+                  CATPPO_SERVO_TERM_FLOATS == 16 && CATPPO_SERVO_TERM_MAX_TERMS == 15,
+              "catppo_servo_sim_terminations: observation, event, command and termination descriptors behind the 368 bytes");
 
 // command of (env, episode, resample index): uniform in the reference ranges, dead zone, standing fraction; with a
 // fixed-command table the caller's row `e` as it stands, for every episode and resample index - in the step-response
@@ -232,6 +238,37 @@ __device__ __forceinline__ void first_command(const catppo_servo_sim& d, const C
   if ((C.flags & CATPPO_SERVO_COMMAND_STANDING) && standing) c[0] = c[1] = c[2] = 0.f;
 }
 
+// "any" over the 16 lanes of an env: the butterfly of tree16 with max in place of + (exact, so its order does not matter)
+__device__ __forceinline__ float any16(float x) {
+  x = fmaxf(x, __shfl_xor(x, 8, 16));
+  x = fmaxf(x, __shfl_xor(x, 4, 16));
+  x = fmaxf(x, __shfl_xor(x, 2, 16));
+  x = fmaxf(x, __shfl_xor(x, 1, 16));
+  return x;
+}
+
+// the length of a contact force, in the association of IsaacLab's norm over (x, y, z)
+__device__ __forceinline__ float force_norm(float fx, float fy, float fz) { return sqrtf((fx * fx + fy * fy) + fz * fz); }
+
+// what a lane keeps for the termination terms between the top of the kernel and their loop; empty without them
+template <bool kOn>
+struct TermRegs {};
+template <>
+struct TermRegs<true> {
+  catppo_servo_term_entry entry = {0, 0u, 0.f, 0.f};      // lane k: entry k of the table
+  int terms = 0;
+  float rec0 = 0.f;                                        // lane k: float k of the env's record before this step
+  uint32_t fired = 0u;                                     // bit k: term k fired in this step
+  bool gone = false;                                       // some term that is no time-out fired
+};
+
+// what ends the episode besides the time-out: the model's roll-over flag, or the table's verdict
+template <bool kOn>
+__device__ __forceinline__ bool gone_of(const TermRegs<kOn>& tr, bool fallen) {
+  if constexpr (kOn) return tr.gone;
+  else return fallen;
+}
+
 // kMode = kTrain is the launch with all three evaluation pointers NULL: everything they add is compiled out of it, so
 // that a training step runs the code it ran before the fields existed.  kEvaluate: a fixed-command table [N, 3] or an
 // evaluation record, and nothing else - the evaluation that runs inside training keeps the code it had, too.
@@ -251,12 +288,17 @@ __device__ __forceinline__ void first_command(const catppo_servo_sim& d, const C
 // catppo_servo_commands, last in the pack ("Commands"): the velocity command is the stateful process of the
 // command block instead of command_of's draws, at its three call sites.  Orthogonal to the rest, compiled out without it:
 // 24 more instances, none of which is held to 64 VGPRs.
+// catppo_servo_terminations, last in the pack ("Terminations"): the table's terms decide when an episode
+// is over; `terminated` (the OR of the fired terms that are no time-out) stands where `fallen` stood in `ends`, hard_reset,
+// reward kinds 15 / 16, the evaluation record and the trace.  Orthogonal to the rest, compiled out without it: 32 more
+// instances (their evaluation mode launches the step-response one, see launch()), none of which is held to 64 VGPRs.
 template <int kMode, bool kRew, typename... Ext>
 __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeof...(Ext) == 0) ? 8 : 1) void servo_sim_kernel(
     const catppo_servo_sim d, const Ext... ext) {
   constexpr bool kObs = (std::is_same_v<Ext, catppo_servo_obs> || ...);
   constexpr bool kEv = (std::is_same_v<Ext, catppo_servo_events> || ...);
   constexpr bool kCmd = (std::is_same_v<Ext, catppo_servo_commands> || ...);
+  constexpr bool kTerm = (std::is_same_v<Ext, catppo_servo_terminations> || ...);
   constexpr bool kEval = kMode != kTrain;
   extern __shared__ float4 lds4[];
   float* lds = reinterpret_cast<float*>(lds4);
@@ -359,6 +401,15 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
     // the last-action block of the input row: the action manager's history (zero after a step that ended an episode)
     if (isj && !rst && D >= 45) a_prev = in[d.off_obs + 33 + lane];
   }
+  // termination table and record: lane k holds entry k (one 16-byte load, long before the loop that reads it through
+  // readlane); lane k of a live lane group owns float k of its env's record (one 64-byte access per env)
+  TermRegs<kTerm> TR;
+  if constexpr (kTerm) {
+    const catppo_servo_terminations& tm = ext_of<catppo_servo_terminations>(ext...);
+    TR.terms = tm.terms;
+    if (!init && lane < TR.terms) TR.entry = tm.table[lane];
+    if (e0 + grp < d.N && !init) TR.rec0 = tm.rec[e * CATPPO_SERVO_TERM_FLOATS + lane];
+  }
 
   if (init) {
     // the first state of episode 0: default pose + noise, at rest, four feet on the ground
@@ -406,6 +457,9 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
       if (rec) d.eval[rec_at] = 0.f;
     if constexpr (kRew)
       if (rrec) d.reward_rec[rrec_at] = 0.f, d.reward_rec[rrec_at + 16] = 0.f;
+    // term_state is part of the zero-filled row
+    if constexpr (kTerm)
+      if (e0 + grp < d.N) ext_of<catppo_servo_terminations>(ext...).rec[e * CATPPO_SERVO_TERM_FLOATS + lane] = 0.f;
   } else {
     // ---- the state this step starts from: the row, or the first state of episode `ep` re-derived from the counter
     float q = 0.f, qd = 0.f, a = 0.f;
@@ -500,11 +554,57 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
     float x0 = rst ? 0.f : in[d.off_root_pos], y0 = rst ? 0.f : in[d.off_root_pos + 1];
     if constexpr (kEv)
       if (rst) x0 = first_xy[0], y0 = first_xy[1];
+    // ---- termination terms: bit k of `fired` is term k of the table; a wave-uniform loop, every lane ends with the same bits
+    if constexpr (kTerm) {
+      bool gone = false;
+      uint32_t fired = 0u;
+      // the projected gravity before the roll-over override: what the orientation terms read
+      const float g_pre[3] = {(0.f - pitch) / nrm, roll / nrm, -1.f / nrm};
+      for (int k = 0; k < TR.terms; ++k) {
+        catppo_servo_term_entry te;
+        te.kind = __builtin_amdgcn_readlane(TR.entry.kind, k);
+        te.mask = (uint32_t)__builtin_amdgcn_readlane((int)TR.entry.mask, k);
+        te.p0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(TR.entry.p0), k));
+        te.p1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(TR.entry.p1), k));
+        const bool mj = isj && ((te.mask >> lane) & 1u);
+        bool fire = false;
+        switch (te.kind) {
+          case 1: fire = t + 1 >= d.max_episode_length; break;
+          case 2: {
+            // slot 0, this step: base_link (body 0) on every lane, foot lane & 3 (body 4 f + 4); slots 1 .. H - 1 are slots
+            // 0 .. H - 2 of the input row (none after a reset): lane l takes body l, lane 0 body 16 as well
+            float hit = (te.mask & 1u) && force_norm(0.f, 0.f, fbase) > te.p0 ? 1.f : 0.f;
+            if (((te.mask >> foot_body) & 1u) && force_norm(0.f, 0.f, fz) > te.p0) hit = 1.f;
+            if (!rst) {
+              for (int h = 0; h + 1 < d.H; ++h) {
+                const float* fr = in + d.off_forces + h * B3;
+                if (((te.mask >> lane) & 1u) && force_norm(fr[lane * 3], fr[lane * 3 + 1], fr[lane * 3 + 2]) > te.p0) hit = 1.f;
+                if (lane == 0 && ((te.mask >> 16) & 1u) && force_norm(fr[48], fr[49], fr[50]) > te.p0) hit = 1.f;
+              }
+            }
+            fire = any16(hit) > 0.f;
+            break;
+          }
+          case 3: fire = sqrtf(g_pre[0] * g_pre[0] + g_pre[1] * g_pre[1]) > te.p0; break;
+          case 4: fire = (0.f - g_pre[2]) < te.p0; break;
+          case 5: fire = z < te.p0; break;
+          case 6: fire = any16(mj && (q < te.p0 || q > te.p1) ? 1.f : 0.f) > 0.f; break;
+          case 7: fire = any16(mj && fabsf(qd) > te.p0 ? 1.f : 0.f) > 0.f; break;
+          case 8: fire = tilt2 > d.tilt_max * d.tilt_max; break;
+          default: break;                                  // the table's writer admits no other kind
+        }
+        if (fire) {
+          fired |= 1u << k;
+          if (te.kind != 1) gone = true;
+        }
+      }
+      TR.fired = fired, TR.gone = gone;
+    }
     // ---- reward: rational stand-ins for the two exp tracking rewards
     const float ex = cmd[0] - v[0], ey = cmd[1] - v[1], ew = cmd[2] - v[2];
     const float reward = 1.f / (1.f + (ex * ex + ey * ey) / d.reward_scale) + 0.5f / (1.f + (ew * ew) / d.reward_scale);
     // ---- does this step end the episode?  Then `obs` already shows the first state of the next one.
-    const bool ends = t + 1 >= d.max_episode_length || fallen;
+    const bool ends = t + 1 >= d.max_episode_length || gone_of(TR, fallen);
     const uint32_t ep_out = ep + (ends ? 1u : 0u);
     if constexpr (kObs) obs_ep = ep_out, obs_t = ends ? 0u : (uint32_t)(t + 1);
     // ---- reward terms: value_k = (raw_k * weight_k) * step_dt in table order, summed from 0.f; lane k keeps value_k
@@ -536,8 +636,8 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
           case 12: raw = tree16(a * a); break;
           case 13: raw = tree4((last_air - tm.param) * (touch ? 1.f : 0.f)) * moving; break;
           case 14: raw = (z - tm.param) * (z - tm.param); break;
-          case 15: raw = fallen ? 1.f : 0.f; break;
-          case 16: raw = fallen ? 0.f : 1.f; break;
+          case 15: raw = gone_of(TR, fallen) ? 1.f : 0.f; break;
+          case 16: raw = gone_of(TR, fallen) ? 0.f : 1.f; break;
           default: break;                                // the table's writer admits no other kind
         }
         const float value = (raw * tm.weight) * step_dt;
@@ -563,7 +663,7 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
         switch (lane) {
           case 0: head = (float)t; break;
           case 1: head = ends ? 1.f : 0.f; break;
-          case 2: head = fallen ? 1.f : 0.f; break;
+          case 2: head = gone_of(TR, fallen) ? 1.f : 0.f; break;
           case 3: head = reward; break;
           case 4: head = cmd[0]; break;
           case 5: head = cmd[1]; break;
@@ -627,8 +727,16 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
     if (lane == 13) {
       for (int k = 0; k < 3; ++k) row[d.off_command + k] = cmd[k];
       row[d.off_reward] = kRew ? rsum : reward;
-      row[d.off_hard_reset] = fallen ? 1.f : 0.f;
+      row[d.off_hard_reset] = gone_of(TR, fallen) ? 1.f : 0.f;
       if constexpr (kCmd) row[ext_of<catppo_servo_commands>(ext...).off_cmd_state] = cmd_gen ? cmd_tl : 0.f;
+    }
+    if constexpr (kTerm) {
+      const catppo_servo_terminations& tm = ext_of<catppo_servo_terminations>(ext...);
+      // the fired terms as a float (exact: fewer than 16 bits); lane k counts term k over the steps that end an episode,
+      // lane 15 those steps
+      if (lane == 12) row[tm.off_term_state] = (float)TR.fired;
+      if (e0 + grp < d.N && ends)
+        tm.rec[e * CATPPO_SERVO_TERM_FLOATS + lane] = TR.rec0 + (lane == 15 || ((TR.fired >> lane) & 1u) ? 1.f : 0.f);
     }
     if (lane == 14) {
       for (int k = 0; k < 3; ++k) row[d.off_servo + k] = v[k];
@@ -664,7 +772,7 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
       float term = 1.f, acc = rec0;
       switch (lane) {
         case 1: term = ends ? 1.f : 0.f; break;
-        case 2: term = fallen ? 1.f : 0.f; break;
+        case 2: term = gone_of(TR, fallen) ? 1.f : 0.f; break;
         case 3: term = reward; break;
         case 4: term = ex * ex + ey * ey; break;
         case 5: term = ew * ew; break;
@@ -737,8 +845,11 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
 template <typename... Ext>
 void launch(int mode, bool rew, unsigned nblk, size_t lds_bytes, hipStream_t stream, const catppo_servo_sim& d, const Ext&... ext) {
   using Kernel = void (*)(const catppo_servo_sim, const Ext...);
+  // packs with terminations fold the evaluation instances into the step-response ones (which take a NULL trace and a plain
+  // command table through two wave-uniform branches and compute the same bits): a third fewer instances to compile
+  constexpr int kEvalAs = (std::is_same_v<Ext, catppo_servo_terminations> || ...) ? kStepResponse : kEvaluate;
   const Kernel table[3][2] = {{servo_sim_kernel<kTrain, false, Ext...>, servo_sim_kernel<kTrain, true, Ext...>},
-                              {servo_sim_kernel<kEvaluate, false, Ext...>, servo_sim_kernel<kEvaluate, true, Ext...>},
+                              {servo_sim_kernel<kEvalAs, false, Ext...>, servo_sim_kernel<kEvalAs, true, Ext...>},
                               {servo_sim_kernel<kStepResponse, false, Ext...>, servo_sim_kernel<kStepResponse, true, Ext...>}};
   hipLaunchKernelGGL(table[mode][rew ? 1 : 0], dim3(nblk), dim3(kThreads), lds_bytes, stream, d, ext...);
 }
@@ -752,14 +863,18 @@ extern "C" int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* de
   // reserved names what lies behind the descriptor: nothing, the observation descriptor of a catppo_servo_sim_obs, or the
   // observation and event descriptors of a catppo_servo_sim_events (whose observation descriptor may be empty)
   // ... or all three of a catppo_servo_sim_commands (whose event descriptor may be empty, too)
-  const bool ext_cmd = d.reserved == CATPPO_SERVO_EXT_COMMANDS;
+  // ... or all four of a catppo_servo_sim_terminations (whose command descriptor may be empty, too)
+  const bool ext_term = d.reserved == CATPPO_SERVO_EXT_TERMINATIONS;
+  const bool ext_cmd = d.reserved == CATPPO_SERVO_EXT_COMMANDS || ext_term;
   CATPPO_CHECK_ARG(ctx, d.reserved == 0 || d.reserved == CATPPO_SERVO_EXT_OBS || d.reserved == CATPPO_SERVO_EXT_EVENTS || ext_cmd);
   const catppo_servo_obs* obs = d.reserved != 0 ? &reinterpret_cast<const catppo_servo_sim_obs*>(desc)->obs : nullptr;
   const catppo_servo_events* ev = d.reserved == CATPPO_SERVO_EXT_EVENTS || ext_cmd
                                       ? &reinterpret_cast<const catppo_servo_sim_events*>(desc)->ev : nullptr;
   const catppo_servo_commands* cm = ext_cmd ? &reinterpret_cast<const catppo_servo_sim_commands*>(desc)->cmd : nullptr;
   if (ev && obs->width == 0 && obs->table == nullptr) obs = nullptr;
+  const catppo_servo_terminations* tm = ext_term ? &reinterpret_cast<const catppo_servo_sim_terminations*>(desc)->term : nullptr;
   if (cm && ev->block == nullptr && ev->floats == 0) ev = nullptr;
+  if (tm && cm->block == nullptr && cm->floats == 0) cm = nullptr;
   CATPPO_CHECK_ARG(ctx, d.N >= 1 && d.N < (int64_t(1) << 31) && d.env_offset >= 0 && d.env_offset + d.N < (int64_t(1) << 32));
   CATPPO_CHECK_ARG(ctx, d.state_in && d.state_out && d.episode_length);
   CATPPO_CHECK_ARG(ctx, d.init || (d.action && d.reset && d.state_in != d.state_out));
@@ -836,12 +951,45 @@ extern "C" int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* de
       CATPPO_CHECK_ARG(ctx, cs + 4 <= obs->off_policy_obs || cs >= obs->off_policy_obs + padded);
     }
   }
+  if (tm) {
+    CATPPO_CHECK_ARG(ctx, tm->terms >= 1 && tm->terms <= CATPPO_SERVO_TERM_MAX_TERMS);
+    // the entries are device memory: their writer checks kinds, masks and params (Solo12ServoSim.set_termination_table);
+    // whatever they hold the launch stays inside its row and its record: they are never addresses, and the history
+    // slots a contact term reads are the input row's own
+    const void* tb = tm->table;
+    const void* rc = tm->rec;
+    CATPPO_CHECK_ARG(ctx, tb != nullptr && ((uintptr_t)tb % 16) == 0 && rc != nullptr && ((uintptr_t)rc % 16) == 0);
+    const uintptr_t tb0 = (uintptr_t)tb, tb1 = tb0 + sizeof(catppo_servo_term_entry) * CATPPO_SERVO_TERM_MAX_TERMS;
+    const uintptr_t rc0 = (uintptr_t)rc, rc1 = rc0 + (uintptr_t)d.N * CATPPO_SERVO_TERM_FLOATS * sizeof(float);
+    CATPPO_CHECK_ARG(ctx, tb1 <= rc0 || rc1 <= tb0);
+    const void* others[] = {d.state_in, d.state_out, d.eval, d.trace, d.fixed_command, d.reward_rec, (const void*)d.reward_table,
+                            obs ? (const void*)obs->table : nullptr, ev ? (const void*)ev->block : nullptr,
+                            cm ? (const void*)cm->block : nullptr};
+    for (const void* o : others) CATPPO_CHECK_ARG(ctx, tb != o && rc != o);
+    // the state field: four floats of the row on a 16-byte boundary that no other field the kernel writes touches
+    const int64_t ts = tm->off_term_state;
+    CATPPO_CHECK_ARG(ctx, ts >= 0 && ts % 4 == 0 && ts + 4 <= d.row_floats);
+    for (const auto& fl : fields) CATPPO_CHECK_ARG(ctx, ts + 4 <= fl.off || ts >= (int64_t)fl.off + fl.width);
+    if (obs) {
+      const int64_t padded = (obs->width + 3) / 4 * 4;
+      CATPPO_CHECK_ARG(ctx, ts + 4 <= obs->off_policy_obs || ts >= obs->off_policy_obs + padded);
+    }
+    if (cm) CATPPO_CHECK_ARG(ctx, ts + 4 <= cm->off_cmd_state || ts >= (int64_t)cm->off_cmd_state + 4);
+  }
   const unsigned nblk = (unsigned)cdiv64(d.N, kEnvsPerBlock);
   const size_t lds_bytes = (size_t)d.row_floats * kEnvsPerBlock * sizeof(float);
   const int mode = (d.trace || d.fixed_segments > 1) ? kStepResponse : (d.fixed_command || d.eval) ? kEvaluate : kTrain;
   const bool rew = d.reward_terms > 0;
   const hipStream_t st = static_cast<hipStream_t>(stream);
-  if (cm && obs && ev) launch(mode, rew, nblk, lds_bytes, st, d, *obs, *ev, *cm);
+  if (tm && cm && obs && ev) launch(mode, rew, nblk, lds_bytes, st, d, *obs, *ev, *cm, *tm);
+  else if (tm && cm && ev) launch(mode, rew, nblk, lds_bytes, st, d, *ev, *cm, *tm);
+  else if (tm && cm && obs) launch(mode, rew, nblk, lds_bytes, st, d, *obs, *cm, *tm);
+  else if (tm && cm) launch(mode, rew, nblk, lds_bytes, st, d, *cm, *tm);
+  else if (tm && obs && ev) launch(mode, rew, nblk, lds_bytes, st, d, *obs, *ev, *tm);
+  else if (tm && ev) launch(mode, rew, nblk, lds_bytes, st, d, *ev, *tm);
+  else if (tm && obs) launch(mode, rew, nblk, lds_bytes, st, d, *obs, *tm);
+  else if (tm) launch(mode, rew, nblk, lds_bytes, st, d, *tm);
+  else if (cm && obs && ev) launch(mode, rew, nblk, lds_bytes, st, d, *obs, *ev, *cm);
   else if (cm && ev) launch(mode, rew, nblk, lds_bytes, st, d, *ev, *cm);
   else if (cm && obs) launch(mode, rew, nblk, lds_bytes, st, d, *obs, *cm);
   else if (cm) launch(mode, rew, nblk, lds_bytes, st, d, *cm);

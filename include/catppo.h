@@ -729,7 +729,7 @@ typedef struct catppo_servo_sim {
   const uint8_t* reset;                  /* [N] */
   const int64_t* episode_length;         /* [N], before this step's increment */
   int64_t max_episode_length;
-  int32_t decimation, resample_steps, init, reserved;   /* reserved: 0 or one of CATPPO_SERVO_EXT_OBS / _EVENTS / _COMMANDS (see below) */
+  int32_t decimation, resample_steps, init, reserved;   /* reserved: 0 or one of CATPPO_SERVO_EXT_OBS / _EVENTS / _COMMANDS / _TERMINATIONS (see below) */
   uint64_t seed;
   float default_joint_pos[12];
   float dt, kp, kd, inertia, tau_max, action_scale, vel_alpha, tilt_beta, tilt_max, reward_scale, foot_clearance,
@@ -883,6 +883,64 @@ typedef struct catppo_servo_sim_commands {
   catppo_servo_events ev;                 /* block NULL and floats 0: no events */
   catppo_servo_commands cmd;
 } catppo_servo_sim_commands;
+
+/* Terminations ("Terminations").  desc->reserved == CATPPO_SERVO_EXT_TERMINATIONS: `desc` is the head of a
+ * catppo_servo_sim_terminations, i.e. the observation, event, command and termination descriptors lie behind the 368
+ * bytes.  Under this value obs.width == 0 with a NULL table means "no observation table", ev.block == NULL with
+ * ev.floats == 0 "no events" and cmd.block == NULL with cmd.floats == 0 "no commands"; otherwise the three are checked and
+ * used exactly as under CATPPO_SERVO_EXT_COMMANDS.  Every older value of `reserved` keeps its meaning.
+ * term.table is a DEVICE array of `terms` entries {kind, mask, p0, p1} (1 <= terms <= CATPPO_SERVO_TERM_MAX_TERMS; the
+ * entry point reserves CATPPO_SERVO_TERM_MAX_TERMS entries behind the pointer when it checks for overlap), 16-byte aligned,
+ * read by every launch that is no init launch (params the host rewrites in stream order are in the next launch, under graph
+ * replay too).  Term k fires in a step when (symbols of csrc/servo_sim.hip, all after the step's integration; fp32, unfused):
+ *   1 time_out                         t + 1 >= max_episode_length
+ *   2 illegal_contact                  some body b with bit b of mask set (17 bodies, base_link = bit 0) and some history slot
+ *                                      h < H has sqrt((fx fx + fy fy) + fz fz) > p0.  Slot 0 is this step's forces (fbase on
+ *                                      body 0, fz on the feet 4 8 12 16, zero elsewhere), slot h >= 1 is slot h - 1 of the
+ *                                      input row; a step whose reset flag is set has only slot 0
+ *   3 upside_down                      sqrt(g0 g0 + g1 g1) > p0          g = (0 - pitch, roll, -1) / sqrt(tilt2 + 1), the
+ *   4 bad_orientation                  (0 - g2) < p0                     projected gravity BEFORE the roll-over override;
+ *                                                                        p0 = f32(cos(limit_angle)), computed by the host
+ *   5 root_height_below_minimum        z < p0
+ *   6 joint_pos_out_of_manual_limit    some joint j with bit j of mask set has q < p0 or q > p1
+ *   7 joint_vel_out_of_manual_limit    some joint j with bit j of mask set has |qd| > p0
+ *   8 rolled_over                      tilt2 > tilt_max * tilt_max       (the model's own flag)
+ * "some" over joints or bodies is a max over the env's 16 lanes in the shape of tree16 (exact: the order cannot matter);
+ * kind 2 gives lane l body l of the history slots and lane 0 body 16 as well.  terminated = some fired term of kind != 1.
+ * It stands where the model's flag `fallen` stands without this descriptor: an episode ends on t + 1 >= max_episode_length
+ * or terminated; the row's hard_reset, reward kinds 15 and 16, field 2 of the evaluation record and float 2 of a trace
+ * row are `terminated`.  The written projected gravity is still overridden with (0, 0, 1) when tilt2 > tilt_max^2, which no
+ * longer ends an episode by itself.
+ * term.off_term_state names one more 16-byte field of the row (a multiple of 4, disjoint from every other field the kernel
+ * writes): float 0 is the step's fired terms as a float, bit k = term k (exact: below 2^16), floats 1..3 zero; an init
+ * launch writes zeros.
+ * term.rec ([N, CATPPO_SERVO_TERM_FLOATS] fp32, 16-byte aligned; may alias none of the state buffers, the records, the
+ * trace, the command table or the other tables and blocks): a step that ends its episode adds 1 to float k < 15 when term k
+ * fired and 1 to float 15, the count of ended episodes; any other step leaves it alone; an init launch zeroes it.  No
+ * atomics, no communication between envs.
+ * The table's writer checks its entries (Solo12ServoSim.set_termination_table); whatever it holds the launch stays inside
+ * its row and its record: an unknown kind never fires, masks select lanes, params are compared, nothing is an address. */
+#define CATPPO_SERVO_EXT_TERMINATIONS 0x54524D31   /* "TRM1": value of catppo_servo_sim.reserved that announces catppo_servo_sim_terminations */
+#define CATPPO_SERVO_TERM_FLOATS 16
+#define CATPPO_SERVO_TERM_MAX_TERMS 15
+typedef struct catppo_servo_term_entry {
+  int32_t kind;
+  uint32_t mask;                          /* kinds 6, 7: joints (bits 0..11); kind 2: bodies (bits 0..16) */
+  float p0, p1;
+} catppo_servo_term_entry;
+typedef struct catppo_servo_terminations {
+  const catppo_servo_term_entry* table;   /* DEVICE array [terms], 16-byte aligned */
+  float* rec;                             /* DEVICE [N, CATPPO_SERVO_TERM_FLOATS], 16-byte aligned */
+  int32_t terms;                          /* 1 .. CATPPO_SERVO_TERM_MAX_TERMS */
+  int32_t off_term_state;                 /* the row's 4-float field: fired terms | 0 0 0 */
+} catppo_servo_terminations;
+typedef struct catppo_servo_sim_terminations {
+  catppo_servo_sim sim;                   /* sim.reserved = CATPPO_SERVO_EXT_TERMINATIONS */
+  catppo_servo_obs obs;                   /* width 0 and table NULL: no observation table */
+  catppo_servo_events ev;                 /* block NULL and floats 0: no events */
+  catppo_servo_commands cmd;              /* block NULL and floats 0: no commands */
+  catppo_servo_terminations term;
+} catppo_servo_sim_terminations;
 
 /* ---- test hook (ABI 0.6) ------------------------------------------------------------------------------------------
  * buf != NULL ([2][M] int32, device): the head / loss kernel of every following catppo_ppo_minibatch_* call writes the clip

@@ -11,9 +11,10 @@ BASELINE shapes (profiles/r5_explain_plan.txt is this output).
     python tools/explain_plan.py --task Isaac-Velocity-CaT-Flat-Solo12-Servo-Reference-v0        (needs no device)
 
 names the instance of the servo simulator's kernel a task's training step launches: which of ``cfg.rewards``,
-``cfg.observations``, ``cfg.events`` and ``cfg.commands`` (``RewardsCfg``, ``ObservationsCfg``, ``EventCfg``, ``CommandsCfg``) the
-cfg carries decides the kernel's template pack (csrc/servo_sim.hip).  The servo tasks are
-``...-Solo12-Servo-v0`` and its ``-Rewards``, ``-Obs``, ``-Events``, ``-Full``, ``-Commands`` and ``-Reference`` variants."""
+``cfg.observations``, ``cfg.events``, ``cfg.commands`` and ``cfg.terminations`` (``RewardsCfg``, ``ObservationsCfg``, ``EventCfg``,
+``CommandsCfg``, ``TerminationsCfg``) the cfg carries decides the kernel's template pack (csrc/servo_sim.hip).
+The servo tasks are ``...-Solo12-Servo-v0`` and its ``-Rewards``, ``-Obs``, ``-Events``, ``-Full``, ``-Commands``, ``-Reference``,
+``-Terminations`` and ``-Reference-Terminations`` variants."""
 import argparse
 import os
 import sys
@@ -68,10 +69,10 @@ def explain_task(task):
     cfg = load_cfg_from_registry(task, "env_cfg_entry_point")
     if str(getattr(cfg.synthetic, "kind", "stream")) != "servo":
         return f"== {task}: the stream simulator (no simulator kernel; the state is a pre-generated stream)"
-    has = {k: getattr(cfg, k, None) is not None for k in ("rewards", "observations", "events", "commands")}
+    has = {k: getattr(cfg, k, None) is not None for k in ("rewards", "observations", "events", "commands", "terminations")}
     pack = [name for key, name in (("observations", "catppo_servo_obs"), ("events", "catppo_servo_events"),
-                                   ("commands", "catppo_servo_commands")) if has[key]]
-    row = 308 + (48 if has["observations"] else 0) + (4 if has["commands"] else 0)
+                                   ("commands", "catppo_servo_commands"), ("terminations", "catppo_servo_terminations")) if has[key]]
+    row = 308 + (48 if has["observations"] else 0) + (4 if has["commands"] else 0) + (4 if has["terminations"] else 0)
     out = [f"== {task}: " + ", ".join(f"cfg.{k} {'set' if v else 'unset'}" for k, v in has.items()),
            f"servo_sim_kernel<kTrain, {'true' if has['rewards'] else 'false'}{''.join(', ' + n for n in pack)}>: row of {row} floats "
            f"(with the reference's 45-float policy observation), {row * 64} bytes of LDS per workgroup"]
@@ -80,6 +81,12 @@ def explain_task(task):
         b = KM.build_block(cfg.commands, cfg.sim.dt, cfg.episode_length_s)
         out.append(f"command term '{b['name']}' ({b['class']}): flags {b['flags']:#x}, p_still {b['p_still']:g}, p_move {b['p_move']:g}, "
                    f"ranges {b['bounds']}, resampling {b['time']} s; inert: {', '.join(b['inert']) or 'none'}")
+    if has["terminations"]:
+        import cat_envs.tasks.utils.cat.cat_env as E
+        from cat_envs.tasks.utils.mdp import terminations as TM
+        kinds = {v: k for k, v in TM.K.items()}
+        for name, kind, mask, p0, p1 in TM.build_table(cfg.terminations, E.SOLO12_JOINTS, E.SOLO12_BODIES):
+            out.append(f"termination term '{name}' ({kinds[kind]}{', time_out' if kind == 1 else ''}): mask {mask:#x}, p0 {p0:g}, p1 {p1:g}")
     return "\n".join(out)
 
 

@@ -26,6 +26,10 @@ simulator's launch is the commands-on training instance.  The reference's p_move
 of 32768 - and flips the yaw of as many, and the redraw branch is part of what is timed.
 profiles/servo_commands_kernel_stats.csv: the parent's library, this library without the flag and this library with --commands,
 alternating in one session, every run listed.
+--terminations runs the task with the reference's termination block (Isaac-Velocity-CaT-Flat-Solo12-Servo-Terminations-v0:
+time_out, base_contact on base_link and the upper legs, upside_down at 0.1), so that the simulator's launch is the
+terminations-on training instance; the values are the reference's own.  profiles/servo_terminations_kernel_stats.csv: the
+parent's library, this library without the flag and this library with --terminations, alternating in one session, every run listed.
 
 Per env step the trace shows servo_sim_kernel (the simulator), the two launches of catppo_rollout_pre, the one of
 catppo_rollout_post and the policy forward."""
@@ -50,16 +54,18 @@ def main():
     ap.add_argument("--obs", action="store_true", help="the task with ObservationsCfg: observation terms inside the simulator launch")
     ap.add_argument("--events", action="store_true", help="the task with EventCfg (push probability 0.01): events inside the simulator launch")
     ap.add_argument("--commands", action="store_true", help="the task with CommandsCfg (p_move 0.01): the command term inside the simulator launch")
+    ap.add_argument("--terminations", action="store_true", help="the task with TerminationsCfg: termination terms inside the simulator launch")
     a = ap.parse_args()
-    if a.obs + a.rewards + a.events + a.commands > 1:
-        ap.error("--obs, --rewards, --events and --commands are separate arms")
+    if a.obs + a.rewards + a.events + a.commands + a.terminations > 1:
+        ap.error("--obs, --rewards, --events, --commands and --terminations are separate arms")
     import cat_envs.tasks  # noqa: F401
     from cat_envs.shim import load_cfg_from_registry, make
     from cat_envs.tasks.utils.cleanrl.ppo import PPOTrainer
     task = ("Isaac-Velocity-CaT-Flat-Solo12-Servo-Rewards-v0" if a.rewards else
             "Isaac-Velocity-CaT-Flat-Solo12-Servo-Obs-v0" if a.obs else
             "Isaac-Velocity-CaT-Flat-Solo12-Servo-Events-v0" if a.events else
-            "Isaac-Velocity-CaT-Flat-Solo12-Servo-Commands-v0" if a.commands else "Isaac-Velocity-CaT-Flat-Solo12-Servo-v0")
+            "Isaac-Velocity-CaT-Flat-Solo12-Servo-Commands-v0" if a.commands else
+            "Isaac-Velocity-CaT-Flat-Solo12-Servo-Terminations-v0" if a.terminations else "Isaac-Velocity-CaT-Flat-Solo12-Servo-v0")
     env_cfg = load_cfg_from_registry(task, "env_cfg_entry_point")
     if a.rewards:
         from cat_envs.tasks.locomotion.velocity.config.solo12.cat_flat_env_cfg import ShapedRewardsCfg
@@ -111,6 +117,9 @@ def main():
         zero = (sim.view("command") == 0).all(1).float().mean()
         print(f"commands: {km.active_terms}, p_move {km.block['p_move']:g}, row of {sim.F} floats, zero commands {float(zero):.4f}, "
               f"mean time left {float(sim.view('cmd_state')[:, 0].mean()):.3f} s")
+    if a.terminations:
+        tm = env_u.termination_manager
+        print(f"terminations: {tm.active_terms}, row of {env_u.sim.F} floats, shares of the ended episodes {tm.pop_log()}")
     if a.eval or a.trace:
         steps = record[:, 0].cpu()
         assert float(steps.min()) == float(steps.max()) == a.rollouts * trainer.T, (float(steps.min()), float(steps.max()))
