@@ -243,6 +243,31 @@ class ServoSimTerminations(ServoSimCommands):
     _fields_ = [("term", ServoTerminations)]
 
 
+SERVO_EXT_ACTIONS = 0x41435431          # CATPPO_SERVO_EXT_ACTIONS: ``reserved`` of a descriptor followed by obs, events, commands, terminations and actions
+SERVO_ACTION_KIND_MASK, SERVO_ACTION_CLIP = 0x7, 0x8     # CATPPO_SERVO_ACTION_KIND_MASK / _CLIP: the two parts of an entry's flags
+#: kinds of the servo surrogate's joint action terms (include/catppo.h, "Actions"): name -> kind in catppo_servo_action_entry.flags
+SERVO_ACTION_KINDS = {"none": 0, "joint_position": 1, "relative_joint_position": 2, "joint_velocity": 3, "joint_effort": 4}
+
+
+class ServoActionEntry(C.Structure):
+    """catppo_servo_action_entry: entry j of the device-resident action table, what drives simulator joint j"""
+    _fields_ = [("col", C.c_int32), ("flags", C.c_uint32), ("scale", C.c_float), ("offset", C.c_float),
+                ("clip_lo", C.c_float), ("clip_hi", C.c_float), ("zero", C.c_uint32 * 2)]
+
+
+class ServoActions(C.Structure):
+    """catppo_servo_actions: the action descriptor; ``table`` is a device array of 12 ``ServoActionEntry``, ``width`` the
+    width A of the action the simulator reads"""
+    _fields_ = [("table", C.c_void_p), ("width", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ServoSimActions(ServoSimTerminations):
+    """catppo_servo_sim_actions: catppo_servo_sim, a ``ServoObs``, a ``ServoEvents``, a ``ServoCommands``, a
+    ``ServoTerminations`` (a NULL table and ``terms`` 0: no terminations) and a ``ServoActions`` behind it; the library reads
+    all five while ``reserved`` is ``SERVO_EXT_ACTIONS``"""
+    _fields_ = [("act", ServoActions)]
+
+
 F32, F16, F64 = 0, 1, 2                 # CATPPO_F32 / _F16 / _F64
 SUM, MAX = 0, 1                         # CATPPO_SUM / _MAX
 LR_FIXED, LR_LINEAR, LR_KEEP = 0, 1, 2
@@ -853,6 +878,8 @@ class Native:
             raise TypeError("servo_sim_step: a descriptor whose 'reserved' announces commands must be a native.ServoSimCommands")
         if desc.reserved == SERVO_EXT_TERMINATIONS and not isinstance(desc, ServoSimTerminations):   # ... and a catppo_servo_terminations
             raise TypeError("servo_sim_step: a descriptor whose 'reserved' announces terminations must be a native.ServoSimTerminations")
+        if desc.reserved == SERVO_EXT_ACTIONS and not isinstance(desc, ServoSimActions):   # ... and a catppo_servo_actions
+            raise TypeError("servo_sim_step: a descriptor whose 'reserved' announces actions must be a native.ServoSimActions")
         rc = self.lib.catppo_servo_sim_step(self.h, C.byref(desc), self._stream())
         if rc:
             self._ok(rc)

@@ -7,7 +7,9 @@ surface: ``configclass`` (dataclass tolerant of un-annotated overrides, mutable 
 registry replacing ``gym.register`` / ``gym.make`` / ``load_cfg_from_registry``.
 """
 from .configclass import MISSING, configclass  # noqa: F401
-from .managers import (AdditiveUniformNoiseCfg, CurriculumTermCfg, EventTermCfg, ManagerBase, ManagerTermBase,  # noqa: F401
-                       ManagerTermBaseCfg, ObservationGroupCfg, ObservationTermCfg, RewardTermCfg, SceneEntityCfg, TerminationTermCfg)
+from .managers import (AdditiveUniformNoiseCfg, CurriculumTermCfg, EventTermCfg, JointEffortActionCfg,  # noqa: F401
+                       JointPositionActionCfg, JointVelocityActionCfg, ManagerBase, ManagerTermBase, ManagerTermBaseCfg,
+                       ObservationGroupCfg, ObservationTermCfg, RelativeJointPositionActionCfg, RewardTermCfg, SceneEntityCfg,
+                       TerminationTermCfg)
 from .registry import (apply_overrides, hydra_task_config, load_cfg_from_registry, make, register,  # noqa: F401
                        registry)

@@ -15,6 +15,8 @@ try:  # pragma: no cover
     from isaaclab.managers.manager_term_cfg import ObservationGroupCfg, ObservationTermCfg  # type: ignore
     from isaaclab.managers.manager_term_cfg import EventTermCfg  # type: ignore
     from isaaclab.managers.manager_term_cfg import TerminationTermCfg  # type: ignore
+    from isaaclab.envs.mdp.actions import (JointEffortActionCfg, JointPositionActionCfg, JointVelocityActionCfg,  # type: ignore
+                                           RelativeJointPositionActionCfg)
     from isaaclab.utils.noise import AdditiveUniformNoiseCfg  # type: ignore
     HAVE_ISAACLAB = True
 except Exception:
@@ -52,6 +54,36 @@ except Exception:
     class TerminationTermCfg(ManagerTermBaseCfg):
         """IsaacLab's DoneTerm: ``time_out`` marks the term whose firing is a truncation, not a termination"""
         time_out: bool = False
+
+    @configclass
+    class JointActionCfg:
+        """the fields IsaacLab's joint action terms share"""
+        asset_name: str = "robot"
+        joint_names: Any = None                  # list of regular expressions
+        scale: Any = 1.0                         # float or {regex: float}
+        offset: Any = 0.0                        # float or {regex: float}
+        preserve_order: bool = False             # the term's columns follow ``joint_names``, not the asset's joint order
+        clip: Any = None                         # {regex: (lo, hi)} on the processed action
+        debug_vis: bool = False                  # accepted, ignored
+
+    @configclass
+    class JointPositionActionCfg(JointActionCfg):
+        """processed action = position target; ``use_default_offset``: the offset is the joint's default position"""
+        use_default_offset: bool = True
+
+    @configclass
+    class RelativeJointPositionActionCfg(JointActionCfg):
+        """processed action + current position = position target; ``use_zero_offset``: the offset is zero"""
+        use_zero_offset: bool = True
+
+    @configclass
+    class JointVelocityActionCfg(JointActionCfg):
+        """processed action = velocity target; ``use_default_offset``: the offset is the default joint velocity"""
+        use_default_offset: bool = True
+
+    @configclass
+    class JointEffortActionCfg(JointActionCfg):
+        """processed action = joint torque"""
 
     @configclass
     class ObservationGroupCfg:

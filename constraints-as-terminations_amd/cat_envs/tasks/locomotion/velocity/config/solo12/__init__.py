@@ -102,10 +102,26 @@ for _name, _cfg in (("Commands", "Solo12ServoCommandsFlatEnvCfg"), ("Reference",
     )
 
 # the servo task with a TerminationsCfg: the reference's termination terms inside the simulator's launch (DESIGN section 9,
-# "Terminations"); "Reference-Terminations" is every MDP block of the reference's cfg together (the "Reference" task keeps its
-# four blocks and its row)
+# "Terminations"); "Reference-Terminations" is these five MDP blocks of the reference's cfg together (the "Reference" task keeps
+# its four blocks and its row; the sixth block, the actions, is "Reference-Actions" below)
 for _name, _cfg in (("Terminations", "Solo12ServoTerminationsFlatEnvCfg"),
                     ("Reference-Terminations", "Solo12ServoReferenceTerminationsFlatEnvCfg")):
+    register(
+        id=f"Isaac-Velocity-CaT-Flat-Solo12-Servo-{_name}-v0",
+        entry_point=CaTEnv,
+        disable_env_checker=True,
+        kwargs={"env_cfg_entry_point": f"{__name__}.cat_flat_env_cfg:{_cfg}", **_KW},
+    )
+    register(
+        id=f"Isaac-Velocity-CaT-Flat-Solo12-Servo-{_name}-Play-v0",
+        entry_point=CaTEnv,
+        disable_env_checker=True,
+        kwargs={"env_cfg_entry_point": f"{__name__}.cat_flat_env_cfg:{_cfg}_PLAY", **_KW},
+    )
+
+# the servo task with an ActionsCfg: the reference's joint action term inside the simulator's launch (DESIGN section 9,
+# "Actions"); "Reference-Actions" is all six MDP blocks of the reference's cfg together (the tasks above keep their rows)
+for _name, _cfg in (("Actions", "Solo12ServoActionsFlatEnvCfg"), ("Reference-Actions", "Solo12ServoReferenceActionsFlatEnvCfg")):
     register(
         id=f"Isaac-Velocity-CaT-Flat-Solo12-Servo-{_name}-v0",
         entry_point=CaTEnv,

@@ -15,6 +15,8 @@ blocks together.  Commands: ``CommandsCfg`` (the reference's ``UniformVelocityCo
 (``Solo12ServoCommandsFlatEnvCfg``, DESIGN section 9 "Commands"); ``Solo12ServoReferenceFlatEnvCfg`` is all four blocks.
 Terminations: ``TerminationsCfg`` (the reference's three terms and values) likewise (``Solo12ServoTerminationsFlatEnvCfg``,
 DESIGN section 9 "Terminations"); ``Solo12ServoReferenceTerminationsFlatEnvCfg`` is all five blocks.
+Actions: ``ActionsCfg`` (the reference's ``JointPositionActionCfg`` and values) likewise (``Solo12ServoActionsFlatEnvCfg``,
+DESIGN section 9 "Actions"); ``Solo12ServoReferenceActionsFlatEnvCfg`` is all six blocks.
 """
 import math
 
@@ -28,7 +30,7 @@ from cat_envs.shim import SceneEntityCfg, configclass
 from cat_envs.shim import TerminationTermCfg as DoneTerm
 from cat_envs.tasks.utils.cat import constraints, curriculums
 from cat_envs.tasks.utils.cat.manager_constraint_cfg import ConstraintTermCfg as ConstraintTerm
-from cat_envs.tasks.utils.mdp import commands, events, observations, rewards, terminations
+from cat_envs.tasks.utils.mdp import actions, commands, events, observations, rewards, terminations
 
 ALL_JOINTS = [".*_HAA", ".*_HFE", ".*_KFE"]
 
@@ -417,13 +419,45 @@ class Solo12ServoTerminationsFlatEnvCfg_PLAY(Solo12ServoTerminationsFlatEnvCfg):
 
 @configclass
 class Solo12ServoReferenceTerminationsFlatEnvCfg(Solo12ServoReferenceFlatEnvCfg):
-    """rewards, observations, events, commands and terminations: every MDP block of the reference's cfg"""
+    """rewards, observations, events, commands and terminations: five of the six MDP blocks of the reference's cfg (the
+    action block is ``Solo12ServoReferenceActionsFlatEnvCfg``'s)"""
     terminations: TerminationsCfg = TerminationsCfg()
 
 
 @configclass
 class Solo12ServoReferenceTerminationsFlatEnvCfg_PLAY(Solo12ServoReferenceFlatEnvCfg_PLAY):
     terminations: TerminationsCfg = TerminationsCfg()
+
+
+@configclass
+class ActionsCfg:
+    """the reference's action block (solo12/cat_flat_env_cfg.py ActionsCfg): one joint position term over all twelve joints
+    in the reference's order FL FR HR HL (the simulator's joints are FL FR HL HR), scale 0.5, offset = the default pose"""
+    joint_pos = actions.JointPositionActionCfg(asset_name="robot", joint_names=OBS_JOINTS, scale=0.5, use_default_offset=True,
+                                               preserve_order=True)
+
+
+@configclass
+class Solo12ServoActionsFlatEnvCfg(Solo12ServoFlatEnvCfg):
+    """the servo task with a configurable action block: the simulator's launch evaluates ``actions``' terms"""
+    actions: ActionsCfg = ActionsCfg()
+
+
+@configclass
+class Solo12ServoActionsFlatEnvCfg_PLAY(Solo12ServoActionsFlatEnvCfg):
+    scene: SceneCfg = SceneCfg(num_envs=50, env_spacing=3.0)
+    curriculum: object = None
+
+
+@configclass
+class Solo12ServoReferenceActionsFlatEnvCfg(Solo12ServoReferenceTerminationsFlatEnvCfg):
+    """rewards, observations, events, commands, terminations and actions: every MDP block of the reference's cfg"""
+    actions: ActionsCfg = ActionsCfg()
+
+
+@configclass
+class Solo12ServoReferenceActionsFlatEnvCfg_PLAY(Solo12ServoReferenceTerminationsFlatEnvCfg_PLAY):
+    actions: ActionsCfg = ActionsCfg()
 
 
 @configclass

@@ -184,7 +184,8 @@ class Solo12ServoSim(SyntheticSolo12Sim):
 
     def __init__(self, num_envs: int, obs_dim: int, device, seed: int, syn, dt: float, decimation: int,
                  max_episode_length: int, episode_length: torch.Tensor, reset: torch.Tensor, env_offset: int = 0,
-                 policy_obs_dim: int = 0, events: bool = False, commands: bool = False, terminations: bool = False):
+                 policy_obs_dim: int = 0, events: bool = False, commands: bool = False, terminations: bool = False,
+                 actions: bool = False):
         """``policy_obs_dim`` = P > 0: the row gets a second observation field ``policy_obs`` of P floats (padded to a
         multiple of 4) that ``set_observation_table`` configures; the raw field ``obs`` stays what it is.
         ``events``: the descriptor carries the event descriptor, too, and ``set_event_block`` configures it.
@@ -192,7 +193,9 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         the timed resample), the descriptor carries the command descriptor and ``set_command_block`` configures it.
         ``terminations``: the row gets one more 16-byte field ``term_state`` behind everything else (float 0: the terms that
         fired in the step, bit k = term k), the descriptor carries the termination descriptor and
-        ``set_termination_table`` configures it"""
+        ``set_termination_table`` configures it.
+        ``actions``: the descriptor carries the action descriptor and ``set_action_table`` configures it (which action
+        column drives which joint, through which scale, offset and clip, as what kind of target); the row stays what it is"""
         self.N, self.D, self.device = num_envs, obs_dim, torch.device(device)
         self.P = int(policy_obs_dim)
         if self.P and not (1 <= self.P <= native.SERVO_OBS_MAX_WIDTH and obs_dim == native.SERVO_OBS_RAW):
@@ -225,7 +228,7 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         self._episode_length, self._reset = episode_length, reset       # referenced by the descriptor: keep alive
         self._nat = native.get(self.device)
         # with a policy observation the descriptor carries the observation descriptor behind its 368 bytes
-        d = self._desc = (native.ServoSimTerminations() if terminations
+        d = self._desc = (native.ServoSimActions() if actions else native.ServoSimTerminations() if terminations
                           else native.ServoSimCommands() if commands else native.ServoSimEvents() if events
                           else native.ServoSimObs() if self.P else native.ServoSimRewards())
         d.N, d.env_offset, d.row_stride, d.row_floats = num_envs, int(env_offset), self.F, self.F
@@ -253,6 +256,8 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         self._terminations = bool(terminations)
         self._term_table = self._term_record = None                     # device table and record of the termination descriptor
         self._term_entries = []
+        self._actions = bool(actions)
+        self._action_table, self._action_entries, self.action_width = None, [], J   # device table of the action descriptor
         self._build_scene()
 
     def _table(self, t, width, what, lead=()):
@@ -421,7 +426,8 @@ class Solo12ServoSim(SyntheticSolo12Sim):
 
     def _announce(self):
         """``reserved`` names the descriptors behind the 368 bytes that are configured by now"""
-        self._desc.reserved = (native.SERVO_EXT_TERMINATIONS if self._term_table is not None
+        self._desc.reserved = (native.SERVO_EXT_ACTIONS if self._action_table is not None
+                               else native.SERVO_EXT_TERMINATIONS if self._term_table is not None
                                else native.SERVO_EXT_COMMANDS if self._command_block is not None
                                else native.SERVO_EXT_EVENTS if self._event_block is not None
                                else native.SERVO_EXT_OBS if self._obs_table is not None else 0)
@@ -502,6 +508,53 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         self._term_table.copy_(torch.frombuffer(bytearray(host), dtype=torch.uint8))
         self._term_entries = entries
 
+    def set_action_table(self, entries, width: int):
+        """``entries``: 12 ``(col, kind, scale, offset, clip)``, one per simulator joint (``native.SERVO_ACTION_KINDS``; ``col``
+        -1 and kind 0 for a joint no term drives; ``clip`` None or ``(lo, hi)``; what ``mdp.actions.build_table`` describes),
+        ``width`` = A the width of the action.  Every following step reads an action [N, A] and turns it into servo targets
+        with the table, inside the simulator's own launch.  The table lives on the device and is rewritten here and nowhere
+        else, in stream order: new scales, offsets and clips are in the next launch.  Columns, kinds, the clip bits and the
+        width are fixed by the first call.  The entries are checked here - the library cannot read them."""
+        if not self._actions:
+            raise ValueError("this simulator was built without an action descriptor (actions = False)")
+        width = int(width)
+        if not 1 <= width <= self.J:
+            raise ValueError(f"an action of width {width}: the simulator reads 1 .. {self.J} columns")
+        entries = [(int(c), int(k), float(sc), float(of), None if cl is None else (float(cl[0]), float(cl[1])))
+                   for c, k, sc, of, cl in (entries or [])]
+        if len(entries) != self.J:
+            raise ValueError(f"the action table has one entry per joint ({self.J}), got {len(entries)}")
+        cols = [c for c, k, *_ in entries if k != 0]
+        for j, (c, k, sc, of, cl) in enumerate(entries):
+            if not 0 <= k <= 4:
+                raise ValueError(f"joint {j}: unknown action kind {k}")
+            if (k == 0) != (c == -1) or not -1 <= c < width:
+                raise ValueError(f"joint {j}: column {c} with kind {k} (a driven joint has a column in 0 .. {width - 1}, any other -1)")
+            if not (math.isfinite(sc) and math.isfinite(of)):
+                raise ValueError(f"joint {j}: scale and offset must be finite, got {sc}, {of}")
+            if cl is not None and not (math.isfinite(cl[0]) and math.isfinite(cl[1]) and cl[0] <= cl[1]):
+                raise ValueError(f"joint {j}: a clip needs finite lo <= hi, got {cl}")
+        if sorted(cols) != list(range(width)):
+            raise ValueError(f"the action's {width} columns must drive one joint each, got columns {sorted(cols)}")
+        fixed = [(c, k, cl is not None) for c, k, _, _, cl in entries]
+        if self._action_entries and (fixed != [(c, k, cl is not None) for c, k, _, _, cl in self._action_entries]
+                                     or width != self.action_width):
+            raise ValueError("the action table's columns, kinds, clip bits and width are fixed by the first call; only scale, "
+                             "offset and clip bounds may change")
+        host = (native.ServoActionEntry * self.J)()
+        for j, (c, k, sc, of, cl) in enumerate(entries):
+            h = host[j]
+            h.col, h.flags, h.scale, h.offset = c, k | (native.SERVO_ACTION_CLIP if cl is not None else 0), sc, of
+            h.clip_lo, h.clip_hi = cl if cl is not None else (0.0, 0.0)
+        if self._action_table is None:
+            self._action_table = torch.zeros(C.sizeof(host), dtype=torch.uint8, device=self.device)
+            a = self._desc.act
+            a.table, a.width, a.reserved = self._action_table.data_ptr(), width, 0
+            self.action_width = width
+            self._announce()                                            # from now on every launch reads the table
+        self._action_table.copy_(torch.frombuffer(bytearray(host), dtype=torch.uint8))
+        self._action_entries = entries
+
     @property
     def termination_record(self):
         """[N, 16] fp32 or None: 0..14 how many ended episodes had term k set in their last step | 15 the ended episodes"""
@@ -529,6 +582,9 @@ class Solo12ServoSim(SyntheticSolo12Sim):
             raise ValueError("Solo12ServoSim.advance needs the action: the simulator is closed loop")
         if action.dtype != torch.float32 or not action.is_contiguous():
             action = action.float().contiguous()
+        if self._action_table is not None and tuple(action.shape) != (self.N, self.action_width):
+            raise ValueError(f"Solo12ServoSim.advance: the action is {tuple(action.shape)}, the simulator reads "
+                             f"[{self.N}, {self.action_width}]")
         self.cursor = (self.cursor + 1) % 2
         slab = self._slabs[self.cursor]
         d = self._desc
@@ -650,6 +706,18 @@ class CaTEnv:
         kind = str(getattr(syn, "kind", "stream"))
         if kind not in ("stream", "servo"):
             raise ValueError(f"SyntheticCfg.kind must be 'stream' or 'servo', got {kind!r}")
+        # cfg.actions: which action column drives which joint, through which scale, offset and clip, as what kind of target,
+        # is IsaacLab's action block, evaluated inside the simulator's launch ("Actions"); without it column
+        # j is joint j's position target default + servo_action_scale * a.  Built first: its width A is the policy's output
+        # width and the width of a last_action observation term
+        self._action_table = None
+        if getattr(cfg, "actions", None) is not None:
+            if kind != "servo":
+                raise TypeError("cfg.actions needs the closed-loop simulator (SyntheticCfg.kind = 'servo'): the action terms "
+                                "are evaluated inside its launch; the stream simulator is open loop and reads no action")
+            from cat_envs.tasks.utils.mdp import actions as AM
+            self._action_table = AM.build_table(cfg.actions, SOLO12_JOINTS, DEFAULT_JOINT_POS)
+            self.act_dim = max(t["slice"][1] for t in self._action_table[1].values())
         # cfg.observations: the policy's input is a second field of the simulator's row, filled inside its launch (DESIGN
         # section 9, "Observations"); the table is built first because its width is part of the row's layout
         self._obs_field, self._obs_table = "obs", None
@@ -662,7 +730,9 @@ class CaTEnv:
                 raise ValueError(f"cfg.observations reads the simulator's raw observation of {native.SERVO_OBS_RAW} floats: "
                                  f"synthetic.obs_dim is {syn.obs_dim}")
             from cat_envs.tasks.utils.mdp import observation_manager as OM
-            self._obs_table = OM.build_table(OM.policy_group(cfg.observations), SOLO12_JOINTS, DEFAULT_JOINT_POS)
+            self._obs_table = OM.build_table(OM.policy_group(cfg.observations), SOLO12_JOINTS, DEFAULT_JOINT_POS,
+                                             action_terms=None if self._action_table is None else
+                                             {n: t["slice"] for n, t in self._action_table[1].items()})
             self._obs_field, self.obs_dim = "policy_obs", len(self._obs_table[0])
         # cfg.events: pushes, reset ranges and traction are evaluated inside the simulator's launch, too (DESIGN section 9,
         # "Events"); the block is built before the simulator because an error in the cfg should cost no device memory
@@ -720,7 +790,7 @@ class CaTEnv:
                                       self.reset_buf, env_offset=int(getattr(cfg.scene, "env_offset", 0) or 0),
                                       policy_obs_dim=self.obs_dim if self._obs_table is not None else 0,
                                       events=self._event_block is not None, commands=self._command_block is not None,
-                                      terminations=self._term_table is not None)
+                                      terminations=self._term_table is not None, actions=self._action_table is not None)
             self.scene = self.sim.scene
         self.obs_buf = {"policy": self.sim.view(self._obs_field)}
         self._rstep = None
@@ -757,7 +827,12 @@ class CaTEnv:
     # managers --------------------------------------------------------------------------------
     def load_managers(self):
         """reference: cat_env.py:18-40 (constraint manager created after the base managers)"""
-        self.action_manager = _ActionManager(self.num_envs, self.act_dim, self.device)
+        if self._action_table is not None:
+            from cat_envs.tasks.utils.mdp.action_manager import ActionManager
+            self.action_manager = ActionManager(self.cfg.actions, self, self._action_table)
+            print("[INFO] Action Manager: ", self.action_manager)
+        else:
+            self.action_manager = _ActionManager(self.num_envs, self.act_dim, self.device)
         cmd = self.sim.view("command")
         self.command_manager = types.SimpleNamespace(get_command=lambda name: cmd, reset=lambda ids=None: {},
                                                      compute=lambda dt: None)
@@ -870,6 +945,8 @@ class CaTEnv:
             fp["command_terms"] = self.command_manager.fingerprint()
         if getattr(self, "_term_table", None) is not None:             # likewise
             fp["termination_terms"] = self.termination_manager.fingerprint()
+        if getattr(self, "_action_table", None) is not None:           # likewise
+            fp["action_terms"] = self.action_manager.fingerprint()
         return fp
 
     def state_dict(self) -> dict:
@@ -891,6 +968,8 @@ class CaTEnv:
             sd["commands"] = self.command_manager.state_dict()
         if getattr(self, "_term_table", None) is not None:             # the record of the ended episodes and the current params
             sd["terminations"] = self.termination_manager.state_dict()
+        if getattr(self, "_action_table", None) is not None:           # the table's current scales, offsets and clip bounds
+            sd["actions"] = self.action_manager.state_dict()
         return sd
 
     def check_state_dict(self, sd: dict):
@@ -918,6 +997,10 @@ class CaTEnv:
             keys.append("terminations")
         elif "terminations" in sd:
             raise ValueError("run state: it carries terminations, this env has no cfg.terminations")
+        if getattr(self, "_action_table", None) is not None:
+            keys.append("actions")
+        elif "actions" in sd:
+            raise ValueError("run state: it carries actions, this env has no cfg.actions")
         missing = [k for k in keys if k not in sd]
         if missing:
             raise ValueError(f"run state: the env's part lacks {missing}")
@@ -943,6 +1026,8 @@ class CaTEnv:
             self.command_manager.check_state_dict(sd["commands"])
         if getattr(self, "_term_table", None) is not None:
             self.termination_manager.check_state_dict(sd["terminations"])
+        if getattr(self, "_action_table", None) is not None:
+            self.action_manager.check_state_dict(sd["actions"])
 
     def load_state_dict(self, sd: dict):
         """IN PLACE (``copy_`` into the existing tensors, never a rebound attribute): the fused step's argument block, the
@@ -966,6 +1051,8 @@ class CaTEnv:
             self.command_manager.load_state_dict(sd["commands"])
         if getattr(self, "_term_table", None) is not None:
             self.termination_manager.load_state_dict(sd["terminations"])
+        if getattr(self, "_action_table", None) is not None:
+            self.action_manager.load_state_dict(sd["actions"])
         self.curriculum_manager.load_state_dict(sd["curriculum"])      # through set_term_cfg: the next launch carries it
 
     # episode control -------------------------------------------------------------------------

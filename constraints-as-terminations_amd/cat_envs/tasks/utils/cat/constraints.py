@@ -185,8 +185,12 @@ def _d_joint_range(env, limit: float, asset_cfg: SceneEntityCfg):
 
 
 def _d_action_rate(env, limit: float, asset_cfg: SceneEntityCfg):
+    # joint_ids index the action's COLUMNS, as in the reference - also under cfg.actions, where column k need not drive
+    # joint k and there may be fewer columns than joints (all joints = all columns)
     am = env.action_manager
     ids = _ids(asset_cfg.joint_ids, am._action.shape[1])
+    if any(not 0 <= i < am._action.shape[1] for i in ids):
+        raise ValueError(f"action_rate: joint_ids {ids} index the action's columns, and the action has {am._action.shape[1]}")
     return TermDescription(TERM_ACTION_RATE, len(ids), ids, limit, native.f32(env.step_dt), x=am._action,
                            y=am._prev_action)
 

@@ -196,10 +196,12 @@ def export_policy_as_onnx(state_dict, path: str, batch=1) -> str:
     return path
 
 
-def export_policy(state_dict, directory: str, observation_spec=None) -> Dict[str, str]:
+def export_policy(state_dict, directory: str, observation_spec=None, action_spec=None) -> Dict[str, str]:
     """``<directory>/model.onnx`` + ``<directory>/model.pt`` (play.py:111-135).  ``observation_spec`` (a dict, see
     ``ObservationManager.spec``): also ``<directory>/observations.json``, the input contract of the deployed policy -
-    term names, slices, sources, scales, clips and the joint order of the vector the models take"""
+    term names, slices, sources, scales, clips and the joint order of the vector the models take.  ``action_spec`` (a dict,
+    see ``ActionManager.spec``): also ``<directory>/actions.json``, the output contract - per column of the vector the models
+    give: the action term, the joint it drives, the kind of target, scale, offset and clip"""
     out = {"onnx": export_policy_as_onnx(state_dict, os.path.join(directory, "model.onnx")),
            "jit": export_policy_as_jit(state_dict, os.path.join(directory, "model.pt"))}
     if observation_spec is not None:
@@ -207,4 +209,9 @@ def export_policy(state_dict, directory: str, observation_spec=None) -> Dict[str
         out["observations"] = os.path.join(directory, "observations.json")
         with open(out["observations"], "w") as f:
             json.dump(observation_spec, f, indent=1)
+    if action_spec is not None:
+        import json
+        out["actions"] = os.path.join(directory, "actions.json")
+        with open(out["actions"], "w") as f:
+            json.dump(action_spec, f, indent=1)
     return out

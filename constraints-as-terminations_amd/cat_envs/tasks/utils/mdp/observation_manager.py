@@ -37,12 +37,13 @@ def group_items(group_cfg):
                                                                     "flatten_history_dim")]
 
 
-def build_table(group_cfg, joint_names, default_joint_pos=None):
+def build_table(group_cfg, joint_names, default_joint_pos=None, action_terms=None):
     """(entries, group_obs_term_dim) from an observation group cfg and the robot's joint names; pure, needs no device.
     ``entries``: one ``(src, flags, bias, noise_lo, noise_width, clip_lo, clip_hi, scale)`` per float of the policy
     observation, terms concatenated in cfg order, every float already rounded to fp32; the noise bit is set for every term
     that has a noise cfg (the corruption switch masks it later).  ``group_obs_term_dim``: ``{term name: (width,)}`` in the
-    same order.  ``ValueError``s name the term."""
+    same order.  ``ValueError``s name the term.  ``action_terms`` (envs with ``cfg.actions``): ``{term: (first column, end)}``
+    of the action block - a ``last_action`` term then has the block's width, or with ``action_name`` that term's columns."""
     import types
     if default_joint_pos is None:
         from cat_envs.tasks.utils.cat.cat_env import DEFAULT_JOINT_POS as default_joint_pos
@@ -50,7 +51,7 @@ def build_table(group_cfg, joint_names, default_joint_pos=None):
         raise ValueError("observation group: concatenate_terms=False is not supported; the policy observation is one "
                          "concatenated field of the simulator's row")
     env = types.SimpleNamespace(scene={"robot": types.SimpleNamespace(joint_names=list(joint_names), body_names=[])},
-                                default_joint_pos=[float(v) for v in default_joint_pos])
+                                default_joint_pos=[float(v) for v in default_joint_pos], action_terms=action_terms)
     entries, dims = [], {}
     for name, term in group_items(group_cfg):
         if not isinstance(term, ObservationTermCfg):
@@ -60,7 +61,10 @@ def build_table(group_cfg, joint_names, default_joint_pos=None):
             raise ValueError(f"observation term '{name}': {getattr(term.func, '__name__', term.func)!r} has no describe(); "
                              f"the servo task evaluates observations inside the simulator launch and runs no Python "
                              f"observation function")
-        pairs = list(describe(env, **(term.params or {})))
+        try:
+            pairs = list(describe(env, **(term.params or {})))
+        except KeyError as e:
+            raise ValueError(f"observation term '{name}': {e.args[0]}") from e
         width = len(pairs)
         scale = term.scale
         if scale is None:

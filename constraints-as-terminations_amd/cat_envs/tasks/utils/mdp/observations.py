@@ -83,7 +83,20 @@ def joint_vel_rel(env, asset_cfg=None):
     _refuse("joint_vel_rel")
 
 
-@_term(lambda env, action_name=None: [(RAW_ACTION + j, None) for j in range(NUM_JOINTS)])
+def _action_cols(env, action_name):
+    """the columns of the raw action a ``last_action`` term shows: all twelve without ``cfg.actions``; with it the block's
+    A columns, or those of the term ``action_name``"""
+    terms = getattr(env, "action_terms", None)
+    if terms is None:
+        return range(NUM_JOINTS)
+    if action_name is None:
+        return range(max(b for _, b in terms.values()))
+    if action_name not in terms:
+        raise KeyError(f"action_name '{action_name}' names no action term of cfg.actions ({list(terms)})")
+    return range(*terms[action_name])
+
+
+@_term(lambda env, action_name=None: [(RAW_ACTION + k, None) for k in _action_cols(env, action_name)])
 def last_action(env, action_name=None):
-    """the action of the step that led to this state (zero in the first state of an episode)"""
+    """the raw action of the step that led to this state, in column order (zero in the first state of an episode)"""
     _refuse("last_action")

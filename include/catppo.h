@@ -729,7 +729,7 @@ typedef struct catppo_servo_sim {
   const uint8_t* reset;                  /* [N] */
   const int64_t* episode_length;         /* [N], before this step's increment */
   int64_t max_episode_length;
-  int32_t decimation, resample_steps, init, reserved;   /* reserved: 0 or one of CATPPO_SERVO_EXT_OBS / _EVENTS / _COMMANDS / _TERMINATIONS (see below) */
+  int32_t decimation, resample_steps, init, reserved;   /* reserved: 0 or one of CATPPO_SERVO_EXT_OBS / _EVENTS / _COMMANDS / _TERMINATIONS / _ACTIONS (see below) */
   uint64_t seed;
   float default_joint_pos[12];
   float dt, kp, kd, inertia, tau_max, action_scale, vel_alpha, tilt_beta, tilt_max, reward_scale, foot_clearance,
@@ -941,6 +941,53 @@ typedef struct catppo_servo_sim_terminations {
   catppo_servo_commands cmd;              /* block NULL and floats 0: no commands */
   catppo_servo_terminations term;
 } catppo_servo_sim_terminations;
+
+/* Actions ("Actions").  desc->reserved == CATPPO_SERVO_EXT_ACTIONS: `desc` is the head of a
+ * catppo_servo_sim_actions, i.e. the observation, event, command, termination and action descriptors lie behind the 368
+ * bytes.  Under this value term.table == NULL with term.terms == 0 means "no terminations" (the three blocks before it are
+ * marked absent as under CATPPO_SERVO_EXT_TERMINATIONS); otherwise the four are checked and used exactly as under that
+ * value.  Every older value of `reserved` keeps its meaning.
+ * act.table is a DEVICE array of 12 entries of 32 bytes, one per simulator joint j (lane j), 16-byte aligned, read by every
+ * launch that is no init launch (values the host rewrites in stream order are in the next launch, under graph replay too).
+ * act.width = A, 1 <= A <= 12, is the width of the action: sim.action is [N, A].  Entry j: col in -1 .. A - 1 is the action
+ * column that drives joint j (-1: none; the kernel clamps it into 0 .. A - 1 before it is used, whatever the table holds),
+ * flags & CATPPO_SERVO_ACTION_KIND_MASK the kind, flags & CATPPO_SERVO_ACTION_CLIP the clip bit.  fp32, unfused:
+ *   raw = action[e * A + col]       p = raw * scale + offset       clip bit: p = p < clip_lo ? clip_lo : p, then
+ *                                                                            p = p > clip_hi ? clip_hi : p
+ * and per substep, before the clamp to +- tau_max (which, like qdd, the integration and the choice of the reported
+ * substep, stays as it is):
+ *   0 not driven                    tau = kp * (def - q) - kd * qd
+ *   1 JointPositionAction           tau = kp * (p - q) - kd * qd
+ *   2 RelativeJointPositionAction   tau = kp * ((p + q) - q) - kd * qd       (q of this substep; sum and difference rounded)
+ *   3 JointVelocityAction           tau = kd * (p - qd)                      (no position gain on such a joint)
+ *   4 JointEffortAction             tau = p
+ * The raw action by column is what the rest of the step calls `a`: obs[33 + k], trace float 60 + k and reward kinds 11 / 12
+ * read column k for k < A and zero for k >= A.  sim.action_scale is unused.  With col = j, kind 1, scale = action_scale,
+ * offset = default_joint_pos[j] and no clip the launch computes the bits of the launch without the descriptor.
+ * The table's writer checks its entries (Solo12ServoSim.set_action_table); whatever it holds the launch stays inside the
+ * action's row: col is clamped, an unknown kind is "not driven", the rest are values. */
+#define CATPPO_SERVO_EXT_ACTIONS 0x41435431        /* "ACT1": value of catppo_servo_sim.reserved that announces catppo_servo_sim_actions */
+#define CATPPO_SERVO_ACTION_KIND_MASK 0x7u
+#define CATPPO_SERVO_ACTION_CLIP 0x8u
+typedef struct catppo_servo_action_entry {
+  int32_t col;                            /* -1 .. A - 1 */
+  uint32_t flags;                         /* kind | CATPPO_SERVO_ACTION_CLIP */
+  float scale, offset, clip_lo, clip_hi;
+  uint32_t zero[2];
+} catppo_servo_action_entry;
+typedef struct catppo_servo_actions {
+  const catppo_servo_action_entry* table; /* DEVICE array [12], 16-byte aligned */
+  int32_t width;                          /* A: 1 .. 12 */
+  int32_t reserved;                       /* 0 */
+} catppo_servo_actions;
+typedef struct catppo_servo_sim_actions {
+  catppo_servo_sim sim;                   /* sim.reserved = CATPPO_SERVO_EXT_ACTIONS */
+  catppo_servo_obs obs;                   /* width 0 and table NULL: no observation table */
+  catppo_servo_events ev;                 /* block NULL and floats 0: no events */
+  catppo_servo_commands cmd;              /* block NULL and floats 0: no commands */
+  catppo_servo_terminations term;         /* table NULL and terms 0: no terminations */
+  catppo_servo_actions act;
+} catppo_servo_sim_actions;
 
 /* ---- test hook (ABI 0.6) ------------------------------------------------------------------------------------------
  * buf != NULL ([2][M] int32, device): the head / loss kernel of every following catppo_ppo_minibatch_* call writes the clip

@@ -113,12 +113,16 @@ def main(argv=None):
 
     from cat_envs.tasks.utils.cleanrl.export import export_policy
     om = getattr(env.unwrapped, "observation_manager", None)
+    am = env.unwrapped.action_manager                   # envs with cfg.actions: the manager that knows the output contract
     exported = export_policy(actor.state_dict(), os.path.join(os.path.dirname(resume_path), "exported"),
-                             observation_spec=None if om is None else om.spec())
+                             observation_spec=None if om is None else om.spec(),
+                             action_spec=am.spec() if hasattr(am, "spec") else None)
     print(f"[INFO] Exported ONNX model to {exported['onnx']}")
     print(f"[INFO] Exported .pt model to {exported['jit']}")
     if om is not None:
         print(f"[INFO] Wrote the policy's input contract to {exported['observations']}")
+    if "actions" in exported:
+        print(f"[INFO] Wrote the policy's output contract to {exported['actions']}")
 
     obs = env.reset()[0]["policy"]
     ret = 0.0

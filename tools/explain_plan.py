@@ -11,10 +11,11 @@ BASELINE shapes (profiles/r5_explain_plan.txt is this output).
     python tools/explain_plan.py --task Isaac-Velocity-CaT-Flat-Solo12-Servo-Reference-v0        (needs no device)
 
 names the instance of the servo simulator's kernel a task's training step launches: which of ``cfg.rewards``,
-``cfg.observations``, ``cfg.events``, ``cfg.commands`` and ``cfg.terminations`` (``RewardsCfg``, ``ObservationsCfg``, ``EventCfg``,
-``CommandsCfg``, ``TerminationsCfg``) the cfg carries decides the kernel's template pack (csrc/servo_sim.hip).
+``cfg.observations``, ``cfg.events``, ``cfg.commands``, ``cfg.terminations`` and ``cfg.actions`` (``RewardsCfg``, ``ObservationsCfg``,
+``EventCfg``, ``CommandsCfg``, ``TerminationsCfg``, ``ActionsCfg``) the cfg carries decides the kernel's template pack
+(csrc/servo_sim_kernel.h, instantiated in servo_sim.hip and, with actions, servo_sim_actions.hip).
 The servo tasks are ``...-Solo12-Servo-v0`` and its ``-Rewards``, ``-Obs``, ``-Events``, ``-Full``, ``-Commands``, ``-Reference``,
-``-Terminations`` and ``-Reference-Terminations`` variants."""
+``-Terminations``, ``-Reference-Terminations``, ``-Actions`` and ``-Reference-Actions`` variants."""
 import argparse
 import os
 import sys
@@ -69,9 +70,10 @@ def explain_task(task):
     cfg = load_cfg_from_registry(task, "env_cfg_entry_point")
     if str(getattr(cfg.synthetic, "kind", "stream")) != "servo":
         return f"== {task}: the stream simulator (no simulator kernel; the state is a pre-generated stream)"
-    has = {k: getattr(cfg, k, None) is not None for k in ("rewards", "observations", "events", "commands", "terminations")}
+    has = {k: getattr(cfg, k, None) is not None for k in ("rewards", "observations", "events", "commands", "terminations", "actions")}
     pack = [name for key, name in (("observations", "catppo_servo_obs"), ("events", "catppo_servo_events"),
-                                   ("commands", "catppo_servo_commands"), ("terminations", "catppo_servo_terminations")) if has[key]]
+                                   ("commands", "catppo_servo_commands"), ("terminations", "catppo_servo_terminations"),
+                                   ("actions", "catppo_servo_actions")) if has[key]]
     row = 308 + (48 if has["observations"] else 0) + (4 if has["commands"] else 0) + (4 if has["terminations"] else 0)
     out = [f"== {task}: " + ", ".join(f"cfg.{k} {'set' if v else 'unset'}" for k, v in has.items()),
            f"servo_sim_kernel<kTrain, {'true' if has['rewards'] else 'false'}{''.join(', ' + n for n in pack)}>: row of {row} floats "
@@ -87,6 +89,14 @@ def explain_task(task):
         kinds = {v: k for k, v in TM.K.items()}
         for name, kind, mask, p0, p1 in TM.build_table(cfg.terminations, E.SOLO12_JOINTS, E.SOLO12_BODIES):
             out.append(f"termination term '{name}' ({kinds[kind]}{', time_out' if kind == 1 else ''}): mask {mask:#x}, p0 {p0:g}, p1 {p1:g}")
+    if has["actions"]:
+        import cat_envs.tasks.utils.cat.cat_env as E
+        from cat_envs.tasks.utils.mdp import actions as AM
+        entries, terms = AM.build_table(cfg.actions, E.SOLO12_JOINTS, E.DEFAULT_JOINT_POS)
+        out.append(f"action block (servo_sim_actions.hip): {max(t['slice'][1] for t in terms.values())} columns, terms "
+                   + ", ".join(f"'{n}' ({t['kind']}, columns {t['slice'][0]}..{t['slice'][1] - 1})" for n, t in terms.items()))
+        for c in AM.action_spec(entries, terms, E.SOLO12_JOINTS)["columns"]:
+            out.append(f"  column {c['column']:2d} -> {c['joint']:<7s} {c['kind']}: scale {c['scale']:g}, offset {c['offset']:g}, clip {c['clip']}")
     return "\n".join(out)
 
 

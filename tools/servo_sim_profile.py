@@ -30,6 +30,10 @@ alternating in one session, every run listed.
 time_out, base_contact on base_link and the upper legs, upside_down at 0.1), so that the simulator's launch is the
 terminations-on training instance; the values are the reference's own.  profiles/servo_terminations_kernel_stats.csv: the
 parent's library, this library without the flag and this library with --terminations, alternating in one session, every run listed.
+--actions runs the task with the reference's action block (Isaac-Velocity-CaT-Flat-Solo12-Servo-Actions-v0: one joint position
+term over the twelve joints in the order FL FR HR HL, scale 0.5, default offsets), so that the simulator's launch is the
+actions-on training instance; the values are the reference's own.  profiles/servo_actions_kernel_stats.csv: the parent's
+library, this library without the flag and this library with --actions, alternating in one session, every run listed.
 
 Per env step the trace shows servo_sim_kernel (the simulator), the two launches of catppo_rollout_pre, the one of
 catppo_rollout_post and the policy forward."""
@@ -55,9 +59,10 @@ def main():
     ap.add_argument("--events", action="store_true", help="the task with EventCfg (push probability 0.01): events inside the simulator launch")
     ap.add_argument("--commands", action="store_true", help="the task with CommandsCfg (p_move 0.01): the command term inside the simulator launch")
     ap.add_argument("--terminations", action="store_true", help="the task with TerminationsCfg: termination terms inside the simulator launch")
+    ap.add_argument("--actions", action="store_true", help="the task with ActionsCfg: joint action terms inside the simulator launch")
     a = ap.parse_args()
-    if a.obs + a.rewards + a.events + a.commands + a.terminations > 1:
-        ap.error("--obs, --rewards, --events, --commands and --terminations are separate arms")
+    if a.obs + a.rewards + a.events + a.commands + a.terminations + a.actions > 1:
+        ap.error("--obs, --rewards, --events, --commands, --terminations and --actions are separate arms")
     import cat_envs.tasks  # noqa: F401
     from cat_envs.shim import load_cfg_from_registry, make
     from cat_envs.tasks.utils.cleanrl.ppo import PPOTrainer
@@ -65,7 +70,8 @@ def main():
             "Isaac-Velocity-CaT-Flat-Solo12-Servo-Obs-v0" if a.obs else
             "Isaac-Velocity-CaT-Flat-Solo12-Servo-Events-v0" if a.events else
             "Isaac-Velocity-CaT-Flat-Solo12-Servo-Commands-v0" if a.commands else
-            "Isaac-Velocity-CaT-Flat-Solo12-Servo-Terminations-v0" if a.terminations else "Isaac-Velocity-CaT-Flat-Solo12-Servo-v0")
+            "Isaac-Velocity-CaT-Flat-Solo12-Servo-Terminations-v0" if a.terminations else
+            "Isaac-Velocity-CaT-Flat-Solo12-Servo-Actions-v0" if a.actions else "Isaac-Velocity-CaT-Flat-Solo12-Servo-v0")
     env_cfg = load_cfg_from_registry(task, "env_cfg_entry_point")
     if a.rewards:
         from cat_envs.tasks.locomotion.velocity.config.solo12.cat_flat_env_cfg import ShapedRewardsCfg
@@ -120,6 +126,10 @@ def main():
     if a.terminations:
         tm = env_u.termination_manager
         print(f"terminations: {tm.active_terms}, row of {env_u.sim.F} floats, shares of the ended episodes {tm.pop_log()}")
+    if a.actions:
+        am = env_u.action_manager
+        print(f"actions: {am.active_terms}, {am.total_action_dim} columns, row of {env_u.sim.F} floats, columns -> joints "
+              f"{[c['joint'] for c in am.spec()['columns']]}")
     if a.eval or a.trace:
         steps = record[:, 0].cpu()
         assert float(steps.min()) == float(steps.max()) == a.rollouts * trainer.T, (float(steps.min()), float(steps.max()))
