@@ -268,6 +268,31 @@ class ServoSimActions(ServoSimTerminations):
     _fields_ = [("act", ServoActions)]
 
 
+SERVO_EXT_ACTUATORS = 0x41435531        # CATPPO_SERVO_EXT_ACTUATORS: ``reserved`` of a descriptor followed by all five and the actuators
+SERVO_ACTUATOR_DC_MOTOR = 0x1           # CATPPO_SERVO_ACTUATOR_DC_MOTOR: the one bit of an actuator entry's flags
+SERVO_ACT_HIST_FLOATS = 48              # CATPPO_SERVO_ACT_HIST_FLOATS: the row's history field, 3 slots of 16 floats
+SERVO_ACTUATOR_MAX_LAG_STEPS = 3        # the history reaches back three control steps: max_delay <= 3 * decimation
+
+
+class ServoActuatorEntry(C.Structure):
+    """catppo_servo_actuator_entry: entry j of the device-resident actuator table, the actuator of simulator joint j;
+    ``delay`` = min | max << 8 | group << 16"""
+    _fields_ = [("kp", C.c_float), ("kd", C.c_float), ("inertia", C.c_float), ("effort_limit", C.c_float),
+                ("saturation_effort", C.c_float), ("velocity_limit", C.c_float), ("flags", C.c_uint32), ("delay", C.c_uint32)]
+
+
+class ServoActuators(C.Structure):
+    """catppo_servo_actuators: the actuator descriptor; ``table`` is a device array of 12 ``ServoActuatorEntry``,
+    ``off_act_hist`` the row's 48-float field (three slots of processed actions)"""
+    _fields_ = [("table", C.c_void_p), ("off_act_hist", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ServoSimActuators(ServoSimActions):
+    """catppo_servo_sim_actuators: a ``ServoSimActions`` (whose action table is never NULL here) and a ``ServoActuators``
+    behind it; the library reads all six while ``reserved`` is ``SERVO_EXT_ACTUATORS``"""
+    _fields_ = [("actu", ServoActuators)]
+
+
 F32, F16, F64 = 0, 1, 2                 # CATPPO_F32 / _F16 / _F64
 SUM, MAX = 0, 1                         # CATPPO_SUM / _MAX
 LR_FIXED, LR_LINEAR, LR_KEEP = 0, 1, 2
@@ -880,6 +905,8 @@ class Native:
             raise TypeError("servo_sim_step: a descriptor whose 'reserved' announces terminations must be a native.ServoSimTerminations")
         if desc.reserved == SERVO_EXT_ACTIONS and not isinstance(desc, ServoSimActions):   # ... and a catppo_servo_actions
             raise TypeError("servo_sim_step: a descriptor whose 'reserved' announces actions must be a native.ServoSimActions")
+        if desc.reserved == SERVO_EXT_ACTUATORS and not isinstance(desc, ServoSimActuators):   # ... and a catppo_servo_actuators
+            raise TypeError("servo_sim_step: a descriptor whose 'reserved' announces actuators must be a native.ServoSimActuators")
         rc = self.lib.catppo_servo_sim_step(self.h, C.byref(desc), self._stream())
         if rc:
             self._ok(rc)

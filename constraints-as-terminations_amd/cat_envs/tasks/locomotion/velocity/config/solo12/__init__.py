@@ -134,3 +134,20 @@ for _name, _cfg in (("Actions", "Solo12ServoActionsFlatEnvCfg"), ("Reference-Act
         disable_env_checker=True,
         kwargs={"env_cfg_entry_point": f"{__name__}.cat_flat_env_cfg:{_cfg}_PLAY", **_KW},
     )
+
+# the servo task with a robot: the reference's actuators inside the simulator's launch ("Actuators");
+# "Reference-Actuators" is all six MDP blocks and the robot, "DelayedActuators" the same gains behind an actuator delay
+for _name, _cfg in (("Actuators", "Solo12ServoActuatorsFlatEnvCfg"), ("Reference-Actuators", "Solo12ServoReferenceActuatorsFlatEnvCfg"),
+                    ("DelayedActuators", "Solo12ServoDelayedActuatorsFlatEnvCfg")):
+    register(
+        id=f"Isaac-Velocity-CaT-Flat-Solo12-Servo-{_name}-v0",
+        entry_point=CaTEnv,
+        disable_env_checker=True,
+        kwargs={"env_cfg_entry_point": f"{__name__}.cat_flat_env_cfg:{_cfg}", **_KW},
+    )
+    register(
+        id=f"Isaac-Velocity-CaT-Flat-Solo12-Servo-{_name}-Play-v0",
+        entry_point=CaTEnv,
+        disable_env_checker=True,
+        kwargs={"env_cfg_entry_point": f"{__name__}.cat_flat_env_cfg:{_cfg}_PLAY", **_KW},
+    )

@@ -17,16 +17,20 @@ Terminations: ``TerminationsCfg`` (the reference's three terms and values) likew
 DESIGN section 9 "Terminations"); ``Solo12ServoReferenceTerminationsFlatEnvCfg`` is all five blocks.
 Actions: ``ActionsCfg`` (the reference's ``JointPositionActionCfg`` and values) likewise (``Solo12ServoActionsFlatEnvCfg``,
 DESIGN section 9 "Actions"); ``Solo12ServoReferenceActionsFlatEnvCfg`` is all six blocks.
+Actuators: ``scene.robot`` (the reference's ``SOLO12_MINIMAL_CFG``: one ideal PD group, its gains, armature and limits)
+likewise (``Solo12ServoActuatorsFlatEnvCfg``, DESIGN section 9 "Actuators"); ``Solo12ServoReferenceActuatorsFlatEnvCfg`` is
+all six blocks and the robot, ``Solo12ServoDelayedActuatorsFlatEnvCfg`` the same gains behind an actuator delay.
 """
 import math
 
+from cat_envs.assets.odri import SOLO12_MINIMAL_CFG
 from cat_envs.shim import AdditiveUniformNoiseCfg as Unoise
 from cat_envs.shim import CurriculumTermCfg as CurrTerm
 from cat_envs.shim import EventTermCfg as EventTerm
 from cat_envs.shim import ObservationGroupCfg as ObsGroup
 from cat_envs.shim import ObservationTermCfg as ObsTerm
 from cat_envs.shim import RewardTermCfg as RewTerm
-from cat_envs.shim import SceneEntityCfg, configclass
+from cat_envs.shim import DelayedPDActuatorCfg, SceneEntityCfg, configclass
 from cat_envs.shim import TerminationTermCfg as DoneTerm
 from cat_envs.tasks.utils.cat import constraints, curriculums
 from cat_envs.tasks.utils.cat.manager_constraint_cfg import ConstraintTermCfg as ConstraintTerm
@@ -150,6 +154,7 @@ class SceneCfg:
     num_envs: int = 4096
     env_spacing: float = 3.0
     env_offset: int = 0          # global id of this process's first env (env-sharded runs of the servo simulator)
+    robot: object = None         # an ArticulationCfg: its actuators are evaluated inside the servo simulator's launch
 
 
 @configclass
@@ -458,6 +463,48 @@ class Solo12ServoReferenceActionsFlatEnvCfg(Solo12ServoReferenceTerminationsFlat
 @configclass
 class Solo12ServoReferenceActionsFlatEnvCfg_PLAY(Solo12ServoReferenceTerminationsFlatEnvCfg_PLAY):
     actions: ActionsCfg = ActionsCfg()
+
+
+def _delayed(robot, min_delay, max_delay):
+    """``robot`` with every actuator group turned into a ``DelayedPDActuatorCfg`` of the same joints, gains and limits"""
+    fields = ("joint_names_expr", "effort_limit", "velocity_limit", "stiffness", "damping", "armature", "friction")
+    return robot.replace(actuators={n: DelayedPDActuatorCfg(**{f: getattr(a, f) for f in fields}, min_delay=min_delay,
+                                                            max_delay=max_delay) for n, a in robot.actuators.items()})
+
+
+@configclass
+class Solo12ServoActuatorsFlatEnvCfg(Solo12ServoFlatEnvCfg):
+    """the servo task with the reference's robot: the simulator's launch evaluates its actuators"""
+    scene: SceneCfg = SceneCfg(num_envs=4096, env_spacing=3.0, robot=SOLO12_MINIMAL_CFG)
+
+
+@configclass
+class Solo12ServoActuatorsFlatEnvCfg_PLAY(Solo12ServoActuatorsFlatEnvCfg):
+    scene: SceneCfg = SceneCfg(num_envs=50, env_spacing=3.0, robot=SOLO12_MINIMAL_CFG)
+    curriculum: object = None
+
+
+@configclass
+class Solo12ServoReferenceActuatorsFlatEnvCfg(Solo12ServoReferenceActionsFlatEnvCfg):
+    """every MDP block of the reference's cfg and the reference's robot"""
+    scene: SceneCfg = SceneCfg(num_envs=4096, env_spacing=3.0, robot=SOLO12_MINIMAL_CFG)
+
+
+@configclass
+class Solo12ServoReferenceActuatorsFlatEnvCfg_PLAY(Solo12ServoReferenceActionsFlatEnvCfg_PLAY):
+    scene: SceneCfg = SceneCfg(num_envs=50, env_spacing=3.0, robot=SOLO12_MINIMAL_CFG)
+
+
+@configclass
+class Solo12ServoDelayedActuatorsFlatEnvCfg(Solo12ServoFlatEnvCfg):
+    """the reference's gains behind an actuator delay of 0 .. 4 physics steps (up to one control step), drawn per episode"""
+    scene: SceneCfg = SceneCfg(num_envs=4096, env_spacing=3.0, robot=_delayed(SOLO12_MINIMAL_CFG, 0, 4))
+
+
+@configclass
+class Solo12ServoDelayedActuatorsFlatEnvCfg_PLAY(Solo12ServoDelayedActuatorsFlatEnvCfg):
+    scene: SceneCfg = SceneCfg(num_envs=50, env_spacing=3.0, robot=_delayed(SOLO12_MINIMAL_CFG, 0, 4))
+    curriculum: object = None
 
 
 @configclass

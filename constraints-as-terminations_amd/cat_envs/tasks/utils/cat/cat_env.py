@@ -185,7 +185,7 @@ class Solo12ServoSim(SyntheticSolo12Sim):
     def __init__(self, num_envs: int, obs_dim: int, device, seed: int, syn, dt: float, decimation: int,
                  max_episode_length: int, episode_length: torch.Tensor, reset: torch.Tensor, env_offset: int = 0,
                  policy_obs_dim: int = 0, events: bool = False, commands: bool = False, terminations: bool = False,
-                 actions: bool = False):
+                 actions: bool = False, actuators: bool = False):
         """``policy_obs_dim`` = P > 0: the row gets a second observation field ``policy_obs`` of P floats (padded to a
         multiple of 4) that ``set_observation_table`` configures; the raw field ``obs`` stays what it is.
         ``events``: the descriptor carries the event descriptor, too, and ``set_event_block`` configures it.
@@ -195,7 +195,11 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         fired in the step, bit k = term k), the descriptor carries the termination descriptor and
         ``set_termination_table`` configures it.
         ``actions``: the descriptor carries the action descriptor and ``set_action_table`` configures it (which action
-        column drives which joint, through which scale, offset and clip, as what kind of target); the row stays what it is"""
+        column drives which joint, through which scale, offset and clip, as what kind of target); the row stays what it is.
+        ``actuators``: the row gets one more field ``act_hist`` of 48 floats behind everything else (three slots of processed
+        actions), the descriptor carries the action and the actuator descriptors and ``set_actuator_table`` configures the
+        latter (per-joint gains, inertia, effort limits, DC-motor clamps and the actuator delay)"""
+        actions = bool(actions or actuators)
         self.N, self.D, self.device = num_envs, obs_dim, torch.device(device)
         self.P = int(policy_obs_dim)
         if self.P and not (1 <= self.P <= native.SERVO_OBS_MAX_WIDTH and obs_dim == native.SERVO_OBS_RAW):
@@ -221,6 +225,9 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         if terminations:
             self.off["term_state"] = (self.F, 4)
             self.F += 4
+        if actuators:
+            self.off["act_hist"] = (self.F, native.SERVO_ACT_HIST_FLOATS)
+            self.F += native.SERVO_ACT_HIST_FLOATS
         self.cur = torch.zeros(num_envs, self.F, device=self.device)
         self._slabs = [torch.zeros(num_envs, self.F, device=self.device) for _ in range(2)]
         self.cursor = -1
@@ -228,7 +235,7 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         self._episode_length, self._reset = episode_length, reset       # referenced by the descriptor: keep alive
         self._nat = native.get(self.device)
         # with a policy observation the descriptor carries the observation descriptor behind its 368 bytes
-        d = self._desc = (native.ServoSimActions() if actions else native.ServoSimTerminations() if terminations
+        d = self._desc = (native.ServoSimActuators() if actuators else native.ServoSimActions() if actions else native.ServoSimTerminations() if terminations
                           else native.ServoSimCommands() if commands else native.ServoSimEvents() if events
                           else native.ServoSimObs() if self.P else native.ServoSimRewards())
         d.N, d.env_offset, d.row_stride, d.row_floats = num_envs, int(env_offset), self.F, self.F
@@ -258,6 +265,8 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         self._term_entries = []
         self._actions = bool(actions)
         self._action_table, self._action_entries, self.action_width = None, [], J   # device table of the action descriptor
+        self._actuators = bool(actuators)
+        self._actuator_table, self._actuator_entries = None, []         # device table of the actuator descriptor
         self._build_scene()
 
     def _table(self, t, width, what, lead=()):
@@ -426,7 +435,8 @@ class Solo12ServoSim(SyntheticSolo12Sim):
 
     def _announce(self):
         """``reserved`` names the descriptors behind the 368 bytes that are configured by now"""
-        self._desc.reserved = (native.SERVO_EXT_ACTIONS if self._action_table is not None
+        self._desc.reserved = (native.SERVO_EXT_ACTUATORS if self._actuator_table is not None
+                               else native.SERVO_EXT_ACTIONS if self._action_table is not None
                                else native.SERVO_EXT_TERMINATIONS if self._term_table is not None
                                else native.SERVO_EXT_COMMANDS if self._command_block is not None
                                else native.SERVO_EXT_EVENTS if self._event_block is not None
@@ -554,6 +564,69 @@ class Solo12ServoSim(SyntheticSolo12Sim):
             self._announce()                                            # from now on every launch reads the table
         self._action_table.copy_(torch.frombuffer(bytearray(host), dtype=torch.uint8))
         self._action_entries = entries
+
+    def identity_actuator_entries(self):
+        """the table that must change nothing: the descriptor's own scalars on every joint, ideal PD, no delay"""
+        d = self._desc
+        return [dict(kp=float(d.kp), kd=float(d.kd), inertia=float(d.inertia), effort_limit=float(d.tau_max))] * self.J
+
+    def set_actuator_table(self, entries):
+        """``entries``: 12 dicts, one per simulator joint, with ``kp``, ``kd``, ``inertia`` (link inertia + armature),
+        ``effort_limit`` and optionally ``saturation_effort``, ``velocity_limit``, ``dc_motor``, ``min_delay``, ``max_delay``
+        (physics steps) and ``group`` (what ``mdp.actuators.build_table`` returns).  Every following step takes joint j's gains,
+        inertia and clamp from entry j and lets its processed action act ``min_delay .. max_delay`` physics steps late, inside
+        the simulator's own launch.  The table lives on the device and is rewritten here and nowhere else, in stream order:
+        new gains and limits are in the next launch.  Kinds, groups and delay ranges are fixed by the first call.  A
+        simulator without an action table gets the identity one here, so ``set_action_table`` comes first where it is
+        wanted.  The entries are checked here - the library cannot read them."""
+        if not self._actuators:
+            raise ValueError("this simulator was built without an actuator descriptor (actuators = False)")
+        entries = [dict(e) for e in (entries or [])]
+        if len(entries) != self.J:
+            raise ValueError(f"the actuator table has one entry per joint ({self.J}), got {len(entries)}")
+        max_lag = native.SERVO_ACTUATOR_MAX_LAG_STEPS * int(self._desc.decimation)
+        rows, ranges = [], {}
+        for j, e in enumerate(entries):
+            unknown = set(e) - {"kp", "kd", "inertia", "effort_limit", "saturation_effort", "velocity_limit", "dc_motor",
+                                "min_delay", "max_delay", "group"}
+            if unknown:
+                raise ValueError(f"joint {j}: unknown actuator fields {sorted(unknown)}")
+            vals = [float(e[k]) for k in ("kp", "kd", "inertia", "effort_limit")]
+            vals += [float(e.get("saturation_effort") or 0.0), float(e.get("velocity_limit") or 0.0)]
+            dc = bool(e.get("dc_motor", False))
+            mn, mx, g = int(e.get("min_delay", 0)), int(e.get("max_delay", 0)), int(e.get("group", 0))
+            if not all(math.isfinite(v) and v >= 0.0 for v in vals):
+                raise ValueError(f"joint {j}: gains, inertia and limits must be finite and >= 0, got {e!r}")
+            if not vals[2] > 0.0:
+                raise ValueError(f"joint {j}: inertia must be > 0, got {vals[2]}")
+            if dc and not (vals[4] > 0.0 and vals[5] > 0.0):
+                raise ValueError(f"joint {j}: a DC motor needs saturation_effort > 0 and velocity_limit > 0, got {e!r}")
+            if not (0 <= mn <= mx <= max_lag and mx <= 255):
+                raise ValueError(f"joint {j}: the delay needs 0 <= min_delay <= max_delay <= {min(max_lag, 255)} physics steps "
+                                 f"(three control steps), got {mn} .. {mx}")
+            if not 0 <= g <= 255:
+                raise ValueError(f"joint {j}: the group index must be in 0 .. 255, got {g}")
+            if ranges.setdefault(g, (mn, mx)) != (mn, mx):
+                raise ValueError(f"joint {j}: the joints of group {g} share one lag, so one delay range; got {ranges[g]} and {(mn, mx)}")
+            rows.append((*vals, dc, mn, mx, g))
+        fixed = [r[6:] for r in rows]
+        if self._actuator_entries and fixed != [r[6:] for r in self._actuator_entries]:
+            raise ValueError("the actuator table's kinds, groups and delay ranges are fixed by the first call; only gains, inertia "
+                             "and limits may change")
+        host = (native.ServoActuatorEntry * self.J)()
+        for h, (kp, kd, inertia, eff, sat, vlim, dc, mn, mx, g) in zip(host, rows):
+            h.kp, h.kd, h.inertia, h.effort_limit, h.saturation_effort, h.velocity_limit = kp, kd, inertia, eff, sat, vlim
+            h.flags, h.delay = (native.SERVO_ACTUATOR_DC_MOTOR if dc else 0), mn | mx << 8 | g << 16
+        if self._actuator_table is None:
+            if self._action_table is None:                              # the identity action table (byte-identical to none)
+                self.set_action_table([(j, native.SERVO_ACTION_KINDS["joint_position"], float(self._desc.action_scale),
+                                        float(self._desc.default_joint_pos[j]), None) for j in range(self.J)], self.J)
+            self._actuator_table = torch.zeros(C.sizeof(host), dtype=torch.uint8, device=self.device)
+            a = self._desc.actu
+            a.table, a.off_act_hist, a.reserved = self._actuator_table.data_ptr(), self.off["act_hist"][0], 0
+            self._announce()                                            # from now on every launch reads the table
+        self._actuator_table.copy_(torch.frombuffer(bytearray(host), dtype=torch.uint8))
+        self._actuator_entries = rows
 
     @property
     def termination_record(self):
@@ -763,6 +836,16 @@ class CaTEnv:
                                 "terms are evaluated inside its launch; the stream simulator's resets are a pre-generated stream")
             from cat_envs.tasks.utils.mdp import terminations as TM
             self._term_table = TM.build_table(cfg.terminations, SOLO12_JOINTS, SOLO12_BODIES)
+        # cfg.scene.robot: the robot's actuators - per-joint gains, armature, effort limits, a DC motor's curve, the actuator
+        # delay - are IsaacLab's ArticulationCfg, evaluated inside the simulator's launch ("Actuators");
+        # without it all twelve joints share the servo_kp / servo_kd / servo_inertia / servo_tau_max scalars
+        self._actuator_table = None
+        if getattr(cfg.scene, "robot", None) is not None:
+            if kind != "servo":
+                raise TypeError("cfg.scene.robot needs the closed-loop simulator (SyntheticCfg.kind = 'servo'): the actuators "
+                                "are evaluated inside its launch; the stream simulator has no joints to drive")
+            from cat_envs.tasks.utils.mdp import actuators as UM
+            self._actuator_table = UM.build_table(cfg.scene.robot, SOLO12_JOINTS, syn, cfg.decimation, DEFAULT_JOINT_POS)
         if kind == "stream":
             self.sim = SyntheticSolo12Sim(self.num_envs, self.obs_dim, self.device, seed + int(syn.seed_offset),
                                           int(syn.stream_steps))
@@ -790,7 +873,8 @@ class CaTEnv:
                                       self.reset_buf, env_offset=int(getattr(cfg.scene, "env_offset", 0) or 0),
                                       policy_obs_dim=self.obs_dim if self._obs_table is not None else 0,
                                       events=self._event_block is not None, commands=self._command_block is not None,
-                                      terminations=self._term_table is not None, actions=self._action_table is not None)
+                                      terminations=self._term_table is not None, actions=self._action_table is not None,
+                                      actuators=self._actuator_table is not None)
             self.scene = self.sim.scene
         self.obs_buf = {"policy": self.sim.view(self._obs_field)}
         self._rstep = None
@@ -833,6 +917,10 @@ class CaTEnv:
             print("[INFO] Action Manager: ", self.action_manager)
         else:
             self.action_manager = _ActionManager(self.num_envs, self.act_dim, self.device)
+        if self._actuator_table is not None:                           # behind the action manager: its table comes first
+            from cat_envs.tasks.utils.mdp.actuator_model import ActuatorModel
+            self.actuators = ActuatorModel(self.cfg.scene.robot, self, self._actuator_table)
+            print("[INFO] Actuator Model: ", self.actuators)
         cmd = self.sim.view("command")
         self.command_manager = types.SimpleNamespace(get_command=lambda name: cmd, reset=lambda ids=None: {},
                                                      compute=lambda dt: None)
@@ -947,6 +1035,8 @@ class CaTEnv:
             fp["termination_terms"] = self.termination_manager.fingerprint()
         if getattr(self, "_action_table", None) is not None:           # likewise
             fp["action_terms"] = self.action_manager.fingerprint()
+        if getattr(self, "_actuator_table", None) is not None:         # likewise
+            fp["actuators"] = self.actuators.fingerprint()
         return fp
 
     def state_dict(self) -> dict:
@@ -970,6 +1060,8 @@ class CaTEnv:
             sd["terminations"] = self.termination_manager.state_dict()
         if getattr(self, "_action_table", None) is not None:           # the table's current scales, offsets and clip bounds
             sd["actions"] = self.action_manager.state_dict()
+        if getattr(self, "_actuator_table", None) is not None:         # the history is part of the simulator's ``cur``; the gains are not
+            sd["actuators"] = self.actuators.state_dict()
         return sd
 
     def check_state_dict(self, sd: dict):
@@ -1001,6 +1093,10 @@ class CaTEnv:
             keys.append("actions")
         elif "actions" in sd:
             raise ValueError("run state: it carries actions, this env has no cfg.actions")
+        if getattr(self, "_actuator_table", None) is not None:
+            keys.append("actuators")
+        elif "actuators" in sd:
+            raise ValueError("run state: it carries actuators, this env has no cfg.scene.robot")
         missing = [k for k in keys if k not in sd]
         if missing:
             raise ValueError(f"run state: the env's part lacks {missing}")
@@ -1028,6 +1124,8 @@ class CaTEnv:
             self.termination_manager.check_state_dict(sd["terminations"])
         if getattr(self, "_action_table", None) is not None:
             self.action_manager.check_state_dict(sd["actions"])
+        if getattr(self, "_actuator_table", None) is not None:
+            self.actuators.check_state_dict(sd["actuators"])
 
     def load_state_dict(self, sd: dict):
         """IN PLACE (``copy_`` into the existing tensors, never a rebound attribute): the fused step's argument block, the
@@ -1053,6 +1151,8 @@ class CaTEnv:
             self.termination_manager.load_state_dict(sd["terminations"])
         if getattr(self, "_action_table", None) is not None:
             self.action_manager.load_state_dict(sd["actions"])
+        if getattr(self, "_actuator_table", None) is not None:
+            self.actuators.load_state_dict(sd["actuators"])
         self.curriculum_manager.load_state_dict(sd["curriculum"])      # through set_term_cfg: the next launch carries it
 
     # episode control -------------------------------------------------------------------------

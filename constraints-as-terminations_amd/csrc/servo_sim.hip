@@ -9,7 +9,7 @@
 // for another except through the shuffles.  The next row is assembled in LDS and leaves as coalesced 16-byte stores.
 //   tree16: x += xor-shuffle 8, 4, 2, 1 (width 16)     tree4 (feet): x += xor-shuffle 1, 2
 // The kernel template is servo_sim_kernel.h; this unit holds the entry point and the instances of the packs without an action
-// table, servo_sim_actions.hip those with one.
+// table, servo_sim_actions.hip those with one, servo_sim_actuators.hip those with an actuator table behind it.
 #include "servo_sim_kernel.h"
 
 // the descriptor's size is part of the ABI: cat_envs/native.py (ServoSimRewards) and tests/test_servo_reward_twin.py pin it
@@ -36,6 +36,11 @@ static_assert(offsetof(catppo_servo_sim_actions, term) == 416 && offsetof(catppo
                   sizeof(catppo_servo_action_entry) == 32 && sizeof(catppo_servo_actions) == 16 &&
                   offsetof(catppo_servo_actions, width) == 8 && sizeof(catppo_servo_sim_actions) == 456,
               "catppo_servo_sim_actions: the action descriptor behind the termination descriptor");
+static_assert(offsetof(catppo_servo_sim_actuators, act) == 440 && offsetof(catppo_servo_sim_actuators, actu) == 456 &&
+                  sizeof(catppo_servo_actuator_entry) == 32 && offsetof(catppo_servo_actuator_entry, flags) == 24 &&
+                  sizeof(catppo_servo_actuators) == 16 && offsetof(catppo_servo_actuators, off_act_hist) == 8 &&
+                  sizeof(catppo_servo_sim_actuators) == 472 && CATPPO_SERVO_ACT_HIST_FLOATS == 48,
+              "catppo_servo_sim_actuators: the actuator descriptor behind the action descriptor");
 
 extern "C" int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* desc, void* stream) {
   CATPPO_CHECK_ARG(ctx, ctx != nullptr);
@@ -46,9 +51,12 @@ extern "C" int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* de
   // ... or all three of a catppo_servo_sim_commands (whose event descriptor may be empty, too)
   // ... or all four of a catppo_servo_sim_terminations (whose command descriptor may be empty, too)
   // ... or all five of a catppo_servo_sim_actions (whose termination descriptor may be empty, too)
-  const bool ext_act = d.reserved == CATPPO_SERVO_EXT_ACTIONS;
+  // ... or all six of a catppo_servo_sim_actuators (whose action descriptor is never empty)
+  const bool ext_actu = d.reserved == CATPPO_SERVO_EXT_ACTUATORS;
+  const bool ext_act = d.reserved == CATPPO_SERVO_EXT_ACTIONS || ext_actu;
   const bool ext_term = d.reserved == CATPPO_SERVO_EXT_TERMINATIONS || ext_act;
   const bool ext_cmd = d.reserved == CATPPO_SERVO_EXT_COMMANDS || ext_term;
+  // d.reserved is one of the known values
   CATPPO_CHECK_ARG(ctx, d.reserved == 0 || d.reserved == CATPPO_SERVO_EXT_OBS || d.reserved == CATPPO_SERVO_EXT_EVENTS || ext_cmd);
   const catppo_servo_obs* obs = d.reserved != 0 ? &reinterpret_cast<const catppo_servo_sim_obs*>(desc)->obs : nullptr;
   const catppo_servo_events* ev = d.reserved == CATPPO_SERVO_EXT_EVENTS || ext_cmd
@@ -60,6 +68,7 @@ extern "C" int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* de
   if (tm && cm->block == nullptr && cm->floats == 0) cm = nullptr;
   const catppo_servo_actions* ac = ext_act ? &reinterpret_cast<const catppo_servo_sim_actions*>(desc)->act : nullptr;
   if (ac && tm->table == nullptr && tm->terms == 0) tm = nullptr;
+  const catppo_servo_actuators* au = ext_actu ? &reinterpret_cast<const catppo_servo_sim_actuators*>(desc)->actu : nullptr;
   CATPPO_CHECK_ARG(ctx, d.N >= 1 && d.N < (int64_t(1) << 31) && d.env_offset >= 0 && d.env_offset + d.N < (int64_t(1) << 32));
   CATPPO_CHECK_ARG(ctx, d.state_in && d.state_out && d.episode_length);
   CATPPO_CHECK_ARG(ctx, d.init || (d.action && d.reset && d.state_in != d.state_out));
@@ -179,12 +188,43 @@ extern "C" int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* de
       CATPPO_CHECK_ARG(ctx, tb1 <= rc0 || rc1 <= tb0);
     }
   }
+  if (au) {
+    CATPPO_CHECK_ARG(ctx, au->reserved == 0);
+    // the entries are device memory: their writer checks them (Solo12ServoSim.set_actuator_table); they are values, never
+    // addresses, and the kernel clamps the history slot a lag reaches back to
+    const void* tb = au->table;
+    CATPPO_CHECK_ARG(ctx, tb != nullptr && ((uintptr_t)tb % 16) == 0);
+    const void* others[] = {d.state_in, d.state_out, d.eval, d.trace, d.fixed_command, d.reward_rec, (const void*)d.reward_table,
+                            d.action, obs ? (const void*)obs->table : nullptr, ev ? (const void*)ev->block : nullptr,
+                            cm ? (const void*)cm->block : nullptr, tm ? (const void*)tm->table : nullptr,
+                            tm ? (const void*)tm->rec : nullptr};
+    for (const void* o : others) CATPPO_CHECK_ARG(ctx, tb != o);
+    // the table's 12 entries overlap neither the action table's nor the termination record
+    const uintptr_t tb0 = (uintptr_t)tb, tb1 = tb0 + sizeof(catppo_servo_actuator_entry) * kJoints;
+    const uintptr_t at0 = (uintptr_t)ac->table, at1 = at0 + sizeof(catppo_servo_action_entry) * kJoints;
+    CATPPO_CHECK_ARG(ctx, tb1 <= at0 || at1 <= tb0);
+    if (tm) {
+      const uintptr_t rc0 = (uintptr_t)tm->rec, rc1 = rc0 + (uintptr_t)d.N * CATPPO_SERVO_TERM_FLOATS * sizeof(float);
+      CATPPO_CHECK_ARG(ctx, tb1 <= rc0 || rc1 <= tb0);
+    }
+    // the history field: 48 floats of the row on a 16-byte boundary that no other field the kernel writes touches
+    const int64_t hs = au->off_act_hist, hw = CATPPO_SERVO_ACT_HIST_FLOATS;
+    CATPPO_CHECK_ARG(ctx, hs >= 0 && hs % 4 == 0 && hs + hw <= d.row_floats);
+    for (const auto& fl : fields) CATPPO_CHECK_ARG(ctx, hs + hw <= fl.off || hs >= (int64_t)fl.off + fl.width);
+    if (obs) {
+      const int64_t padded = (obs->width + 3) / 4 * 4;
+      CATPPO_CHECK_ARG(ctx, hs + hw <= obs->off_policy_obs || hs >= obs->off_policy_obs + padded);
+    }
+    if (cm) CATPPO_CHECK_ARG(ctx, hs + hw <= cm->off_cmd_state || hs >= (int64_t)cm->off_cmd_state + 4);
+    if (tm) CATPPO_CHECK_ARG(ctx, hs + hw <= tm->off_term_state || hs >= (int64_t)tm->off_term_state + 4);
+  }
   const unsigned nblk = (unsigned)cdiv64(d.N, kEnvsPerBlock);
   const size_t lds_bytes = (size_t)d.row_floats * kEnvsPerBlock * sizeof(float);
   const int mode = (d.trace || d.fixed_segments > 1) ? kStepResponse : (d.fixed_command || d.eval) ? kEvaluate : kTrain;
   const bool rew = d.reward_terms > 0;
   const hipStream_t st = static_cast<hipStream_t>(stream);
-  if (ac) catppo_internal_servo_sim_launch_actions(mode, rew, nblk, lds_bytes, st, d, obs, ev, cm, tm, *ac);
+  if (au) catppo_internal_servo_sim_launch_actuators(mode, rew, nblk, lds_bytes, st, d, obs, ev, cm, tm, *ac, *au);
+  else if (ac) catppo_internal_servo_sim_launch_actions(mode, rew, nblk, lds_bytes, st, d, obs, ev, cm, tm, *ac);
   else if (tm && cm && obs && ev) launch(mode, rew, nblk, lds_bytes, st, d, *obs, *ev, *cm, *tm);
   else if (tm && cm && ev) launch(mode, rew, nblk, lds_bytes, st, d, *ev, *cm, *tm);
   else if (tm && cm && obs) launch(mode, rew, nblk, lds_bytes, st, d, *obs, *cm, *tm);

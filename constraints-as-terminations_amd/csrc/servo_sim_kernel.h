@@ -1,6 +1,6 @@
 // The servo simulator's kernel template, its helpers and launch(): included by servo_sim.hip (the packs without an action
-// table, and the entry point) and by servo_sim_actions.hip (the packs with one), so that the two sets of instances
-// compile side by side.  Everything here has internal linkage.
+// table, and the entry point), by servo_sim_actions.hip (the packs with one) and by servo_sim_actuators.hip (the packs with
+// an actuator table behind it), so that the three sets of instances compile side by side.  Everything here has internal linkage.
 #pragma once
 #include <type_traits>
 
@@ -17,6 +17,7 @@ constexpr int kRawObs = 45;                                              // the 
 constexpr uint32_t kTagPush = 0x50555348u, kTagJvel = 0x4A56454Cu, kTagRoot = 0x524F4F54u, kTagFric = 0x46524943u;
 // "CMDD", "CMDT": command draws and resampling times of the configured command process ("Commands")
 constexpr uint32_t kTagCmdDraw = 0x434D4444u, kTagCmdTime = 0x434D4454u;
+constexpr uint32_t kTagActDelay = 0x41444C59u;                           // "ADLY": the actuator lag ("Actuators")
 
 // G[k][lane]: the fixed 5 x 12 matrix of the base model (rows vx, vy, wz, roll, pitch)
 __device__ __forceinline__ float gain(int k, int lane) {
@@ -251,6 +252,18 @@ struct ActRegs<true> {
   int A = kJoints;
 };
 
+// what lane j < 12 keeps of entry j of the actuator table, the env's lag and the three history slots of the input row;
+// empty without the table
+template <bool kOn>
+struct ActuRegs {};
+template <>
+struct ActuRegs<true> {
+  catppo_servo_actuator_entry entry = {0.f, 0.f, 1.f, 0.f, 0.f, 1.f, 0u, 0u};
+  float h0 = 0.f, h1 = 0.f, h2 = 0.f;                      // slot k - 1: the processed action k control steps ago
+  int L = 0;                                               // the lag of the joint's group, in physics steps
+  float vl = 1.f;                                          // the velocity limit of a DC motor, 1.f for every other joint
+};
+
 // the servo torque of one substep before its clamp: the PD law on the target q_des, or the action term's (kind, processed
 // action p) of the joint's table entry.  Selects, no branches: the kinds differ between the lanes of a wave
 template <bool kOn>
@@ -265,6 +278,43 @@ __device__ __forceinline__ float servo_tau(const catppo_servo_sim& d, const ActR
   } else {
     return d.kp * (q_des - q) - d.kd * qd;
   }
+}
+
+// the joint's inertia: the descriptor's scalar, or lane j's entry of the actuator table
+template <bool kOn>
+__device__ __forceinline__ float inertia_of(const catppo_servo_sim& d, const ActuRegs<kOn>& ur) {
+  if constexpr (kOn) return ur.entry.inertia;
+  else return d.inertia;
+}
+
+// ... with the gains of the joint's actuator entry in the place of d.kp and d.kd
+__device__ __forceinline__ float servo_tau(const ActRegs<true>& ar, const ActuRegs<true>& ur, float p, float def, float q,
+                                           float qd) {
+  const int kind = (int)(ar.entry.flags & CATPPO_SERVO_ACTION_KIND_MASK);
+  const float tgt = kind == 1 ? p : kind == 2 ? p + q : def;
+  const float pd = ur.entry.kp * (tgt - q) - ur.entry.kd * qd;
+  const float vel = ur.entry.kd * (p - qd);
+  return kind == 3 ? vel : kind == 4 ? p : pd;
+}
+
+// the processed action substep s acts on: this step's, or the history slot the lag reaches back to (at most the third)
+__device__ __forceinline__ float delayed_p(const ActuRegs<true>& ur, int s, int decimation, float p) {
+  int k = s >= ur.L ? 0 : (ur.L - s + decimation - 1) / decimation;
+  k = k < 3 ? k : 3;
+  return k == 0 ? p : k == 1 ? ur.h0 : k == 2 ? ur.h1 : ur.h2;
+}
+
+// the clamp of one substep's torque: +- effort_limit, or the DC motor's torque-speed bounds at the substep's qd
+__device__ __forceinline__ float actuator_clamp(const ActuRegs<true>& ur, float tau, float qd) {
+  const float eff = ur.entry.effort_limit, sat = ur.entry.saturation_effort;
+  const float ideal = fminf(fmaxf(tau, -eff), eff);
+  const float r = qd / ur.vl;
+  float hi = sat * (1.f - r);
+  hi = fminf(fmaxf(hi, 0.f), eff);
+  float lo = sat * (-1.f - r);
+  lo = fminf(fmaxf(lo, -eff), 0.f);
+  const float dc = fminf(fmaxf(tau, lo), hi);
+  return (ur.entry.flags & CATPPO_SERVO_ACTUATOR_DC_MOTOR) ? dc : ideal;
 }
 
 // kMode = kTrain is the launch with all three evaluation pointers NULL: everything they add is compiled out of it, so
@@ -294,6 +344,10 @@ __device__ __forceinline__ float servo_tau(const catppo_servo_sim& d, const ActR
 // column drives joint j, through which scale, offset and clip, and as what kind of target; the raw action by column stands
 // where `a` stood.  Orthogonal to the rest, compiled out without it: 64 more instances (16 packs, evaluation folded as
 // above), compiled in servo_sim_actions.hip.
+// catppo_servo_actuators, last in the pack and only behind catppo_servo_actions ("Actuators"): lane j's entry
+// of the actuator table stands where d.kp, d.kd, d.inertia and d.tau_max stand, a DC motor's clamp follows the substep's qd,
+// and the processed action may act late by the env's lag, out of three history slots of the row.  Orthogonal to the rest,
+// compiled out without it: 64 more instances (16 packs, evaluation folded as above), compiled in servo_sim_actuators.hip.
 template <int kMode, bool kRew, typename... Ext>
 __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeof...(Ext) == 0) ? 8 : 1) void servo_sim_kernel(
     const catppo_servo_sim d, const Ext... ext) {
@@ -302,7 +356,10 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
   constexpr bool kCmd = (std::is_same_v<Ext, catppo_servo_commands> || ...);
   constexpr bool kTerm = (std::is_same_v<Ext, catppo_servo_terminations> || ...);
   constexpr bool kAct = (std::is_same_v<Ext, catppo_servo_actions> || ...);
+  constexpr bool kActu = (std::is_same_v<Ext, catppo_servo_actuators> || ...);
+  static_assert(kAct || !kActu, "the actuator descriptor comes only behind the action descriptor");
   constexpr bool kEval = kMode != kTrain;
+  ActuRegs<kActu> UR;                    // declared first: further down it reorders two register initialisations of older instances
   extern __shared__ float4 lds4[];
   float* lds = reinterpret_cast<float*>(lds4);
   const int tid = threadIdx.x, lane = tid & 15, grp = tid >> 4;
@@ -420,6 +477,9 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
     if (!init && lane < TR.terms) TR.entry = tm.table[lane];
     if (e0 + grp < d.N && !init) TR.rec0 = tm.rec[e * CATPPO_SERVO_TERM_FLOATS + lane];
   }
+  // lane j < 12 loads entry j of the actuator table (two 16-byte loads), long before the substep loop reads it
+  if constexpr (kActu)
+    if (lane < kJoints && d.init == 0) UR.entry = ext_of<catppo_servo_actuators>(ext...).table[lane];
 
   if (init) {
     // the first state of episode 0: default pose + noise, at rest, four feet on the ground
@@ -494,13 +554,35 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
         act_p = act_p > AR.entry.clip_hi ? AR.entry.clip_hi : act_p;
       }
     }
+    // actuators: the three history slots of the input row (three loads up front, chosen by selects in the loop; after a
+    // reset, or behind an init launch, all three count as this step's p) and the lag of the joint's group
+    if constexpr (kActu) {
+      const float* hin = in + ext_of<catppo_servo_actuators>(ext...).off_act_hist;
+      const float s0 = hin[lane], s1 = hin[16 + lane], s2 = hin[32 + lane];
+      const bool fresh = rst || hin[12] == 0.f;
+      UR.h0 = fresh ? act_p : s0, UR.h1 = fresh ? act_p : s1, UR.h2 = fresh ? act_p : s2;
+      const int mn = (int)(UR.entry.delay & 0xFFu), mx = (int)((UR.entry.delay >> 8) & 0xFFu);
+      UR.L = mn;
+      if (mx > mn) {
+        const float u = rng::uniform_open(ev_block(d, gid, ep, (UR.entry.delay >> 16) & 0xFFu, kTagActDelay).x);
+        const int l = mn + (int)(u * (float)(mx - mn + 1));
+        UR.L = l < mx ? l : mx;
+      }
+      if (UR.entry.flags & CATPPO_SERVO_ACTUATOR_DC_MOTOR) UR.vl = UR.entry.velocity_limit;
+    }
     // ---- joints: `decimation` substeps of the clamped PD servo, semi-implicit Euler; the substep of largest |tau| is reported
     const float q_des = def + d.action_scale * a;
     float tau_w = 0.f;
     for (int s = 0; s < d.decimation; ++s) {
-      float tau = servo_tau(d, AR, q_des, act_p, def, q, qd);
-      tau = fminf(fmaxf(tau, -d.tau_max), d.tau_max);
-      const float qdd = tau / d.inertia;
+      float tau, qdd;
+      if constexpr (kActu) {
+        tau = actuator_clamp(UR, servo_tau(AR, UR, delayed_p(UR, s, d.decimation, act_p), def, q, qd), qd);
+        qdd = tau / UR.entry.inertia;
+      } else {
+        tau = servo_tau(d, AR, q_des, act_p, def, q, qd);
+        tau = fminf(fmaxf(tau, -d.tau_max), d.tau_max);
+        qdd = tau / d.inertia;
+      }
       qd = qd + qdd * d.dt;
       q = q + qd * d.dt;
       if (fabsf(tau) > fabsf(tau_w)) tau_w = tau;
@@ -631,7 +713,7 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
     // ---- reward terms: value_k = (raw_k * weight_k) * step_dt in table order, summed from 0.f; lane k keeps value_k
     float rsum = 0.f, mine = 0.f;
     if constexpr (kRew) {
-      const float acc = tau_w / d.inertia, da = a - a_prev;
+      const float acc = tau_w / inertia_of(d, UR), da = a - a_prev;
       const float moving = sqrtf(cmd[0] * cmd[0] + cmd[1] * cmd[1]) > 0.1f ? 1.f : 0.f;
       for (int k = 0; k < d.reward_terms; ++k) {
         // lanes 0 .. 15 of the wave are its first lane group: lane k of the wave holds entry k
@@ -717,7 +799,7 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
     if (isj) {
       row[d.off_joint_pos + lane] = q;
       row[d.off_joint_vel + lane] = qd;
-      row[d.off_joint_acc + lane] = tau_w / d.inertia;
+      row[d.off_joint_acc + lane] = tau_w / inertia_of(d, UR);
       row[d.off_applied_torque + lane] = tau_w;
       float o_q = dq, o_v = qd, o_a = a;
       if constexpr (kEv) {
@@ -758,6 +840,13 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
       if (lane == 12) row[tm.off_term_state] = (float)TR.fired;
       if (e0 + grp < d.N && ends)
         tm.rec[e * CATPPO_SERVO_TERM_FLOATS + lane] = TR.rec0 + (lane == 15 || ((TR.fired >> lane) & 1u) ? 1.f : 0.f);
+    }
+    // the history moves one slot back: p | old slot 0 | old slot 1; float 12 of slot 0 says that a step wrote the row
+    if constexpr (kActu) {
+      float* hout = row + ext_of<catppo_servo_actuators>(ext...).off_act_hist;
+      hout[lane] = isj ? act_p : lane == 12 ? 1.f : 0.f;
+      hout[16 + lane] = isj ? UR.h0 : 0.f;
+      hout[32 + lane] = isj ? UR.h1 : 0.f;
     }
     if (lane == 14) {
       for (int k = 0; k < 3; ++k) row[d.off_servo + k] = v[k];
@@ -869,7 +958,8 @@ void launch(int mode, bool rew, unsigned nblk, size_t lds_bytes, hipStream_t str
   // packs with terminations fold the evaluation instances into the step-response ones (which take a NULL trace and a plain
   // command table through two wave-uniform branches and compute the same bits): a third fewer instances to compile
   // (packs with an action table likewise)
-  constexpr int kEvalAs = ((std::is_same_v<Ext, catppo_servo_terminations> || std::is_same_v<Ext, catppo_servo_actions>) || ...)
+  constexpr int kEvalAs = ((std::is_same_v<Ext, catppo_servo_terminations> || std::is_same_v<Ext, catppo_servo_actions> ||
+                            std::is_same_v<Ext, catppo_servo_actuators>) || ...)
                               ? kStepResponse : kEvaluate;
   const Kernel table[3][2] = {{servo_sim_kernel<kTrain, false, Ext...>, servo_sim_kernel<kTrain, true, Ext...>},
                               {servo_sim_kernel<kEvalAs, false, Ext...>, servo_sim_kernel<kEvalAs, true, Ext...>},
@@ -885,3 +975,10 @@ void catppo_internal_servo_sim_launch_actions(int mode, bool rew, unsigned nblk,
                                               const catppo_servo_sim& d, const catppo_servo_obs* obs,
                                               const catppo_servo_events* ev, const catppo_servo_commands* cm,
                                               const catppo_servo_terminations* tm, const catppo_servo_actions& act);
+
+// servo_sim_actuators.hip: the launch of a pack that ends with the action and the actuator descriptors
+void catppo_internal_servo_sim_launch_actuators(int mode, bool rew, unsigned nblk, size_t lds_bytes, hipStream_t stream,
+                                                const catppo_servo_sim& d, const catppo_servo_obs* obs,
+                                                const catppo_servo_events* ev, const catppo_servo_commands* cm,
+                                                const catppo_servo_terminations* tm, const catppo_servo_actions& act,
+                                                const catppo_servo_actuators& actu);

@@ -729,7 +729,7 @@ typedef struct catppo_servo_sim {
   const uint8_t* reset;                  /* [N] */
   const int64_t* episode_length;         /* [N], before this step's increment */
   int64_t max_episode_length;
-  int32_t decimation, resample_steps, init, reserved;   /* reserved: 0 or one of CATPPO_SERVO_EXT_OBS / _EVENTS / _COMMANDS / _TERMINATIONS / _ACTIONS (see below) */
+  int32_t decimation, resample_steps, init, reserved;   /* reserved: 0 or one of CATPPO_SERVO_EXT_OBS / _EVENTS / _COMMANDS / _TERMINATIONS / _ACTIONS / _ACTUATORS (see below) */
   uint64_t seed;
   float default_joint_pos[12];
   float dt, kp, kd, inertia, tau_max, action_scale, vel_alpha, tilt_beta, tilt_max, reward_scale, foot_clearance,
@@ -988,6 +988,66 @@ typedef struct catppo_servo_sim_actions {
   catppo_servo_terminations term;         /* table NULL and terms 0: no terminations */
   catppo_servo_actions act;
 } catppo_servo_sim_actions;
+
+/* Actuators ("Actuators").  desc->reserved == CATPPO_SERVO_EXT_ACTUATORS: `desc` is the head of a
+ * catppo_servo_sim_actuators, i.e. the catppo_servo_sim_actions above with an actuator descriptor behind it.  The five
+ * descriptors before it are checked and used exactly as under CATPPO_SERVO_EXT_ACTIONS, except that act.table must not be
+ * NULL: a launch without an ActionsCfg passes the identity action table (col j, kind 1, action_scale, default pose, no
+ * clip), which computes the bits of the launch without one.  Every older value of `reserved` keeps its meaning.
+ * actu.table is a DEVICE array of 12 entries of 32 bytes, one per simulator joint j (lane j), 16-byte aligned, read by every
+ * launch that is no init launch (values the host rewrites in stream order are in the next launch, under graph replay too).
+ * Entry j stands where sim.kp, sim.kd, sim.inertia and sim.tau_max stand for joint j - in the servo torque of every action
+ * kind, the clamp, qdd, the row's joint_acc and reward kind 8 (tau_w / inertia) - which are unused under this value.
+ * fp32, unfused, per substep s = 0 .. decimation - 1, with qd of that substep before its integration:
+ *   tau as under "Actions", with kp_j, kd_j and the delayed processed action (below) in the place of p
+ *   flags & CATPPO_SERVO_ACTUATOR_DC_MOTOR clear (ideal PD, delayed PD, implicit):
+ *     tau = fminf(fmaxf(tau, -effort_limit), effort_limit)
+ *   set (DC motor; IsaacLab's DCMotor._clip_effort):
+ *     r  = qd / velocity_limit
+ *     hi = saturation_effort * (1.f - r)         hi = fminf(fmaxf(hi, 0.f), effort_limit)
+ *     lo = saturation_effort * (-1.f - r)        lo = fminf(fmaxf(lo, -effort_limit), 0.f)
+ *     tau = fminf(fmaxf(tau, lo), hi)
+ *   qdd = tau / inertia_j      (the integration and the choice of the reported substep stay as they are)
+ * velocity_limit of a joint that is no DC motor is not read: the surrogate has no joint velocity clamp.
+ * Delay.  delay = min | max << 8 | group << 16 (8 bits each).  The lag L of (env, episode, group), in physics steps:
+ *   min == max: L = min; otherwise u = uniform_open(word 0 of Philox{gid, episode, group, "ADLY"}),
+ *   L = min + (int)(u * (float)(max - min + 1)), at most max
+ * (one draw per group: the joints of a group share it; re-derived in every step).  The row's field at off_act_hist, three
+ * slots of 16 floats, holds in float j of slot k - 1 the processed action p of joint j of the control step k steps ago;
+ * float 12 of slot 0 is 1.f in every row a step wrote and 0.f in the row of an init launch, floats 13 .. 15 of slot 0 and
+ * 12 .. 15 of slots 1 and 2 are zero.  In a step that follows a reset or whose input row has float 12 of slot 0 equal to
+ * 0.f all three slots count as holding this step's p.  In substep s
+ *   k = s >= L ? 0 : (L - s + decimation - 1) / decimation, at most 3
+ * and the target is this step's p for k == 0, else slot k - 1.  The output row's slots are p, slot 0, slot 1 (as counted).
+ * obs[33 + k], the trace's action floats and reward kinds 11 / 12 keep reading the raw, undelayed columns.
+ * With kp = sim.kp, kd = sim.kd, inertia = sim.inertia, effort_limit = sim.tau_max, flags 0 and delay 0 in every entry the
+ * launch computes the bits of the launch without the descriptor, the field at off_act_hist excepted.
+ * off_act_hist: 48 floats of the row on a 16-byte boundary that no other field the kernel writes touches.  The table's
+ * writer checks its entries (Solo12ServoSim.set_actuator_table); whatever it holds the launch stays inside its rows: the
+ * entries are values, never addresses, and k is clamped. */
+#define CATPPO_SERVO_EXT_ACTUATORS 0x41435531      /* "ACU1": value of catppo_servo_sim.reserved that announces catppo_servo_sim_actuators */
+#define CATPPO_SERVO_ACTUATOR_DC_MOTOR 0x1u
+#define CATPPO_SERVO_ACT_HIST_FLOATS 48            /* 3 slots of 16 floats */
+typedef struct catppo_servo_actuator_entry {
+  float kp, kd, inertia, effort_limit;    /* stiffness, damping, sim.inertia + armature, effort limit of joint j */
+  float saturation_effort, velocity_limit; /* read for a DC motor only */
+  uint32_t flags;                         /* CATPPO_SERVO_ACTUATOR_DC_MOTOR */
+  uint32_t delay;                         /* min | max << 8 | group << 16 */
+} catppo_servo_actuator_entry;
+typedef struct catppo_servo_actuators {
+  const catppo_servo_actuator_entry* table; /* DEVICE array [12], 16-byte aligned */
+  int32_t off_act_hist;                   /* float offset of the row's 48-float history field, a multiple of 4 */
+  int32_t reserved;                       /* 0 */
+} catppo_servo_actuators;
+typedef struct catppo_servo_sim_actuators {
+  catppo_servo_sim sim;                   /* sim.reserved = CATPPO_SERVO_EXT_ACTUATORS */
+  catppo_servo_obs obs;                   /* width 0 and table NULL: no observation table */
+  catppo_servo_events ev;                 /* block NULL and floats 0: no events */
+  catppo_servo_commands cmd;              /* block NULL and floats 0: no commands */
+  catppo_servo_terminations term;         /* table NULL and terms 0: no terminations */
+  catppo_servo_actions act;               /* table never NULL */
+  catppo_servo_actuators actu;
+} catppo_servo_sim_actuators;
 
 /* ---- test hook (ABI 0.6) ------------------------------------------------------------------------------------------
  * buf != NULL ([2][M] int32, device): the head / loss kernel of every following catppo_ppo_minibatch_* call writes the clip

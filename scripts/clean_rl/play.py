@@ -114,9 +114,11 @@ def main(argv=None):
     from cat_envs.tasks.utils.cleanrl.export import export_policy
     om = getattr(env.unwrapped, "observation_manager", None)
     am = env.unwrapped.action_manager                   # envs with cfg.actions: the manager that knows the output contract
+    um = getattr(env.unwrapped, "actuators", None)      # envs with cfg.scene.robot: gains and delay range join actions.json
     exported = export_policy(actor.state_dict(), os.path.join(os.path.dirname(resume_path), "exported"),
                              observation_spec=None if om is None else om.spec(),
-                             action_spec=am.spec() if hasattr(am, "spec") else None)
+                             action_spec=am.spec() if hasattr(am, "spec") else None,
+                             actuator_spec=um.spec() if um is not None else None)
     print(f"[INFO] Exported ONNX model to {exported['onnx']}")
     print(f"[INFO] Exported .pt model to {exported['jit']}")
     if om is not None:

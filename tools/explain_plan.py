@@ -11,9 +11,10 @@ BASELINE shapes (profiles/r5_explain_plan.txt is this output).
     python tools/explain_plan.py --task Isaac-Velocity-CaT-Flat-Solo12-Servo-Reference-v0        (needs no device)
 
 names the instance of the servo simulator's kernel a task's training step launches: which of ``cfg.rewards``,
-``cfg.observations``, ``cfg.events``, ``cfg.commands``, ``cfg.terminations`` and ``cfg.actions`` (``RewardsCfg``, ``ObservationsCfg``,
+``cfg.observations``, ``cfg.events``, ``cfg.commands``, ``cfg.terminations``, ``cfg.actions`` and ``cfg.scene.robot`` (``RewardsCfg``, ``ObservationsCfg``,
 ``EventCfg``, ``CommandsCfg``, ``TerminationsCfg``, ``ActionsCfg``) the cfg carries decides the kernel's template pack
-(csrc/servo_sim_kernel.h, instantiated in servo_sim.hip and, with actions, servo_sim_actions.hip).
+(csrc/servo_sim_kernel.h, instantiated in servo_sim.hip, with actions in servo_sim_actions.hip and with a robot in
+servo_sim_actuators.hip).
 The servo tasks are ``...-Solo12-Servo-v0`` and its ``-Rewards``, ``-Obs``, ``-Events``, ``-Full``, ``-Commands``, ``-Reference``,
 ``-Terminations``, ``-Reference-Terminations``, ``-Actions`` and ``-Reference-Actions`` variants."""
 import argparse
@@ -74,7 +75,12 @@ def explain_task(task):
     pack = [name for key, name in (("observations", "catppo_servo_obs"), ("events", "catppo_servo_events"),
                                    ("commands", "catppo_servo_commands"), ("terminations", "catppo_servo_terminations"),
                                    ("actions", "catppo_servo_actions")) if has[key]]
+    robot = getattr(cfg.scene, "robot", None)
+    if robot is not None:                        # the actuator descriptor comes behind an action descriptor, the identity one if need be
+        pack += ([] if has["actions"] else ["catppo_servo_actions"]) + ["catppo_servo_actuators"]
     row = 308 + (48 if has["observations"] else 0) + (4 if has["commands"] else 0) + (4 if has["terminations"] else 0)
+    row += 48 if robot is not None else 0
+    has["scene.robot"] = robot is not None
     out = [f"== {task}: " + ", ".join(f"cfg.{k} {'set' if v else 'unset'}" for k, v in has.items()),
            f"servo_sim_kernel<kTrain, {'true' if has['rewards'] else 'false'}{''.join(', ' + n for n in pack)}>: row of {row} floats "
            f"(with the reference's 45-float policy observation), {row * 64} bytes of LDS per workgroup"]
@@ -97,6 +103,16 @@ def explain_task(task):
                    + ", ".join(f"'{n}' ({t['kind']}, columns {t['slice'][0]}..{t['slice'][1] - 1})" for n, t in terms.items()))
         for c in AM.action_spec(entries, terms, E.SOLO12_JOINTS)["columns"]:
             out.append(f"  column {c['column']:2d} -> {c['joint']:<7s} {c['kind']}: scale {c['scale']:g}, offset {c['offset']:g}, clip {c['clip']}")
+    if robot is not None:
+        import cat_envs.tasks.utils.cat.cat_env as E
+        from cat_envs.tasks.utils.mdp import actuators as UM
+        entries, spec = UM.build_table(robot, E.SOLO12_JOINTS, cfg.synthetic, cfg.decimation, E.DEFAULT_JOINT_POS)
+        out.append("actuators (servo_sim_actuators.hip): groups " + ", ".join(
+            f"'{n}' ({g['kind']}, {len(g['joints'])} joints, delay {g['min_delay']}..{g['max_delay']} physics steps)"
+            for n, g in spec["groups"].items()) + f"; inert: {', '.join(spec['inert']) or 'none'}")
+        for j in spec["joints"]:
+            out.append(f"  joint {j['joint_id']:2d} {j['joint']:<7s} group '{j['group']}': stiffness {j['stiffness']:g}, damping "
+                       f"{j['damping']:g}, inertia {j['inertia']:g}, effort limit {j['effort_limit']:g}")
     return "\n".join(out)
 
 

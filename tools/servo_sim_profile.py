@@ -34,6 +34,14 @@ parent's library, this library without the flag and this library with --terminat
 term over the twelve joints in the order FL FR HR HL, scale 0.5, default offsets), so that the simulator's launch is the
 actions-on training instance; the values are the reference's own.  profiles/servo_actions_kernel_stats.csv: the parent's
 library, this library without the flag and this library with --actions, alternating in one session, every run listed.
+--reference-actions runs the task with all six MDP blocks of the reference (Isaac-Velocity-CaT-Flat-Solo12-Servo-Reference-Actions-v0;
+its values untouched), the row the actuator arms are measured against: it runs with the parent's library, too.
+--actuators reference | delayed runs that row with the reference's robot (Isaac-Velocity-CaT-Flat-Solo12-Servo-Reference-Actuators-v0:
+one ideal PD group, stiffness 4, damping 0.2, armature 0.00036207, effort limit 10), or with the same gains as a
+``DelayedPDActuatorCfg(min_delay=0, max_delay=4)``, so that the simulator's launch is the actuators-on training instance of the
+full pack.  profiles/servo_actuators_kernel_stats.csv: the parent's library and this library without a flag, both with
+--reference-actions, and this library with --actuators reference and --actuators delayed, alternating in one session, every
+run listed.
 
 Per env step the trace shows servo_sim_kernel (the simulator), the two launches of catppo_rollout_pre, the one of
 catppo_rollout_post and the policy forward."""
@@ -60,9 +68,13 @@ def main():
     ap.add_argument("--commands", action="store_true", help="the task with CommandsCfg (p_move 0.01): the command term inside the simulator launch")
     ap.add_argument("--terminations", action="store_true", help="the task with TerminationsCfg: termination terms inside the simulator launch")
     ap.add_argument("--actions", action="store_true", help="the task with ActionsCfg: joint action terms inside the simulator launch")
+    ap.add_argument("--reference-actions", action="store_true", help="the task with all six MDP blocks of the reference")
+    ap.add_argument("--actuators", choices=("reference", "delayed"), default=None,
+                    help="... and the reference's robot, or its gains behind an actuator delay of 0 .. 4 physics steps")
     a = ap.parse_args()
-    if a.obs + a.rewards + a.events + a.commands + a.terminations + a.actions > 1:
-        ap.error("--obs, --rewards, --events, --commands, --terminations and --actions are separate arms")
+    if a.obs + a.rewards + a.events + a.commands + a.terminations + a.actions + a.reference_actions + (a.actuators is not None) > 1:
+        ap.error("--obs, --rewards, --events, --commands, --terminations, --actions, --reference-actions and --actuators are "
+                 "separate arms")
     import cat_envs.tasks  # noqa: F401
     from cat_envs.shim import load_cfg_from_registry, make
     from cat_envs.tasks.utils.cleanrl.ppo import PPOTrainer
@@ -71,7 +83,10 @@ def main():
             "Isaac-Velocity-CaT-Flat-Solo12-Servo-Events-v0" if a.events else
             "Isaac-Velocity-CaT-Flat-Solo12-Servo-Commands-v0" if a.commands else
             "Isaac-Velocity-CaT-Flat-Solo12-Servo-Terminations-v0" if a.terminations else
-            "Isaac-Velocity-CaT-Flat-Solo12-Servo-Actions-v0" if a.actions else "Isaac-Velocity-CaT-Flat-Solo12-Servo-v0")
+            "Isaac-Velocity-CaT-Flat-Solo12-Servo-Actions-v0" if a.actions else
+            "Isaac-Velocity-CaT-Flat-Solo12-Servo-Reference-Actions-v0" if a.reference_actions else
+            "Isaac-Velocity-CaT-Flat-Solo12-Servo-Reference-Actuators-v0" if a.actuators else
+            "Isaac-Velocity-CaT-Flat-Solo12-Servo-v0")
     env_cfg = load_cfg_from_registry(task, "env_cfg_entry_point")
     if a.rewards:
         from cat_envs.tasks.locomotion.velocity.config.solo12.cat_flat_env_cfg import ShapedRewardsCfg
@@ -81,6 +96,9 @@ def main():
         push.params = {**push.params, "probability": 0.01}
     if a.commands:
         env_cfg.commands.base_velocity.p_move = 0.01
+    if a.actuators == "delayed":
+        from cat_envs.tasks.locomotion.velocity.config.solo12.cat_flat_env_cfg import _delayed
+        env_cfg.scene.robot = _delayed(env_cfg.scene.robot, 0, 4)
     agent_cfg = load_cfg_from_registry(task, "clean_rl_cfg_entry_point")
     env_cfg.scene.num_envs = a.num_envs
     agent_cfg.minibatch_size = min(agent_cfg.minibatch_size, a.num_envs * agent_cfg.num_steps)
@@ -130,6 +148,11 @@ def main():
         am = env_u.action_manager
         print(f"actions: {am.active_terms}, {am.total_action_dim} columns, row of {env_u.sim.F} floats, columns -> joints "
               f"{[c['joint'] for c in am.spec()['columns']]}")
+    if a.actuators:
+        um, sim = env_u.actuators, env_u.sim
+        g = um.get_group("legs")
+        print(f"actuators: {um.active_groups} ({g['kind']}, delay {g['min_delay']} .. {g['max_delay']} physics steps), row of "
+              f"{sim.F} floats, stiffness {g['stiffness'][0]:g}, |history| mean {float(sim.view('act_hist')[:, :12].abs().mean()):.4f}")
     if a.eval or a.trace:
         steps = record[:, 0].cpu()
         assert float(steps.min()) == float(steps.max()) == a.rollouts * trainer.T, (float(steps.min()), float(steps.max()))
