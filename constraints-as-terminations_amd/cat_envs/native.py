@@ -293,6 +293,28 @@ class ServoSimActuators(ServoSimActions):
     _fields_ = [("actu", ServoActuators)]
 
 
+SERVO_EXT_RANDOMIZE = 0x524E4431        # CATPPO_SERVO_EXT_RANDOMIZE: ``reserved`` of a descriptor followed by all six and the randomisation
+SERVO_RANDOMIZE_FLOATS = 32             # CATPPO_SERVO_RANDOMIZE_FLOATS: words of the device-resident randomisation block
+#: bits of the block's flag word: the switch, one bit per quantity, one reset-mode bit per term
+SERVO_RANDOMIZE_FLAGS = {"enable": 0x1, "stiffness": 0x2, "damping": 0x4, "friction": 0x8, "armature": 0x10, "mass": 0x20,
+                         "gains_reset": 0x100, "joint_reset": 0x200, "mass_reset": 0x400}
+SERVO_RANDOMIZE_OPS = {"scale": 0, "add": 1, "abs": 2}      # word 1: gains | joint parameters << 8 | mass << 16
+#: word offsets of the randomisation block (include/catppo.h, "Randomisation"); every range is a (lo, width) pair
+SERVO_RANDOMIZE_WORDS = {"flags": 0, "ops": 1, "gains_mask": 2, "joint_mask": 3, "body_mask": 4, "stiffness": 6, "damping": 8,
+                         "friction": 10, "armature": 12, "mass": 14, "m0": 16, "g": 17, "servo_inertia": 18, "armatures": 20}
+
+
+class ServoRandomize(C.Structure):
+    """catppo_servo_randomize: the randomisation descriptor; ``block`` is a device array of ``SERVO_RANDOMIZE_FLOATS`` words"""
+    _fields_ = [("block", C.c_void_p), ("reserved", C.c_int32 * 2)]
+
+
+class ServoSimRandomize(ServoSimActuators):
+    """catppo_servo_sim_randomize: a ``ServoSimActuators`` (whose actuator table is never NULL here) and a ``ServoRandomize``
+    behind it; the library reads all seven while ``reserved`` is ``SERVO_EXT_RANDOMIZE``"""
+    _fields_ = [("rnd", ServoRandomize)]
+
+
 F32, F16, F64 = 0, 1, 2                 # CATPPO_F32 / _F16 / _F64
 SUM, MAX = 0, 1                         # CATPPO_SUM / _MAX
 LR_FIXED, LR_LINEAR, LR_KEEP = 0, 1, 2
@@ -907,6 +929,8 @@ class Native:
             raise TypeError("servo_sim_step: a descriptor whose 'reserved' announces actions must be a native.ServoSimActions")
         if desc.reserved == SERVO_EXT_ACTUATORS and not isinstance(desc, ServoSimActuators):   # ... and a catppo_servo_actuators
             raise TypeError("servo_sim_step: a descriptor whose 'reserved' announces actuators must be a native.ServoSimActuators")
+        if desc.reserved == SERVO_EXT_RANDOMIZE and not isinstance(desc, ServoSimRandomize):   # ... and a catppo_servo_randomize
+            raise TypeError("servo_sim_step: a descriptor whose 'reserved' announces randomisation must be a native.ServoSimRandomize")
         rc = self.lib.catppo_servo_sim_step(self.h, C.byref(desc), self._stream())
         if rc:
             self._ok(rc)

@@ -151,3 +151,19 @@ for _name, _cfg in (("Actuators", "Solo12ServoActuatorsFlatEnvCfg"), ("Reference
         disable_env_checker=True,
         kwargs={"env_cfg_entry_point": f"{__name__}.cat_flat_env_cfg:{_cfg}_PLAY", **_KW},
     )
+
+# the servo task with a robot of its own per env: gains, joint friction and base mass drawn inside the simulator's launch
+# ("Randomisation"); "Reference-Randomized" is all six MDP blocks, the robot and the three terms
+for _name, _cfg in (("Randomized", "Solo12ServoRandomizedFlatEnvCfg"), ("Reference-Randomized", "Solo12ServoReferenceRandomizedFlatEnvCfg")):
+    register(
+        id=f"Isaac-Velocity-CaT-Flat-Solo12-Servo-{_name}-v0",
+        entry_point=CaTEnv,
+        disable_env_checker=True,
+        kwargs={"env_cfg_entry_point": f"{__name__}.cat_flat_env_cfg:{_cfg}", **_KW},
+    )
+    register(
+        id=f"Isaac-Velocity-CaT-Flat-Solo12-Servo-{_name}-Play-v0",
+        entry_point=CaTEnv,
+        disable_env_checker=True,
+        kwargs={"env_cfg_entry_point": f"{__name__}.cat_flat_env_cfg:{_cfg}_PLAY", **_KW},
+    )

@@ -20,6 +20,9 @@ DESIGN section 9 "Actions"); ``Solo12ServoReferenceActionsFlatEnvCfg`` is all si
 Actuators: ``scene.robot`` (the reference's ``SOLO12_MINIMAL_CFG``: one ideal PD group, its gains, armature and limits)
 likewise (``Solo12ServoActuatorsFlatEnvCfg``, DESIGN section 9 "Actuators"); ``Solo12ServoReferenceActuatorsFlatEnvCfg`` is
 all six blocks and the robot, ``Solo12ServoDelayedActuatorsFlatEnvCfg`` the same gains behind an actuator delay.
+Randomisation: ``RandomizationEventCfg`` (per-env gains, joint friction and base mass; this project's ranges) likewise
+(``Solo12ServoRandomizedFlatEnvCfg``, DESIGN section 9 "Randomisation"); ``Solo12ServoReferenceRandomizedFlatEnvCfg`` adds
+the three terms to the reference's ``EventCfg`` on all six blocks and the robot.
 """
 import math
 
@@ -505,6 +508,65 @@ class Solo12ServoDelayedActuatorsFlatEnvCfg(Solo12ServoFlatEnvCfg):
 class Solo12ServoDelayedActuatorsFlatEnvCfg_PLAY(Solo12ServoDelayedActuatorsFlatEnvCfg):
     scene: SceneCfg = SceneCfg(num_envs=50, env_spacing=3.0, robot=_delayed(SOLO12_MINIMAL_CFG, 0, 4))
     curriculum: object = None
+
+
+def _randomization_terms():
+    """this project's choice of ranges (the reference randomises none of the three): gains +- 20 % per env, a joint friction
+    of up to 0.05 N m per episode, -0.5 .. +1 kg on the base per env"""
+    return dict(
+        actuator_gains=EventTerm(func=events.randomize_actuator_gains, mode="startup",
+                                 params={"asset_cfg": SceneEntityCfg("robot", joint_names=".*"),
+                                         "stiffness_distribution_params": (0.8, 1.2),
+                                         "damping_distribution_params": (0.8, 1.2), "operation": "scale",
+                                         "distribution": "uniform"}),
+        joint_parameters=EventTerm(func=events.randomize_joint_parameters, mode="reset",
+                                   params={"asset_cfg": SceneEntityCfg("robot", joint_names=".*"),
+                                           "friction_distribution_params": (0.0, 0.05), "operation": "abs",
+                                           "distribution": "uniform"}),
+        add_base_mass=EventTerm(func=events.randomize_rigid_body_mass, mode="startup",
+                                params={"asset_cfg": SceneEntityCfg("robot", body_names="base_link"),
+                                        "mass_distribution_params": (-0.5, 1.0), "operation": "add"}))
+
+
+@configclass
+class RandomizationEventCfg:
+    """the robot of every env is its own ("Randomisation"): gains, joint friction and base mass"""
+    actuator_gains = _randomization_terms()["actuator_gains"]
+    joint_parameters = _randomization_terms()["joint_parameters"]
+    add_base_mass = _randomization_terms()["add_base_mass"]
+
+
+@configclass
+class ReferenceRandomizationEventCfg(EventCfg):
+    """the reference's event block with the three randomisation terms added"""
+    actuator_gains = _randomization_terms()["actuator_gains"]
+    joint_parameters = _randomization_terms()["joint_parameters"]
+    add_base_mass = _randomization_terms()["add_base_mass"]
+
+
+@configclass
+class Solo12ServoRandomizedFlatEnvCfg(Solo12ServoActuatorsFlatEnvCfg):
+    """the servo task with the reference's robot, randomised per env: an event block of randomisation terms alone"""
+    events: RandomizationEventCfg = RandomizationEventCfg()
+
+
+@configclass
+class Solo12ServoRandomizedFlatEnvCfg_PLAY(Solo12ServoActuatorsFlatEnvCfg_PLAY):
+    """randomisation stays on, pushes (there are none) off"""
+    events: RandomizationEventCfg = RandomizationEventCfg()
+    pushes: bool = False
+
+
+@configclass
+class Solo12ServoReferenceRandomizedFlatEnvCfg(Solo12ServoReferenceActuatorsFlatEnvCfg):
+    """every MDP block of the reference's cfg, the reference's robot and the three randomisation terms"""
+    events: ReferenceRandomizationEventCfg = ReferenceRandomizationEventCfg()
+
+
+@configclass
+class Solo12ServoReferenceRandomizedFlatEnvCfg_PLAY(Solo12ServoReferenceActuatorsFlatEnvCfg_PLAY):
+    """randomisation stays on, pushes off"""
+    events: ReferenceRandomizationEventCfg = ReferenceRandomizationEventCfg()
 
 
 @configclass

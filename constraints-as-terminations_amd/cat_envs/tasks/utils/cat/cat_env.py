@@ -185,7 +185,7 @@ class Solo12ServoSim(SyntheticSolo12Sim):
     def __init__(self, num_envs: int, obs_dim: int, device, seed: int, syn, dt: float, decimation: int,
                  max_episode_length: int, episode_length: torch.Tensor, reset: torch.Tensor, env_offset: int = 0,
                  policy_obs_dim: int = 0, events: bool = False, commands: bool = False, terminations: bool = False,
-                 actions: bool = False, actuators: bool = False):
+                 actions: bool = False, actuators: bool = False, randomize: bool = False):
         """``policy_obs_dim`` = P > 0: the row gets a second observation field ``policy_obs`` of P floats (padded to a
         multiple of 4) that ``set_observation_table`` configures; the raw field ``obs`` stays what it is.
         ``events``: the descriptor carries the event descriptor, too, and ``set_event_block`` configures it.
@@ -198,7 +198,10 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         column drives which joint, through which scale, offset and clip, as what kind of target); the row stays what it is.
         ``actuators``: the row gets one more field ``act_hist`` of 48 floats behind everything else (three slots of processed
         actions), the descriptor carries the action and the actuator descriptors and ``set_actuator_table`` configures the
-        latter (per-joint gains, inertia, effort limits, DC-motor clamps and the actuator delay)"""
+        latter (per-joint gains, inertia, effort limits, DC-motor clamps and the actuator delay).
+        ``randomize``: the descriptor carries the actuator and the randomisation descriptors and ``set_randomize_block``
+        configures the latter (per-env gains, joint friction, armature and base mass); the row is that of ``actuators``"""
+        actuators = bool(actuators or randomize)
         actions = bool(actions or actuators)
         self.N, self.D, self.device = num_envs, obs_dim, torch.device(device)
         self.P = int(policy_obs_dim)
@@ -235,7 +238,7 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         self._episode_length, self._reset = episode_length, reset       # referenced by the descriptor: keep alive
         self._nat = native.get(self.device)
         # with a policy observation the descriptor carries the observation descriptor behind its 368 bytes
-        d = self._desc = (native.ServoSimActuators() if actuators else native.ServoSimActions() if actions else native.ServoSimTerminations() if terminations
+        d = self._desc = (native.ServoSimRandomize() if randomize else native.ServoSimActuators() if actuators else native.ServoSimActions() if actions else native.ServoSimTerminations() if terminations
                           else native.ServoSimCommands() if commands else native.ServoSimEvents() if events
                           else native.ServoSimObs() if self.P else native.ServoSimRewards())
         d.N, d.env_offset, d.row_stride, d.row_floats = num_envs, int(env_offset), self.F, self.F
@@ -267,6 +270,8 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         self._action_table, self._action_entries, self.action_width = None, [], J   # device table of the action descriptor
         self._actuators = bool(actuators)
         self._actuator_table, self._actuator_entries = None, []         # device table of the actuator descriptor
+        self._randomize = bool(randomize)
+        self._randomize_block, self._randomize_words = None, None       # device block of the randomisation descriptor, its host copy
         self._build_scene()
 
     def _table(self, t, width, what, lead=()):
@@ -435,7 +440,8 @@ class Solo12ServoSim(SyntheticSolo12Sim):
 
     def _announce(self):
         """``reserved`` names the descriptors behind the 368 bytes that are configured by now"""
-        self._desc.reserved = (native.SERVO_EXT_ACTUATORS if self._actuator_table is not None
+        self._desc.reserved = (native.SERVO_EXT_RANDOMIZE if self._randomize_block is not None
+                               else native.SERVO_EXT_ACTUATORS if self._actuator_table is not None
                                else native.SERVO_EXT_ACTIONS if self._action_table is not None
                                else native.SERVO_EXT_TERMINATIONS if self._term_table is not None
                                else native.SERVO_EXT_COMMANDS if self._command_block is not None
@@ -627,6 +633,55 @@ class Solo12ServoSim(SyntheticSolo12Sim):
             self._announce()                                            # from now on every launch reads the table
         self._actuator_table.copy_(torch.frombuffer(bytearray(host), dtype=torch.uint8))
         self._actuator_entries = rows
+
+    def set_randomize_block(self, words):
+        """``words``: the ``native.SERVO_RANDOMIZE_FLOATS`` fp32 words of the randomisation block (``mdp.randomization.pack``;
+        words 0 .. 4 hold the flags, the operations and the masks as integers).  Every following step draws the env's gains,
+        joint friction, armature and base mass inside the simulator's own launch.  The block lives on the device and is
+        rewritten here and nowhere else, in stream order: a new flag word is in the next launch (when nothing but word 0
+        changed, that word alone is copied).  A simulator without an actuator table gets the identity one here, so
+        ``set_actuator_table`` comes first where it is wanted.  The values are checked here - the library cannot read them."""
+        import numpy as np
+        if not self._randomize:
+            raise ValueError("this simulator was built without a randomisation descriptor (randomize = False)")
+        words = np.ascontiguousarray(words, np.float32)
+        if words.shape != (native.SERVO_RANDOMIZE_FLOATS,):
+            raise ValueError(f"the randomisation block has {native.SERVO_RANDOMIZE_FLOATS} words, got shape {words.shape}")
+        W, FL = native.SERVO_RANDOMIZE_WORDS, native.SERVO_RANDOMIZE_FLAGS
+        ints = words.view(np.int32)
+        flags, ops = int(ints[W["flags"]]), int(ints[W["ops"]])
+        if flags & ~sum(FL.values()):
+            raise ValueError(f"randomisation block: flags {flags:#x} has unknown bits")
+        if ops & ~0xFFFFFF or any(((ops >> s) & 0xFF) not in native.SERVO_RANDOMIZE_OPS.values() for s in (0, 8, 16)):
+            raise ValueError(f"randomisation block: operations {ops:#x} (one of 0 scale, 1 add, 2 abs per byte)")
+        if any(int(ints[W[k]]) & ~0xFFF for k in ("gains_mask", "joint_mask")) or int(ints[W["body_mask"]]) & ~1:
+            raise ValueError("randomisation block: the joint masks have 12 bits, the body mask one")
+        if not np.isfinite(words[5:]).all() or words[5] != 0 or words[19] != 0:
+            raise ValueError("randomisation block: every value must be finite and the spare words zero")
+        if (words[7:16:2] < 0).any() or (words[W["armatures"]:] < 0).any():
+            raise ValueError("randomisation block: every width and every armature must be >= 0")
+        if not (words[W["m0"]] > 0 and words[W["g"]] > 0 and words[W["servo_inertia"]] > 0):
+            raise ValueError("randomisation block: m0, g and servo_inertia must be > 0")
+        if flags & FL["friction"] and ((ops >> 8) & 0xFF) == native.SERVO_RANDOMIZE_OPS["scale"]:
+            raise ValueError("randomisation block: friction cannot be scaled, its nominal value is 0")
+        if self._randomize_block is None:
+            if self._actuator_table is None:                            # the identity actuator table (byte-identical to none)
+                self.set_actuator_table(self.identity_actuator_entries())
+            self._randomize_block = torch.zeros(native.SERVO_RANDOMIZE_FLOATS, dtype=torch.float32, device=self.device)
+            r = self._desc.rnd
+            r.block, r.reserved[0], r.reserved[1] = self._randomize_block.data_ptr(), 0, 0
+            self._announce()                                            # from now on every launch reads the block
+        old = self._randomize_words
+        if old is not None and (old.view(np.int32)[1:] == ints[1:]).all():
+            self._randomize_block[:1].copy_(torch.from_numpy(words[:1].copy()))
+        else:
+            self._randomize_block.copy_(torch.from_numpy(words.copy()))
+        self._randomize_words = words.copy()
+
+    @property
+    def randomize_words(self):
+        """the randomisation block as last written (a host copy), or None"""
+        return None if self._randomize_words is None else self._randomize_words.copy()
 
     @property
     def termination_record(self):
@@ -846,6 +901,17 @@ class CaTEnv:
                                 "are evaluated inside its launch; the stream simulator has no joints to drive")
             from cat_envs.tasks.utils.mdp import actuators as UM
             self._actuator_table = UM.build_table(cfg.scene.robot, SOLO12_JOINTS, syn, cfg.decimation, DEFAULT_JOINT_POS)
+        # randomize_actuator_gains / randomize_joint_parameters / randomize_rigid_body_mass among cfg.events: per-env gains,
+        # joint friction, armature and base mass are drawn inside the simulator's launch ("Randomisation");
+        # an EventCfg of such terms alone launches no event pack
+        self._randomization, self._event_pack = None, False
+        if self._event_block is not None:
+            from cat_envs.tasks.utils.mdp import randomization as RZ
+            robot = getattr(cfg.scene, "robot", None)
+            self._randomization = RZ.build_randomization(
+                cfg.events, None if self._actuator_table is None else self._actuator_table[0], SOLO12_JOINTS, syn, cfg.sim.dt,
+                cfg.decimation, armatures=None if robot is None else UM.armatures(robot, SOLO12_JOINTS))[0]
+            self._event_pack = any(k not in EM.RANDOMIZE_KINDS for k in self._event_block["kinds"].values())
         if kind == "stream":
             self.sim = SyntheticSolo12Sim(self.num_envs, self.obs_dim, self.device, seed + int(syn.seed_offset),
                                           int(syn.stream_steps))
@@ -872,9 +938,9 @@ class CaTEnv:
                                       cfg.sim.dt, cfg.decimation, self.max_episode_length, self.episode_length_buf,
                                       self.reset_buf, env_offset=int(getattr(cfg.scene, "env_offset", 0) or 0),
                                       policy_obs_dim=self.obs_dim if self._obs_table is not None else 0,
-                                      events=self._event_block is not None, commands=self._command_block is not None,
+                                      events=self._event_pack, commands=self._command_block is not None,
                                       terminations=self._term_table is not None, actions=self._action_table is not None,
-                                      actuators=self._actuator_table is not None)
+                                      actuators=self._actuator_table is not None, randomize=self._randomization is not None)
             self.scene = self.sim.scene
         self.obs_buf = {"policy": self.sim.view(self._obs_field)}
         self._rstep = None
@@ -919,7 +985,7 @@ class CaTEnv:
             self.action_manager = _ActionManager(self.num_envs, self.act_dim, self.device)
         if self._actuator_table is not None:                           # behind the action manager: its table comes first
             from cat_envs.tasks.utils.mdp.actuator_model import ActuatorModel
-            self.actuators = ActuatorModel(self.cfg.scene.robot, self, self._actuator_table)
+            self.actuators = ActuatorModel(self.cfg.scene.robot, self, self._actuator_table, randomization=self._randomization)
             print("[INFO] Actuator Model: ", self.actuators)
         cmd = self.sim.view("command")
         self.command_manager = types.SimpleNamespace(get_command=lambda name: cmd, reset=lambda ids=None: {},
@@ -947,7 +1013,8 @@ class CaTEnv:
             from cat_envs.tasks.utils.mdp.event_manager import EventManager
             # cfg.pushes = False (the play cfgs): reset and startup terms as configured, interval events off
             self.event_manager = EventManager(self.cfg.events, self, self._event_block,
-                                              interval_enabled=bool(getattr(self.cfg, "pushes", True)))
+                                              interval_enabled=bool(getattr(self.cfg, "pushes", True)),
+                                              randomization=self._randomization)
             print("[INFO] Event Manager: ", self.event_manager)
         if self._term_table is not None:
             from cat_envs.tasks.utils.mdp.termination_manager import TerminationManager
@@ -981,6 +1048,13 @@ class CaTEnv:
         if not hasattr(self, "event_manager"):
             raise TypeError("pushes need cfg.events")
         self.event_manager.set_interval_enabled(on)
+
+    def set_randomization(self, on: bool):
+        """the randomised robot on or off (off: the nominal robot) from the next step on (needs such terms in cfg.events)"""
+        if not hasattr(self, "event_manager"):
+            raise TypeError("randomization needs cfg.events with randomize_actuator_gains, randomize_joint_parameters or "
+                            "randomize_rigid_body_mass")
+        self.event_manager.set_randomization_enabled(on)
 
     def set_eval_record(self, record: torch.Tensor | None):
         """attach (or, with None, detach) the simulator's per-env evaluation record [N, 12]"""

@@ -264,7 +264,8 @@ class EvalResult:
 
 def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool = True,
                     fresh_cat_state: bool = False, segment_steps: int | None = None, trace_envs: int = 0,
-                    corruption: bool | None = None, pushes: bool | None = None) -> EvalResult:
+                    corruption: bool | None = None, pushes: bool | None = None,
+                    randomization: bool | None = None) -> EvalResult:
     """Roll ``policy`` out for ``steps`` control steps from a fresh reset and measure it.
 
     ``policy`` is an ``Agent`` - its observations are normalised by the frozen ``obs_rms`` and the action is the mean
@@ -292,6 +293,9 @@ def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool 
 
     ``pushes`` (envs with ``cfg.events``): None leaves the env's interval-event switch as it is; a bool sets it for the
     evaluation and puts it back afterwards, also when the roll-out raises.  Reset and startup terms stay as configured.
+
+    ``randomization`` (envs whose ``cfg.events`` randomises the robot): None leaves the switch as it is; a bool sets it for
+    the evaluation (False: the nominal robot) and puts it back afterwards, likewise.
 
     On an env with ``cfg.terminations`` the result carries ``termination_share``: per term, the share of the episodes that
     ended during the evaluation whose last step had the term set (the termination manager's record, which the reset zeroes
@@ -352,6 +356,10 @@ def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool 
     if pushes is not None and em is None:
         u.set_eval_record(None)
         raise TypeError("evaluate_policy(pushes=...) needs an env with cfg.events")
+    if randomization is not None and (em is None or em.randomization is None):
+        u.set_eval_record(None)
+        raise TypeError("evaluate_policy(randomization=...) needs an env whose cfg.events randomises the robot")
+    randomization_before = None if em is None else em.randomization_enabled
     pushes_before = None if em is None else em.interval_enabled
     pushes_on = bool(em is not None and (pushes_before if pushes is None else pushes)
                      and em.block["flags"] & 1)        # the env has a push term and it is on for this evaluation
@@ -364,6 +372,8 @@ def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool 
             om.set_corruption(corruption)
         if pushes is not None:
             em.set_interval_enabled(pushes)
+        if randomization is not None:
+            em.set_randomization_enabled(randomization)
         if lead:
             u.set_fixed_commands(table, segment_steps)
         else:
@@ -396,6 +406,8 @@ def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool 
             om.set_corruption(corruption_before)
         if pushes is not None:
             em.set_interval_enabled(pushes_before)
+        if randomization is not None:
+            em.set_randomization_enabled(randomization_before)
     res = EvalResult(per_env=record.cpu().numpy(), commands=None if table is None else table.cpu().numpy(),
                      cat_reward=cat_reward.cpu().numpy(), termination_prob=term_prob.cpu().numpy(),
                      violations=viol.cpu().numpy(), term_names=names, trace=None if trace is None else trace.cpu().numpy(),

@@ -196,14 +196,17 @@ def export_policy_as_onnx(state_dict, path: str, batch=1) -> str:
     return path
 
 
-def export_policy(state_dict, directory: str, observation_spec=None, action_spec=None, actuator_spec=None) -> Dict[str, str]:
+def export_policy(state_dict, directory: str, observation_spec=None, action_spec=None, actuator_spec=None,
+                  randomization_spec=None) -> Dict[str, str]:
     """``<directory>/model.onnx`` + ``<directory>/model.pt`` (play.py:111-135).  ``observation_spec`` (a dict, see
     ``ObservationManager.spec``): also ``<directory>/observations.json``, the input contract of the deployed policy -
     term names, slices, sources, scales, clips and the joint order of the vector the models take.  ``action_spec`` (a dict,
     see ``ActionManager.spec``): also ``<directory>/actions.json``, the output contract - per column of the vector the models
     give: the action term, the joint it drives, the kind of target, scale, offset and clip.  ``actuator_spec`` (a dict, see
     ``ActuatorModel.spec``): ``actions.json`` gets the key ``"actuators"`` - per joint the gains and limits the policy was
-    trained against, per actuator group its kind and delay range; without an ``action_spec`` the file holds that key alone"""
+    trained against, per actuator group its kind and delay range; without an ``action_spec`` the file holds that key alone.
+    ``randomization_spec`` (a dict, see ``EventManager.randomization``): the ranges the robot was randomised over while the
+    policy trained, under ``"actuators": {"randomization": ...}``"""
     out = {"onnx": export_policy_as_onnx(state_dict, os.path.join(directory, "model.onnx")),
            "jit": export_policy_as_jit(state_dict, os.path.join(directory, "model.pt"))}
     if observation_spec is not None:
@@ -211,6 +214,8 @@ def export_policy(state_dict, directory: str, observation_spec=None, action_spec
         out["observations"] = os.path.join(directory, "observations.json")
         with open(out["observations"], "w") as f:
             json.dump(observation_spec, f, indent=1)
+    if randomization_spec is not None:
+        actuator_spec = {**(actuator_spec or {}), "randomization": randomization_spec}
     if action_spec is not None or actuator_spec is not None:
         import json
         spec = dict(action_spec or {})

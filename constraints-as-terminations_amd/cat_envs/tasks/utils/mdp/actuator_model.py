@@ -15,8 +15,10 @@ from . import actuators as UM
 
 
 class ActuatorModel:
-    def __init__(self, robot_cfg, env, table=None):
-        self.cfg, self._env = robot_cfg, env
+    def __init__(self, robot_cfg, env, table=None, randomization=None):
+        """``randomization``: the block of ``mdp.randomization.build_randomization`` when the env randomises the robot;
+        ``set_gains`` then repeats its stability check on the new gains"""
+        self.cfg, self._env, self._randomization = robot_cfg, env, randomization
         self._joint_names = list(env.scene["robot"].joint_names)
         if table is None:
             from cat_envs.tasks.utils.cat.cat_env import DEFAULT_JOINT_POS
@@ -86,6 +88,9 @@ class ActuatorModel:
                 for j, x in zip(ids, UM._per_joint("set_gains", what, value, ids, self._joint_names, 0.0)):
                     new[j][key] = x
         if new != self._entries:
+            if self._randomization is not None:              # the worst corner of the ranges, on the new gains
+                from . import randomization as RZ
+                RZ.check_corners(self._randomization, new, self._env.cfg.sim.dt)
             self._entries = new
             self._push()
 

@@ -144,6 +144,17 @@ def build_table(robot_cfg, joint_names, synthetic_cfg, decimation: int = 4, defa
     return entries, actuator_spec(entries, spec_groups, joint_names, robot_cfg)
 
 
+def armatures(robot_cfg, joint_names) -> list:
+    """the nominal armature of every simulator joint, rounded to fp32 (what ``build_table`` added to ``servo_inertia``)"""
+    joint_names = list(joint_names)
+    out = [0.0] * len(joint_names)
+    for name, a in (getattr(robot_cfg, "actuators", None) or {}).items():
+        ids = _select(name, a.joint_names_expr, joint_names)
+        for j, v in zip(ids, _per_joint(name, "armature", a.armature, ids, joint_names, 0.0)):
+            out[j] = v
+    return out
+
+
 def inert_fields(robot_cfg) -> list:
     """the fields of the robot cfg that are set and do nothing in this model"""
     out = [f for f in INERT_ROBOT_FIELDS if getattr(robot_cfg, f, None) not in (None, 0, False, 1.0)]

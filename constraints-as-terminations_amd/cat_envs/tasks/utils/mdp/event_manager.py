@@ -19,6 +19,8 @@ FLAG = {"push": native.SERVO_EVENT_PUSH, "joint_scale": native.SERVO_EVENT_JOINT
         "joint_offset": native.SERVO_EVENT_JOINT_OFFSET, "root": native.SERVO_EVENT_ROOT,
         "friction": native.SERVO_EVENT_FRICTION}
 MODES = ("startup", "reset", "interval")
+#: kinds the randomisation block evaluates, not the event block (mdp/randomization.py; DESIGN section 9, "Randomisation")
+RANDOMIZE_KINDS = ("actuator_gains", "joint_parameters", "rigid_body_mass")
 #: kind -> what a second term collides with: at most one term per slot
 _SLOT = {"push": "push", "joint_scale": "joint reset", "joint_offset": "joint reset", "root": "root reset", "friction": "material"}
 
@@ -41,7 +43,9 @@ def build_block(cfg, sim_dt, max_episode_length_s):
     """an ``EventCfg`` -> ``{"flags", "p", "num_buckets", "ranges": {group: [(lo, width), ...]}, "terms": {mode: [names]},
     "kinds": {name: kind}, "inert": [...]}``; pure, needs no device, every float already rounded to fp32.  Errors name
     the term: a func without ``describe`` or an unknown mode, an interval term other than the push, a term configured with
-    another mode than its own, a second term of a kind."""
+    another mode than its own, a second term of a kind.  The three randomisation terms (``RANDOMIZE_KINDS``) are listed under
+    their mode, in ``kinds`` and in ``inert`` and fill no word of this block: ``mdp.randomization.build_randomization`` reads
+    them."""
     block = {"flags": 0, "p": 0.0, "num_buckets": 1,
              "ranges": {"push": [(0.0, 0.0)] * 5, "joint_pos": [(0.0, 0.0)], "joint_vel": [(0.0, 0.0)],
                         "root_pos": [(0.0, 0.0)] * 2, "root_vel": [(0.0, 0.0)] * 3, "friction": [(0.0, 0.0)]},
@@ -58,6 +62,18 @@ def build_block(cfg, sim_dt, max_episode_length_s):
             raise ValueError(f"event term '{name}': unknown mode {term.mode!r} (known: {list(MODES)})")
         spec = describe(name, sim_dt, max_episode_length_s, **(term.params or {}))
         kind = spec["kind"]
+        if kind in RANDOMIZE_KINDS:
+            if term.mode not in ("startup", "reset"):
+                raise ValueError(f"event term '{name}': {term.func.__name__} is a 'startup' or 'reset' event, configured as "
+                                 f"{term.mode!r} (interval-mode randomisation is out of scope)")
+            if kind in taken:
+                raise ValueError(f"event term '{name}': a second {term.func.__name__} term (the first is '{taken[kind]}'); at "
+                                 f"most one is evaluated")
+            taken[kind] = name
+            block["terms"][term.mode].append(name)
+            block["kinds"][name] = kind
+            block["inert"] += [f"{name}.{k}" for k in spec["inert"]]
+            continue
         if term.mode == "interval" and kind != "push":
             raise ValueError(f"event term '{name}': the only interval event the simulator evaluates is "
                              f"push_by_setting_velocity_with_random_envs (interval events with per-env timers are out of scope)")
@@ -102,14 +118,25 @@ def pack(block, interval_enabled: bool = True) -> np.ndarray:
 
 
 class EventManager:
-    def __init__(self, cfg: object, env, block=None, interval_enabled: bool = True):
+    def __init__(self, cfg: object, env, block=None, interval_enabled: bool = True, randomization=None):
+        """``randomization``: the block of ``mdp.randomization.build_randomization`` when the cfg carries such terms"""
         self.cfg, self._env = cfg, env
         self._block = block if block is not None else build_block(cfg, env.cfg.sim.dt, env.max_episode_length_s)
         self._interval = bool(interval_enabled)
+        self._rnd, self._rnd_enabled = randomization, True
+        # an EventCfg of randomisation terms alone launches no event pack
+        self._has_events = any(k not in RANDOMIZE_KINDS for k in self._block["kinds"].values())
         self._push()
+        self._push_randomization()
 
     def _push(self):
-        self._env.sim.set_event_block(pack(self._block, self._interval))
+        if self._has_events:
+            self._env.sim.set_event_block(pack(self._block, self._interval))
+
+    def _push_randomization(self):
+        if self._rnd is not None:
+            from . import randomization as RZ
+            self._env.sim.set_randomize_block(RZ.pack(self._rnd, self._rnd_enabled))
 
     # ------------------------------------------------------------------ IsaacLab's names
     @property
@@ -140,6 +167,26 @@ class EventManager:
             self._interval = on
             self._push()                       # only word 0 differs: the simulator copies that word alone
 
+    @property
+    def randomization(self):
+        """the spec of the randomisation terms (kind, mode, operation, ranges and joints per term), or None"""
+        return None if self._rnd is None else self._rnd["spec"]
+
+    @property
+    def randomization_enabled(self) -> bool:
+        return self._rnd is not None and self._rnd_enabled
+
+    def set_randomization_enabled(self, on: bool):
+        """the randomised robot on or off (off: the nominal robot) from the next launch on: one stream-ordered copy of the
+        flag word, in the next launch also under graph replay"""
+        if self._rnd is None:
+            raise TypeError("randomization needs an EventCfg with randomize_actuator_gains, randomize_joint_parameters or "
+                            "randomize_rigid_body_mass")
+        on = bool(on)
+        if on != self._rnd_enabled:
+            self._rnd_enabled = on
+            self._push_randomization()         # only word 0 differs: the simulator copies that word alone
+
     def apply(self, mode: str, env_ids=None, dt=None, global_env_step_count=None):
         """launches nothing: the simulator's own launch evaluates every mode"""
         if mode not in MODES:
@@ -155,6 +202,9 @@ class EventManager:
             for n in names:
                 extra = f" p = {b['p']:g}" if b["kinds"][n] == "push" else ""
                 msg += f"  {mode:<9s} {n:<22s} {b['kinds'][n]}{extra}\n"
+        for n, t in (self._rnd["spec"]["terms"] if self._rnd is not None else {}).items():
+            ranges = ", ".join(f"{q} {tuple(r)}" for q, r in t["ranges"].items() if r is not None)
+            msg += f"  randomisation ({'on' if self._rnd_enabled else 'off'}) {n}: {t['operation']} {ranges}, {len(t['joints'])} joints / bodies\n"
         if b["inert"]:
             msg += f"  without effect on the surrogate: {', '.join(b['inert'])}\n"
         return msg
@@ -164,16 +214,28 @@ class EventManager:
         """names, kinds and every word of the block (pushes as configured): what a loaded state was made with"""
         b = self._block
         words = pack(b, True)
-        return [[n, b["kinds"][n]] for n in b["kinds"]] + [[int(w) for w in words.view(np.int32)]]
+        fp = [[n, b["kinds"][n]] for n in b["kinds"]] + [[int(w) for w in words.view(np.int32)]]
+        if self._rnd is not None:                  # only then: older run states keep their fingerprint
+            from . import randomization as RZ
+            fp.append([int(w) for w in RZ.pack(self._rnd, True).view(np.int32)])
+        return fp
 
     def state_dict(self) -> dict:
-        return {"interval": bool(self._interval)}
+        sd = {"interval": bool(self._interval)}
+        if self._rnd is not None:
+            sd["randomization"] = bool(self._rnd_enabled)
+        return sd
 
     def check_state_dict(self, sd: dict):
         if "interval" not in sd:
             raise ValueError("run state: the events' part lacks 'interval'")
+        if self._rnd is not None and "randomization" not in sd:
+            raise ValueError("run state: the events' part lacks 'randomization'")
 
     def load_state_dict(self, sd: dict):
         self.check_state_dict(sd)
         self._interval = bool(sd["interval"])
         self._push()
+        if self._rnd is not None:
+            self._rnd_enabled = bool(sd["randomization"])
+            self._push_randomization()

@@ -9,6 +9,10 @@ No term does anything in Python.  Each carries ``describe(name, sim_dt, max_epis
 ``(a, b)`` pairs and the params it accepts without effect (``inert``).  The event manager turns that into the block the
 simulator's kernel reads inside its own launch (include/catppo.h, catppo_servo_events).  Calling a term directly raises
 ``TypeError``; an event function without ``describe`` is an error of the manager, not a slow path.
+
+The three randomisation terms at the end (``randomize_actuator_gains``, ``randomize_joint_parameters``,
+``randomize_rigid_body_mass``; DESIGN section 9, "Randomisation") describe themselves in the same way, for either of the modes
+"startup" and "reset"; ``mdp/randomization.py`` turns them into the randomisation block (include/catppo.h, catppo_servo_randomize).
 """
 from __future__ import annotations
 
@@ -129,3 +133,82 @@ def randomize_rigid_body_material(env, env_ids, static_friction_range, dynamic_f
     """each env draws one of ``num_buckets`` shared materials once; its static friction against the ground's 1.0 is the
     env's traction"""
     _refuse("randomize_rigid_body_material")
+
+
+# ---- randomisation of the robot (DESIGN section 9, "Randomisation"): the three terms describe themselves like the others;
+# mdp/randomization.py turns them into the randomisation block, not the event block.  Either mode, "startup" or "reset".
+OPERATIONS = ("scale", "add", "abs")
+
+
+def _randomize_common(name, operation, distribution):
+    if distribution != "uniform":
+        raise ValueError(f"event term '{name}': distribution {distribution!r} is not supported, only 'uniform' (log_uniform "
+                         f"and gaussian need exp / log / cos, which the model's arithmetic excludes)")
+    if operation not in OPERATIONS:
+        raise ValueError(f"event term '{name}': unknown operation {operation!r} (known: {list(OPERATIONS)})")
+
+
+def _names(asset_cfg, field):
+    v = getattr(asset_cfg, field, None) if asset_cfg is not None else None
+    return None if v is None else [v] if isinstance(v, str) else list(v)
+
+
+def _describe_gains(name, sim_dt, max_episode_length_s, asset_cfg=None, stiffness_distribution_params=None,
+                    damping_distribution_params=None, operation="abs", distribution="uniform"):
+    _randomize_common(name, operation, distribution)
+    ranges = {k: None if v is None else _pair(name, k + "_distribution_params", v)
+              for k, v in (("stiffness", stiffness_distribution_params), ("damping", damping_distribution_params))}
+    return {"kind": "actuator_gains", "mode": None, "operation": operation, "quantities": ranges,
+            "joint_names": _names(asset_cfg, "joint_names"), "inert": []}
+
+
+@_term(_describe_gains)
+def randomize_actuator_gains(env, env_ids, asset_cfg, stiffness_distribution_params=None, damping_distribution_params=None,
+                             operation="abs", distribution="uniform"):
+    """stiffness and damping of the selected joints become op(nominal, U(params)), per env (startup) or per episode (reset)"""
+    _refuse("randomize_actuator_gains")
+
+
+def _describe_joint_parameters(name, sim_dt, max_episode_length_s, asset_cfg=None, friction_distribution_params=None,
+                               armature_distribution_params=None, lower_limit_distribution_params=None,
+                               upper_limit_distribution_params=None, operation="abs", distribution="uniform"):
+    _randomize_common(name, operation, distribution)
+    if lower_limit_distribution_params is not None or upper_limit_distribution_params is not None:
+        raise ValueError(f"event term '{name}': lower_limit_distribution_params / upper_limit_distribution_params must be None, "
+                         f"the model has no joint limits")
+    if friction_distribution_params is not None and operation == "scale":
+        raise ValueError(f"event term '{name}': friction_distribution_params with operation 'scale': the nominal joint "
+                         f"friction is 0, and 0 stays 0")
+    ranges = {k: None if v is None else _pair(name, k + "_distribution_params", v)
+              for k, v in (("friction", friction_distribution_params), ("armature", armature_distribution_params))}
+    return {"kind": "joint_parameters", "mode": None, "operation": operation, "quantities": ranges,
+            "joint_names": _names(asset_cfg, "joint_names"), "inert": []}
+
+
+@_term(_describe_joint_parameters)
+def randomize_joint_parameters(env, env_ids, asset_cfg, friction_distribution_params=None, armature_distribution_params=None,
+                               lower_limit_distribution_params=None, upper_limit_distribution_params=None, operation="abs",
+                               distribution="uniform"):
+    """joint friction (a Coulomb torque in N m, nominally 0) and armature of the selected joints become op(nominal, U(params))"""
+    _refuse("randomize_joint_parameters")
+
+
+def _describe_mass(name, sim_dt, max_episode_length_s, asset_cfg=None, mass_distribution_params=None, operation="abs",
+                   distribution="uniform", recompute_inertia=True):
+    import re
+    _randomize_common(name, operation, distribution)
+    if mass_distribution_params is None:
+        raise ValueError(f"event term '{name}': mass_distribution_params is required")
+    bodies = _names(asset_cfg, "body_names")
+    if bodies is not None and not any(re.fullmatch(p, "base_link") for p in bodies):
+        raise ValueError(f"event term '{name}': asset_cfg.body_names {bodies} must match 'base_link', the surrogate has one mass")
+    return {"kind": "rigid_body_mass", "mode": None, "operation": operation,
+            "quantities": {"mass": _pair(name, "mass_distribution_params", mass_distribution_params)}, "joint_names": None,
+            "inert": ["recompute_inertia"]}
+
+
+@_term(_describe_mass)
+def randomize_rigid_body_mass(env, env_ids, asset_cfg, mass_distribution_params, operation="abs", distribution="uniform",
+                              recompute_inertia=True):
+    """the base's mass becomes op(weight / 9.81, U(params)): the load the stance feet share and the base's velocity lag follow it"""
+    _refuse("randomize_rigid_body_mass")

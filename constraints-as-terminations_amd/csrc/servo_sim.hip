@@ -9,7 +9,8 @@
 // for another except through the shuffles.  The next row is assembled in LDS and leaves as coalesced 16-byte stores.
 //   tree16: x += xor-shuffle 8, 4, 2, 1 (width 16)     tree4 (feet): x += xor-shuffle 1, 2
 // The kernel template is servo_sim_kernel.h; this unit holds the entry point and the instances of the packs without an action
-// table, servo_sim_actions.hip those with one, servo_sim_actuators.hip those with an actuator table behind it.
+// table, servo_sim_actions.hip those with one, servo_sim_actuators.hip those with an actuator table behind it,
+// servo_sim_randomize.hip those with a randomisation block behind that.
 #include "servo_sim_kernel.h"
 
 // the descriptor's size is part of the ABI: cat_envs/native.py (ServoSimRewards) and tests/test_servo_reward_twin.py pin it
@@ -41,6 +42,10 @@ static_assert(offsetof(catppo_servo_sim_actuators, act) == 440 && offsetof(catpp
                   sizeof(catppo_servo_actuators) == 16 && offsetof(catppo_servo_actuators, off_act_hist) == 8 &&
                   sizeof(catppo_servo_sim_actuators) == 472 && CATPPO_SERVO_ACT_HIST_FLOATS == 48,
               "catppo_servo_sim_actuators: the actuator descriptor behind the action descriptor");
+static_assert(offsetof(catppo_servo_sim_randomize, actu) == 456 && offsetof(catppo_servo_sim_randomize, rnd) == 472 &&
+                  sizeof(catppo_servo_randomize) == 16 && offsetof(catppo_servo_randomize, reserved) == 8 &&
+                  sizeof(catppo_servo_sim_randomize) == 488 && CATPPO_SERVO_RANDOMIZE_FLOATS == 32,
+              "catppo_servo_sim_randomize: the randomisation descriptor behind the actuator descriptor");
 
 extern "C" int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* desc, void* stream) {
   CATPPO_CHECK_ARG(ctx, ctx != nullptr);
@@ -52,7 +57,9 @@ extern "C" int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* de
   // ... or all four of a catppo_servo_sim_terminations (whose command descriptor may be empty, too)
   // ... or all five of a catppo_servo_sim_actions (whose termination descriptor may be empty, too)
   // ... or all six of a catppo_servo_sim_actuators (whose action descriptor is never empty)
-  const bool ext_actu = d.reserved == CATPPO_SERVO_EXT_ACTUATORS;
+  // ... or all seven of a catppo_servo_sim_randomize (whose actuator descriptor is never empty)
+  const bool ext_rnd = d.reserved == CATPPO_SERVO_EXT_RANDOMIZE;
+  const bool ext_actu = d.reserved == CATPPO_SERVO_EXT_ACTUATORS || ext_rnd;
   const bool ext_act = d.reserved == CATPPO_SERVO_EXT_ACTIONS || ext_actu;
   const bool ext_term = d.reserved == CATPPO_SERVO_EXT_TERMINATIONS || ext_act;
   const bool ext_cmd = d.reserved == CATPPO_SERVO_EXT_COMMANDS || ext_term;
@@ -69,6 +76,7 @@ extern "C" int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* de
   const catppo_servo_actions* ac = ext_act ? &reinterpret_cast<const catppo_servo_sim_actions*>(desc)->act : nullptr;
   if (ac && tm->table == nullptr && tm->terms == 0) tm = nullptr;
   const catppo_servo_actuators* au = ext_actu ? &reinterpret_cast<const catppo_servo_sim_actuators*>(desc)->actu : nullptr;
+  const catppo_servo_randomize* rn = ext_rnd ? &reinterpret_cast<const catppo_servo_sim_randomize*>(desc)->rnd : nullptr;
   CATPPO_CHECK_ARG(ctx, d.N >= 1 && d.N < (int64_t(1) << 31) && d.env_offset >= 0 && d.env_offset + d.N < (int64_t(1) << 32));
   CATPPO_CHECK_ARG(ctx, d.state_in && d.state_out && d.episode_length);
   CATPPO_CHECK_ARG(ctx, d.init || (d.action && d.reset && d.state_in != d.state_out));
@@ -218,12 +226,33 @@ extern "C" int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* de
     if (cm) CATPPO_CHECK_ARG(ctx, hs + hw <= cm->off_cmd_state || hs >= (int64_t)cm->off_cmd_state + 4);
     if (tm) CATPPO_CHECK_ARG(ctx, hs + hw <= tm->off_term_state || hs >= (int64_t)tm->off_term_state + 4);
   }
+  if (rn) {
+    CATPPO_CHECK_ARG(ctx, rn->reserved[0] == 0 && rn->reserved[1] == 0);
+    // the words are device memory: their writer checks them (Solo12ServoSim.set_randomize_block); they are values and
+    // masks, never addresses
+    const void* bk = rn->block;
+    CATPPO_CHECK_ARG(ctx, bk != nullptr && ((uintptr_t)bk % 16) == 0);
+    const void* others[] = {d.state_in, d.state_out, d.eval, d.trace, d.fixed_command, d.reward_rec, (const void*)d.reward_table,
+                            d.action, d.reset, d.episode_length, obs ? (const void*)obs->table : nullptr,
+                            tm ? (const void*)tm->table : nullptr};
+    for (const void* o : others) CATPPO_CHECK_ARG(ctx, bk != o);
+    // the block's 32 words overlap no other block, table or record
+    const uintptr_t b0 = (uintptr_t)bk, b1 = b0 + sizeof(float) * CATPPO_SERVO_RANDOMIZE_FLOATS;
+    const uintptr_t span[][2] = {
+        {(uintptr_t)au->table, sizeof(catppo_servo_actuator_entry) * kJoints},
+        {(uintptr_t)ac->table, sizeof(catppo_servo_action_entry) * kJoints},
+        {ev ? (uintptr_t)ev->block : 0, sizeof(float) * CATPPO_SERVO_EVENT_FLOATS},
+        {cm ? (uintptr_t)cm->block : 0, sizeof(float) * CATPPO_SERVO_COMMAND_FLOATS},
+        {tm ? (uintptr_t)tm->rec : 0, (uintptr_t)d.N * CATPPO_SERVO_TERM_FLOATS * sizeof(float)}};
+    for (const auto& sp : span) CATPPO_CHECK_ARG(ctx, sp[0] == 0 || b1 <= sp[0] || sp[0] + sp[1] <= b0);
+  }
   const unsigned nblk = (unsigned)cdiv64(d.N, kEnvsPerBlock);
   const size_t lds_bytes = (size_t)d.row_floats * kEnvsPerBlock * sizeof(float);
   const int mode = (d.trace || d.fixed_segments > 1) ? kStepResponse : (d.fixed_command || d.eval) ? kEvaluate : kTrain;
   const bool rew = d.reward_terms > 0;
   const hipStream_t st = static_cast<hipStream_t>(stream);
-  if (au) catppo_internal_servo_sim_launch_actuators(mode, rew, nblk, lds_bytes, st, d, obs, ev, cm, tm, *ac, *au);
+  if (rn) catppo_internal_servo_sim_launch_randomize(mode, rew, nblk, lds_bytes, st, d, obs, ev, cm, tm, *ac, *au, *rn);
+  else if (au) catppo_internal_servo_sim_launch_actuators(mode, rew, nblk, lds_bytes, st, d, obs, ev, cm, tm, *ac, *au);
   else if (ac) catppo_internal_servo_sim_launch_actions(mode, rew, nblk, lds_bytes, st, d, obs, ev, cm, tm, *ac);
   else if (tm && cm && obs && ev) launch(mode, rew, nblk, lds_bytes, st, d, *obs, *ev, *cm, *tm);
   else if (tm && cm && ev) launch(mode, rew, nblk, lds_bytes, st, d, *ev, *cm, *tm);

@@ -1,6 +1,7 @@
 // The servo simulator's kernel template, its helpers and launch(): included by servo_sim.hip (the packs without an action
 // table, and the entry point), by servo_sim_actions.hip (the packs with one) and by servo_sim_actuators.hip (the packs with
-// an actuator table behind it), so that the three sets of instances compile side by side.  Everything here has internal linkage.
+// an actuator table behind it) and by servo_sim_randomize.hip (the packs with a randomisation block behind that), so that the
+// four sets of instances compile side by side.  Everything here has internal linkage.
 #pragma once
 #include <type_traits>
 
@@ -18,6 +19,8 @@ constexpr uint32_t kTagPush = 0x50555348u, kTagJvel = 0x4A56454Cu, kTagRoot = 0x
 // "CMDD", "CMDT": command draws and resampling times of the configured command process ("Commands")
 constexpr uint32_t kTagCmdDraw = 0x434D4444u, kTagCmdTime = 0x434D4454u;
 constexpr uint32_t kTagActDelay = 0x41444C59u;                           // "ADLY": the actuator lag ("Actuators")
+// "AGAN", "JPAR", "MASS": the randomised gains, joint parameters and base mass ("Randomisation")
+constexpr uint32_t kTagGains = 0x4147414Eu, kTagJointPar = 0x4A504152u, kTagMass = 0x4D415353u;
 
 // G[k][lane]: the fixed 5 x 12 matrix of the base model (rows vx, vy, wz, roll, pitch)
 __device__ __forceinline__ float gain(int k, int lane) {
@@ -317,6 +320,83 @@ __device__ __forceinline__ float actuator_clamp(const ActuRegs<true>& ur, float 
   return (ur.entry.flags & CATPPO_SERVO_ACTUATOR_DC_MOTOR) ? dc : ideal;
 }
 
+// what a lane keeps of the randomised robot of its env (lane j: joint j); empty without the randomisation block
+template <bool kOn>
+struct RndRegs {};
+template <>
+struct RndRegs<true> {
+  float kp = 0.f, kd = 0.f, inertia = 1.f;                 // in the place of the actuator entry's
+  float fr = 0.f, df = 0.f;                                // the Coulomb torque and the speed it takes off per substep
+  float weight = 0.f, av = 0.f;                            // in the place of d.weight and d.vel_alpha
+  float mine = 0.f, arm = 0.f;                             // wave lane k < 32: word k of the block; lane j: word 20 + j
+};
+
+// ... or the randomised one of the lane's joint
+template <bool kActu>
+__device__ __forceinline__ float inertia_of(const catppo_servo_sim& d, const ActuRegs<kActu>& ur, const RndRegs<true>& rr) {
+  return rr.inertia;
+}
+template <bool kActu>
+__device__ __forceinline__ float inertia_of(const catppo_servo_sim& d, const ActuRegs<kActu>& ur, const RndRegs<false>&) {
+  return inertia_of(d, ur);
+}
+
+// the load the stance feet share and the gain of the base's velocity lags: the descriptor's, or the env's own
+__device__ __forceinline__ float weight_of(const catppo_servo_sim& d, const RndRegs<false>&) { return d.weight; }
+__device__ __forceinline__ float weight_of(const catppo_servo_sim&, const RndRegs<true>& rr) { return rr.weight; }
+__device__ __forceinline__ float vel_alpha_of(const catppo_servo_sim& d, const RndRegs<false>&) { return d.vel_alpha; }
+__device__ __forceinline__ float vel_alpha_of(const catppo_servo_sim&, const RndRegs<true>& rr) { return rr.av; }
+
+// ... with randomised gains in the place of the entry's
+__device__ __forceinline__ float servo_tau(const ActRegs<true>& ar, const RndRegs<true>& rr, float p, float def, float q, float qd) {
+  const int kind = (int)(ar.entry.flags & CATPPO_SERVO_ACTION_KIND_MASK);
+  const float tgt = kind == 1 ? p : kind == 2 ? p + q : def;
+  const float pd = rr.kp * (tgt - q) - rr.kd * qd;
+  const float vel = rr.kd * (p - qd);
+  return kind == 3 ? vel : kind == 4 ? p : pd;
+}
+
+// one rounded operation on the nominal value x: 0 "scale", 1 "add", 2 "abs"
+__device__ __forceinline__ float rnd_op(uint32_t op, float x, float s) { return op == 0u ? x * s : op == 1u ? x + s : s; }
+
+// the robot of (env, episode): the actuator entry's gains and inertia, d.weight and d.vel_alpha, or what the randomisation
+// block's terms make of them.  rr.mine: wave lane k < 32 has loaded word k; every branch on a flag is wave-uniform, a term that
+// is off draws no Philox block.  rr.arm: the nominal armature of the lane's joint (word 20 + lane)
+__device__ __forceinline__ void randomize(const catppo_servo_sim& d, const ActuRegs<true>& ur, uint32_t gid, uint32_t ep, int lane,
+                                          RndRegs<true>& rr) {
+  const float mine = rr.mine, arm = rr.arm;
+  rr.kp = ur.entry.kp, rr.kd = ur.entry.kd, rr.inertia = ur.entry.inertia;
+  rr.fr = 0.f, rr.df = 0.f, rr.weight = d.weight, rr.av = d.vel_alpha;
+  const uint32_t flags = (uint32_t)__float_as_int(ev_word(mine, 0));
+  if (!(flags & CATPPO_SERVO_RANDOMIZE_ENABLE)) return;
+  const uint32_t ops = (uint32_t)__float_as_int(ev_word(mine, 1));
+  if (flags & (CATPPO_SERVO_RANDOMIZE_KP | CATPPO_SERVO_RANDOMIZE_KD)) {
+    const bool sel = (((uint32_t)__float_as_int(ev_word(mine, 2)) >> lane) & 1u) != 0u;
+    const rng::u32x4 r = ev_block(d, gid, (flags & CATPPO_SERVO_RANDOMIZE_GAINS_RESET) ? ep : 0u, (uint32_t)lane, kTagGains);
+    const float s0 = ev_word(mine, 6) + rng::uniform_open(r.x) * ev_word(mine, 7);
+    const float s1 = ev_word(mine, 8) + rng::uniform_open(r.y) * ev_word(mine, 9);
+    if ((flags & CATPPO_SERVO_RANDOMIZE_KP) && sel) rr.kp = rnd_op(ops & 0xFFu, ur.entry.kp, s0);
+    if ((flags & CATPPO_SERVO_RANDOMIZE_KD) && sel) rr.kd = rnd_op(ops & 0xFFu, ur.entry.kd, s1);
+  }
+  if (flags & (CATPPO_SERVO_RANDOMIZE_FRICTION | CATPPO_SERVO_RANDOMIZE_ARMATURE)) {
+    const bool sel = (((uint32_t)__float_as_int(ev_word(mine, 3)) >> lane) & 1u) != 0u;
+    const rng::u32x4 r = ev_block(d, gid, (flags & CATPPO_SERVO_RANDOMIZE_JOINT_RESET) ? ep : 0u, (uint32_t)lane, kTagJointPar);
+    const float s0 = ev_word(mine, 10) + rng::uniform_open(r.x) * ev_word(mine, 11);
+    const float s1 = ev_word(mine, 12) + rng::uniform_open(r.y) * ev_word(mine, 13);
+    const uint32_t op = (ops >> 8) & 0xFFu;
+    if ((flags & CATPPO_SERVO_RANDOMIZE_FRICTION) && sel) rr.fr = rnd_op(op, 0.f, s0);
+    if ((flags & CATPPO_SERVO_RANDOMIZE_ARMATURE) && sel) rr.inertia = ev_word(mine, 18) + rnd_op(op, arm, s1);
+    rr.df = (rr.fr / rr.inertia) * d.dt;
+  }
+  if (flags & CATPPO_SERVO_RANDOMIZE_MASS) {
+    const rng::u32x4 r = ev_block(d, gid, (flags & CATPPO_SERVO_RANDOMIZE_MASS_RESET) ? ep : 0u, 0u, kTagMass);
+    const float m0 = ev_word(mine, 16);
+    const float m = rnd_op((ops >> 16) & 0xFFu, m0, ev_word(mine, 14) + rng::uniform_open(r.x) * ev_word(mine, 15));
+    rr.weight = m * ev_word(mine, 17);
+    rr.av = fminf(d.vel_alpha / (m / m0), 1.f);
+  }
+}
+
 // kMode = kTrain is the launch with all three evaluation pointers NULL: everything they add is compiled out of it, so
 // that a training step runs the code it ran before the fields existed.  kEvaluate: a fixed-command table [N, 3] or an
 // evaluation record, and nothing else - the evaluation that runs inside training keeps the code it had, too.
@@ -348,6 +428,10 @@ __device__ __forceinline__ float actuator_clamp(const ActuRegs<true>& ur, float 
 // of the actuator table stands where d.kp, d.kd, d.inertia and d.tau_max stand, a DC motor's clamp follows the substep's qd,
 // and the processed action may act late by the env's lag, out of three history slots of the row.  Orthogonal to the rest,
 // compiled out without it: 64 more instances (16 packs, evaluation folded as above), compiled in servo_sim_actuators.hip.
+// catppo_servo_randomize, last in the pack and only behind catppo_servo_actuators ("Randomisation"): the
+// env's own gains, joint inertia, joint friction, foot load and velocity-lag gain, re-derived in every step from stateless
+// draws, stand where the actuator entry's and the descriptor's stand.  Orthogonal to the rest, compiled out without it: 64
+// more instances (16 packs, evaluation folded as above), compiled in servo_sim_randomize.hip.
 template <int kMode, bool kRew, typename... Ext>
 __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeof...(Ext) == 0) ? 8 : 1) void servo_sim_kernel(
     const catppo_servo_sim d, const Ext... ext) {
@@ -358,8 +442,11 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
   constexpr bool kAct = (std::is_same_v<Ext, catppo_servo_actions> || ...);
   constexpr bool kActu = (std::is_same_v<Ext, catppo_servo_actuators> || ...);
   static_assert(kAct || !kActu, "the actuator descriptor comes only behind the action descriptor");
+  constexpr bool kRnd = (std::is_same_v<Ext, catppo_servo_randomize> || ...);
+  static_assert(kActu || !kRnd, "the randomisation descriptor comes only behind the actuator descriptor");
   constexpr bool kEval = kMode != kTrain;
-  ActuRegs<kActu> UR;                    // declared first: further down it reorders two register initialisations of older instances
+  RndRegs<kRnd> RR;                      // declared first: further down it reorders register initialisations of older instances
+  ActuRegs<kActu> UR;                    // likewise
   extern __shared__ float4 lds4[];
   float* lds = reinterpret_cast<float*>(lds4);
   const int tid = threadIdx.x, lane = tid & 15, grp = tid >> 4;
@@ -480,6 +567,12 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
   // lane j < 12 loads entry j of the actuator table (two 16-byte loads), long before the substep loop reads it
   if constexpr (kActu)
     if (lane < kJoints && d.init == 0) UR.entry = ext_of<catppo_servo_actuators>(ext...).table[lane];
+  // wave lane k < 32 loads word k of the randomisation block, lane j < 12 the nominal armature of its joint as well
+  if constexpr (kRnd) {
+    const float* blk = ext_of<catppo_servo_randomize>(ext...).block;
+    if ((tid & 63) < CATPPO_SERVO_RANDOMIZE_FLOATS && d.init == 0) RR.mine = blk[tid & 63];
+    if (lane < kJoints && d.init == 0) RR.arm = blk[20 + lane];
+  }
 
   if (init) {
     // the first state of episode 0: default pose + noise, at rest, four feet on the ground
@@ -570,12 +663,17 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
       }
       if (UR.entry.flags & CATPPO_SERVO_ACTUATOR_DC_MOTOR) UR.vl = UR.entry.velocity_limit;
     }
+    // randomisation: the robot of this env and episode
+    if constexpr (kRnd) randomize(d, UR, gid, ep, lane, RR);
     // ---- joints: `decimation` substeps of the clamped PD servo, semi-implicit Euler; the substep of largest |tau| is reported
     const float q_des = def + d.action_scale * a;
     float tau_w = 0.f;
     for (int s = 0; s < d.decimation; ++s) {
       float tau, qdd;
-      if constexpr (kActu) {
+      if constexpr (kRnd) {
+        tau = actuator_clamp(UR, servo_tau(AR, RR, delayed_p(UR, s, d.decimation, act_p), def, q, qd), qd);
+        qdd = tau / RR.inertia;
+      } else if constexpr (kActu) {
         tau = actuator_clamp(UR, servo_tau(AR, UR, delayed_p(UR, s, d.decimation, act_p), def, q, qd), qd);
         qdd = tau / UR.entry.inertia;
       } else {
@@ -584,6 +682,8 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
         qdd = tau / d.inertia;
       }
       qd = qd + qdd * d.dt;
+      // joint friction: an impulse that cannot reverse the joint within the substep
+      if constexpr (kRnd) qd = RR.fr > 0.f ? qd - fminf(fmaxf(qd, -RR.df), RR.df) : qd;
       q = q + qd * d.dt;
       if (fabsf(tau) > fabsf(tau_w)) tau_w = tau;
     }
@@ -624,7 +724,7 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
     for (int k = 0; k < 3; ++k) {
       float v0 = rst ? 0.f : xin[k];
       if constexpr (kEv) v0 = pushed ? push_v[k] : rst ? first_v[k] : xin[k];
-      v[k] = v0 + d.vel_alpha * (red[k] - v0);
+      v[k] = v0 + vel_alpha_of(d, RR) * (red[k] - v0);
     }
     const float roll0 = rst ? 0.f : xin[3], pitch0 = rst ? 0.f : xin[4];
     float roll_k = roll0, pitch_k = pitch0;
@@ -650,7 +750,7 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
     const float air0 = rst ? 0.f : xin[5 + f];
     const float last_air0 = rst ? 0.f : in[d.off_last_air_time + foot_body];
     const bool touch = con > 0.f && !(con_prev > 0.f);
-    const float fz = con > 0.f ? d.weight / nsafe + (touch ? d.impact_gain * fabsf(knee_v) : 0.f) : 0.f;
+    const float fz = con > 0.f ? weight_of(d, RR) / nsafe + (touch ? d.impact_gain * fabsf(knee_v) : 0.f) : 0.f;
     const float last_air = touch ? air0 : last_air0;
     const float air = con > 0.f ? 0.f : air0 + step_dt;
     const float fbase = z < d.min_height ? d.base_stiffness * (d.min_height - z) : 0.f;
@@ -713,7 +813,7 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
     // ---- reward terms: value_k = (raw_k * weight_k) * step_dt in table order, summed from 0.f; lane k keeps value_k
     float rsum = 0.f, mine = 0.f;
     if constexpr (kRew) {
-      const float acc = tau_w / inertia_of(d, UR), da = a - a_prev;
+      const float acc = tau_w / inertia_of(d, UR, RR), da = a - a_prev;
       const float moving = sqrtf(cmd[0] * cmd[0] + cmd[1] * cmd[1]) > 0.1f ? 1.f : 0.f;
       for (int k = 0; k < d.reward_terms; ++k) {
         // lanes 0 .. 15 of the wave are its first lane group: lane k of the wave holds entry k
@@ -799,7 +899,7 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
     if (isj) {
       row[d.off_joint_pos + lane] = q;
       row[d.off_joint_vel + lane] = qd;
-      row[d.off_joint_acc + lane] = tau_w / inertia_of(d, UR);
+      row[d.off_joint_acc + lane] = tau_w / inertia_of(d, UR, RR);
       row[d.off_applied_torque + lane] = tau_w;
       float o_q = dq, o_v = qd, o_a = a;
       if constexpr (kEv) {
@@ -959,7 +1059,7 @@ void launch(int mode, bool rew, unsigned nblk, size_t lds_bytes, hipStream_t str
   // command table through two wave-uniform branches and compute the same bits): a third fewer instances to compile
   // (packs with an action table likewise)
   constexpr int kEvalAs = ((std::is_same_v<Ext, catppo_servo_terminations> || std::is_same_v<Ext, catppo_servo_actions> ||
-                            std::is_same_v<Ext, catppo_servo_actuators>) || ...)
+                            std::is_same_v<Ext, catppo_servo_actuators> || std::is_same_v<Ext, catppo_servo_randomize>) || ...)
                               ? kStepResponse : kEvaluate;
   const Kernel table[3][2] = {{servo_sim_kernel<kTrain, false, Ext...>, servo_sim_kernel<kTrain, true, Ext...>},
                               {servo_sim_kernel<kEvalAs, false, Ext...>, servo_sim_kernel<kEvalAs, true, Ext...>},
@@ -982,3 +1082,10 @@ void catppo_internal_servo_sim_launch_actuators(int mode, bool rew, unsigned nbl
                                                 const catppo_servo_events* ev, const catppo_servo_commands* cm,
                                                 const catppo_servo_terminations* tm, const catppo_servo_actions& act,
                                                 const catppo_servo_actuators& actu);
+
+// servo_sim_randomize.hip: the launch of a pack that ends with the action, actuator and randomisation descriptors
+void catppo_internal_servo_sim_launch_randomize(int mode, bool rew, unsigned nblk, size_t lds_bytes, hipStream_t stream,
+                                                const catppo_servo_sim& d, const catppo_servo_obs* obs,
+                                                const catppo_servo_events* ev, const catppo_servo_commands* cm,
+                                                const catppo_servo_terminations* tm, const catppo_servo_actions& act,
+                                                const catppo_servo_actuators& actu, const catppo_servo_randomize& rnd);

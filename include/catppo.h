@@ -729,7 +729,7 @@ typedef struct catppo_servo_sim {
   const uint8_t* reset;                  /* [N] */
   const int64_t* episode_length;         /* [N], before this step's increment */
   int64_t max_episode_length;
-  int32_t decimation, resample_steps, init, reserved;   /* reserved: 0 or one of CATPPO_SERVO_EXT_OBS / _EVENTS / _COMMANDS / _TERMINATIONS / _ACTIONS / _ACTUATORS (see below) */
+  int32_t decimation, resample_steps, init, reserved;   /* reserved: 0 or one of CATPPO_SERVO_EXT_OBS / _EVENTS / _COMMANDS / _TERMINATIONS / _ACTIONS / _ACTUATORS / _RANDOMIZE (see below) */
   uint64_t seed;
   float default_joint_pos[12];
   float dt, kp, kd, inertia, tau_max, action_scale, vel_alpha, tilt_beta, tilt_max, reward_scale, foot_clearance,
@@ -1048,6 +1048,62 @@ typedef struct catppo_servo_sim_actuators {
   catppo_servo_actions act;               /* table never NULL */
   catppo_servo_actuators actu;
 } catppo_servo_sim_actuators;
+
+/* Randomisation ("Randomisation").  desc->reserved == CATPPO_SERVO_EXT_RANDOMIZE: `desc` is the head of a
+ * catppo_servo_sim_randomize, i.e. the catppo_servo_sim_actuators above with a randomisation descriptor behind it.  The six
+ * descriptors before it are checked and used exactly as under CATPPO_SERVO_EXT_ACTUATORS (a launch without a robot passes
+ * the identity actuator table and the identity action table).  Every older value of `reserved` keeps its meaning.
+ * rnd.block is a DEVICE array of CATPPO_SERVO_RANDOMIZE_FLOATS (32) fp32 words, 16-byte aligned, read by every launch that
+ * is no init launch (a word the host rewrites in stream order is in the next launch, under graph replay too; a device block
+ * because a descriptor is copied into a captured graph's kernel arguments once).  Wave lane k < 32 loads word k, the body
+ * reads through readlane: every branch on a flag is wave-uniform.
+ *   word 0  flags (integer): CATPPO_SERVO_RANDOMIZE_ENABLE | _KP | _KD | _FRICTION | _ARMATURE | _MASS (one bit per
+ *           quantity) | _GAINS_RESET | _JOINT_RESET | _MASS_RESET (the term draws per episode, not once per env)
+ *   word 1  operations (integer): gains | joint parameters << 8 | mass << 16; 0 "scale" x * s, 1 "add" x + s, 2 "abs" s
+ *   words 2 .. 4  12-bit joint masks (integers): gains, joint parameters, and the body mask of the mass term (bit 0 = base_link)
+ *   word 5  zero
+ *   words 6 .. 15  (lo, width) of stiffness, damping, friction, armature, mass: a sample is s = lo + u * width
+ *   words 16 .. 18  m0 = f32(weight / 9.81), g = f32(9.81), servo_inertia        word 19  zero
+ *   words 20 .. 31  the nominal armature of joint 0 .. 11
+ * Draws: Philox4x32-10, key = sim.seed, counter {global env id, e, third, tag}, u = uniform_open(word); e = 0, or the row's
+ * episode word under the term's _RESET bit.  Nothing is stored: lane j re-derives its values in every step.
+ *   gains, tag "AGAN", third = j: kp' = op(entry.kp, s(word 0)), kd' = op(entry.kd, s(word 1)) for the joints of mask 0
+ *   joint parameters, tag "JPAR", third = j, for the joints of mask 1: fr = op(0.f, s(word 0)) (a Coulomb torque, N m);
+ *     armature' = op(armature_j, s(word 1)), inertia' = servo_inertia + armature' (without _ARMATURE: entry.inertia)
+ *   mass, tag "MASS", third = 0: m' = op(m0, s(word 0)); the stance feet share m' * g where they shared sim.weight;
+ *     rho = m' / m0 and the three velocity lags of the base use fminf(sim.vel_alpha / rho, 1.f) where they used sim.vel_alpha
+ * kp', kd' and inertia' stand wherever entry.kp, entry.kd and entry.inertia stand under CATPPO_SERVO_EXT_ACTUATORS.  Per
+ * substep, after the clamp (tau, tau_w and applied_torque keep the actuator's torque before friction):
+ *   qd_free = qd + qdd * dt        df = (fr / inertia') * dt  (once per lane)
+ *   qd = fr > 0.f ? qd_free - fminf(fmaxf(qd_free, -df), df) : qd_free        q = q + qd * dt
+ * With _ENABLE clear, or no quantity bit set, the launch draws nothing and computes the bits of the launch under
+ * CATPPO_SERVO_EXT_ACTUATORS.  The block's writer checks its values (Solo12ServoSim.set_randomize_block); whatever it holds
+ * the launch stays inside its rows: samples are only ever floats, masks only select. */
+#define CATPPO_SERVO_EXT_RANDOMIZE 0x524E4431      /* "RND1": value of catppo_servo_sim.reserved that announces catppo_servo_sim_randomize */
+#define CATPPO_SERVO_RANDOMIZE_FLOATS 32
+#define CATPPO_SERVO_RANDOMIZE_ENABLE 0x1u
+#define CATPPO_SERVO_RANDOMIZE_KP 0x2u
+#define CATPPO_SERVO_RANDOMIZE_KD 0x4u
+#define CATPPO_SERVO_RANDOMIZE_FRICTION 0x8u
+#define CATPPO_SERVO_RANDOMIZE_ARMATURE 0x10u
+#define CATPPO_SERVO_RANDOMIZE_MASS 0x20u
+#define CATPPO_SERVO_RANDOMIZE_GAINS_RESET 0x100u
+#define CATPPO_SERVO_RANDOMIZE_JOINT_RESET 0x200u
+#define CATPPO_SERVO_RANDOMIZE_MASS_RESET 0x400u
+typedef struct catppo_servo_randomize {
+  const float* block;                     /* DEVICE array [32], 16-byte aligned */
+  int32_t reserved[2];                    /* 0 */
+} catppo_servo_randomize;
+typedef struct catppo_servo_sim_randomize {
+  catppo_servo_sim sim;                   /* sim.reserved = CATPPO_SERVO_EXT_RANDOMIZE */
+  catppo_servo_obs obs;                   /* width 0 and table NULL: no observation table */
+  catppo_servo_events ev;                 /* block NULL and floats 0: no events */
+  catppo_servo_commands cmd;              /* block NULL and floats 0: no commands */
+  catppo_servo_terminations term;         /* table NULL and terms 0: no terminations */
+  catppo_servo_actions act;               /* table never NULL */
+  catppo_servo_actuators actu;            /* table never NULL */
+  catppo_servo_randomize rnd;
+} catppo_servo_sim_randomize;
 
 /* ---- test hook (ABI 0.6) ------------------------------------------------------------------------------------------
  * buf != NULL ([2][M] int32, device): the head / loss kernel of every following catppo_ppo_minibatch_* call writes the clip

@@ -64,6 +64,8 @@ def main(argv=None):
                         help="Observation noise of a task with cfg.observations (default: what the task's cfg says).")
     parser.add_argument("--pushes", choices=("on", "off"), default=None,
                         help="Interval events (pushes) of a task with cfg.events (default: what the task's cfg says).")
+    parser.add_argument("--randomization", choices=("on", "off"), default=None,
+                        help="Randomised robot of a task whose cfg.events randomises it (default: on; off: the nominal robot).")
     parser.add_argument("--push_probability", type=float, default=None, metavar="P",
                         help="Push probability per env and control step of a task with a push term (default: the reference's).")
     cli_args.add_clean_rl_args(parser)
@@ -107,6 +109,11 @@ def main(argv=None):
     print(f"[INFO] Loading model: {resume_path}")
 
     env = make(args_cli.task, cfg=env_cfg)
+    if args_cli.randomization is not None:
+        em = getattr(env.unwrapped, "event_manager", None)
+        if em is None or em.randomization is None:
+            parser.error("--randomization needs a task whose cfg.events randomises the robot")
+        em.set_randomization_enabled(args_cli.randomization == "on")
     actor = Agent(env, hidden=tuple(agent_cfg.hidden), mlp_precision=str(getattr(agent_cfg, "mlp_precision", "fp32")))
     actor.load_state_dict(torch.load(resume_path, map_location=actor.flat.device))
     actor.eval()
@@ -118,7 +125,8 @@ def main(argv=None):
     exported = export_policy(actor.state_dict(), os.path.join(os.path.dirname(resume_path), "exported"),
                              observation_spec=None if om is None else om.spec(),
                              action_spec=am.spec() if hasattr(am, "spec") else None,
-                             actuator_spec=um.spec() if um is not None else None)
+                             actuator_spec=um.spec() if um is not None else None,
+                             randomization_spec=getattr(getattr(env.unwrapped, "event_manager", None), "randomization", None))
     print(f"[INFO] Exported ONNX model to {exported['onnx']}")
     print(f"[INFO] Exported .pt model to {exported['jit']}")
     if om is not None:

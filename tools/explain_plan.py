@@ -16,7 +16,8 @@ names the instance of the servo simulator's kernel a task's training step launch
 (csrc/servo_sim_kernel.h, instantiated in servo_sim.hip, with actions in servo_sim_actions.hip and with a robot in
 servo_sim_actuators.hip).
 The servo tasks are ``...-Solo12-Servo-v0`` and its ``-Rewards``, ``-Obs``, ``-Events``, ``-Full``, ``-Commands``, ``-Reference``,
-``-Terminations``, ``-Reference-Terminations``, ``-Actions`` and ``-Reference-Actions`` variants."""
+``-Terminations``, ``-Reference-Terminations``, ``-Actions``, ``-Reference-Actions``, ``-Actuators``, ``-Reference-Actuators``,
+``-DelayedActuators``, ``-Randomized`` (servo_sim_randomize.hip) and ``-Reference-Randomized`` variants."""
 import argparse
 import os
 import sys
@@ -72,14 +73,19 @@ def explain_task(task):
     if str(getattr(cfg.synthetic, "kind", "stream")) != "servo":
         return f"== {task}: the stream simulator (no simulator kernel; the state is a pre-generated stream)"
     has = {k: getattr(cfg, k, None) is not None for k in ("rewards", "observations", "events", "commands", "terminations", "actions")}
+    from cat_envs.tasks.utils.mdp import randomization as RZ
+    event_terms, rnd_terms = RZ.split_events(getattr(cfg, "events", None))   # randomisation terms alone need no event pack
+    packed = dict(has, events=bool(event_terms))
     pack = [name for key, name in (("observations", "catppo_servo_obs"), ("events", "catppo_servo_events"),
                                    ("commands", "catppo_servo_commands"), ("terminations", "catppo_servo_terminations"),
-                                   ("actions", "catppo_servo_actions")) if has[key]]
+                                   ("actions", "catppo_servo_actions")) if packed[key]]
     robot = getattr(cfg.scene, "robot", None)
-    if robot is not None:                        # the actuator descriptor comes behind an action descriptor, the identity one if need be
+    if robot is not None or rnd_terms:           # the actuator descriptor comes behind an action descriptor, the identity one if need be
         pack += ([] if has["actions"] else ["catppo_servo_actions"]) + ["catppo_servo_actuators"]
+    if rnd_terms:                                # ... and the randomisation descriptor behind an actuator descriptor, likewise
+        pack += ["catppo_servo_randomize"]
     row = 308 + (48 if has["observations"] else 0) + (4 if has["commands"] else 0) + (4 if has["terminations"] else 0)
-    row += 48 if robot is not None else 0
+    row += 48 if robot is not None or rnd_terms else 0
     has["scene.robot"] = robot is not None
     out = [f"== {task}: " + ", ".join(f"cfg.{k} {'set' if v else 'unset'}" for k, v in has.items()),
            f"servo_sim_kernel<kTrain, {'true' if has['rewards'] else 'false'}{''.join(', ' + n for n in pack)}>: row of {row} floats "
@@ -113,6 +119,18 @@ def explain_task(task):
         for j in spec["joints"]:
             out.append(f"  joint {j['joint_id']:2d} {j['joint']:<7s} group '{j['group']}': stiffness {j['stiffness']:g}, damping "
                        f"{j['damping']:g}, inertia {j['inertia']:g}, effort limit {j['effort_limit']:g}")
+    if rnd_terms:
+        import cat_envs.tasks.utils.cat.cat_env as E
+        from cat_envs.tasks.utils.mdp import actuators as UM
+        entries = None if robot is None else UM.build_table(robot, E.SOLO12_JOINTS, cfg.synthetic, cfg.decimation, E.DEFAULT_JOINT_POS)[0]
+        _, spec = RZ.build_randomization(cfg.events, entries, E.SOLO12_JOINTS, cfg.synthetic, cfg.sim.dt, cfg.decimation,
+                                         armatures=None if robot is None else UM.armatures(robot, E.SOLO12_JOINTS))
+        out.append(f"randomisation (servo_sim_randomize.hip): nominal mass {spec['nominal_mass']:g} kg, friction in "
+                   f"{spec['friction_unit']}; inert: {', '.join(spec['inert']) or 'none'}")
+        for n, t in spec["terms"].items():
+            ranges = ", ".join(f"{q} {tuple(r)}" for q, r in t["ranges"].items() if r is not None)
+            out.append(f"  {t['mode']:<7s} '{n}' ({t['func']}): {t['operation']} {ranges} on {len(t['joints'])} of "
+                       f"{'the bodies' if t['kind'] == 'rigid_body_mass' else 'the joints'}")
     return "\n".join(out)
 
 

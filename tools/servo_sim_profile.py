@@ -42,6 +42,10 @@ one ideal PD group, stiffness 4, damping 0.2, armature 0.00036207, effort limit 
 full pack.  profiles/servo_actuators_kernel_stats.csv: the parent's library and this library without a flag, both with
 --reference-actions, and this library with --actuators reference and --actuators delayed, alternating in one session, every
 run listed.
+--randomize runs that row with the reference's robot and the three randomisation terms of ``RandomizationEventCfg``
+(Isaac-Velocity-CaT-Flat-Solo12-Servo-Reference-Randomized-v0), so that the simulator's launch is the randomisation-on training
+instance of the full pack.  profiles/servo_randomize_kernel_stats.csv: the parent's library without a robot and with
+--actuators reference, this library likewise and with --randomize, alternating in one session, every run listed.
 
 Per env step the trace shows servo_sim_kernel (the simulator), the two launches of catppo_rollout_pre, the one of
 catppo_rollout_post and the policy forward."""
@@ -71,8 +75,10 @@ def main():
     ap.add_argument("--reference-actions", action="store_true", help="the task with all six MDP blocks of the reference")
     ap.add_argument("--actuators", choices=("reference", "delayed"), default=None,
                     help="... and the reference's robot, or its gains behind an actuator delay of 0 .. 4 physics steps")
+    ap.add_argument("--randomize", action="store_true",
+                    help="... and RandomizationEventCfg's three terms on top of the reference's robot (-Reference-Randomized)")
     a = ap.parse_args()
-    if a.obs + a.rewards + a.events + a.commands + a.terminations + a.actions + a.reference_actions + (a.actuators is not None) > 1:
+    if a.obs + a.rewards + a.events + a.commands + a.terminations + a.actions + a.reference_actions + (a.actuators is not None) + a.randomize > 1:
         ap.error("--obs, --rewards, --events, --commands, --terminations, --actions, --reference-actions and --actuators are "
                  "separate arms")
     import cat_envs.tasks  # noqa: F401
@@ -86,6 +92,7 @@ def main():
             "Isaac-Velocity-CaT-Flat-Solo12-Servo-Actions-v0" if a.actions else
             "Isaac-Velocity-CaT-Flat-Solo12-Servo-Reference-Actions-v0" if a.reference_actions else
             "Isaac-Velocity-CaT-Flat-Solo12-Servo-Reference-Actuators-v0" if a.actuators else
+            "Isaac-Velocity-CaT-Flat-Solo12-Servo-Reference-Randomized-v0" if a.randomize else
             "Isaac-Velocity-CaT-Flat-Solo12-Servo-v0")
     env_cfg = load_cfg_from_registry(task, "env_cfg_entry_point")
     if a.rewards:
@@ -153,6 +160,9 @@ def main():
         g = um.get_group("legs")
         print(f"actuators: {um.active_groups} ({g['kind']}, delay {g['min_delay']} .. {g['max_delay']} physics steps), row of "
               f"{sim.F} floats, stiffness {g['stiffness'][0]:g}, |history| mean {float(sim.view('act_hist')[:, :12].abs().mean()):.4f}")
+    if a.randomize:
+        em, sim = env_u.event_manager, env_u.sim
+        print(f"randomisation: {em.active_terms}, row of {sim.F} floats, flags {int(sim.randomize_words.view('int32')[0]):#x}")
     if a.eval or a.trace:
         steps = record[:, 0].cpu()
         assert float(steps.min()) == float(steps.max()) == a.rollouts * trainer.T, (float(steps.min()), float(steps.max()))
