@@ -315,6 +315,24 @@ class ServoSimRandomize(ServoSimActuators):
     _fields_ = [("rnd", ServoRandomize)]
 
 
+SERVO_EXT_HISTORY = 0x48535431          # CATPPO_SERVO_EXT_HISTORY: ``reserved`` of a descriptor followed by all seven and the history
+SERVO_OBS_HISTORY_MAX_FLOATS = 512      # CATPPO_SERVO_OBS_HISTORY_MAX_FLOATS: the width T of the row's policy_obs_hist field
+SERVO_OBS_HISTORY_MAX_DEPTH = 16        # CATPPO_SERVO_OBS_HISTORY_MAX_DEPTH: frames a term keeps at most
+SERVO_HISTORY_NEWEST = 0x10000          # CATPPO_SERVO_HISTORY_NEWEST: a map word = cur | w << 8 | newest << 16
+
+
+class ServoHistory(C.Structure):
+    """catppo_servo_history: the history descriptor; ``map`` is a device array of ``floats`` 32-bit words, ``off_hist`` the
+    row's ``policy_obs_hist`` field behind ``row_floats``"""
+    _fields_ = [("map", C.c_void_p), ("off_hist", C.c_int32), ("floats", C.c_int32)]
+
+
+class ServoSimHistory(ServoSimRandomize):
+    """catppo_servo_sim_history: a ``ServoSimRandomize`` (whose observation table and randomisation block are never NULL
+    here) and a ``ServoHistory`` behind it; the library reads all eight while ``reserved`` is ``SERVO_EXT_HISTORY``"""
+    _fields_ = [("hist", ServoHistory)]
+
+
 F32, F16, F64 = 0, 1, 2                 # CATPPO_F32 / _F16 / _F64
 SUM, MAX = 0, 1                         # CATPPO_SUM / _MAX
 LR_FIXED, LR_LINEAR, LR_KEEP = 0, 1, 2
@@ -931,6 +949,8 @@ class Native:
             raise TypeError("servo_sim_step: a descriptor whose 'reserved' announces actuators must be a native.ServoSimActuators")
         if desc.reserved == SERVO_EXT_RANDOMIZE and not isinstance(desc, ServoSimRandomize):   # ... and a catppo_servo_randomize
             raise TypeError("servo_sim_step: a descriptor whose 'reserved' announces randomisation must be a native.ServoSimRandomize")
+        if desc.reserved == SERVO_EXT_HISTORY and not isinstance(desc, ServoSimHistory):   # ... and a catppo_servo_history
+            raise TypeError("servo_sim_step: a descriptor whose 'reserved' announces history must be a native.ServoSimHistory")
         rc = self.lib.catppo_servo_sim_step(self.h, C.byref(desc), self._stream())
         if rc:
             self._ok(rc)

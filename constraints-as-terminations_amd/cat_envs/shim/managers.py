@@ -42,6 +42,8 @@ except Exception:
         noise: Any = None
         clip: Any = None              # (lo, hi) or None
         scale: Any = None             # a number, one per element, or None
+        history_length: int = 0       # frames the term keeps, oldest first; 0 and 1: the current frame only
+        flatten_history_dim: bool = True
 
     @configclass
     class EventTermCfg(ManagerTermBaseCfg):
@@ -90,6 +92,8 @@ except Exception:
         """IsaacLab's ObsGroup: its ObsTerm attributes in definition order are the group's terms"""
         concatenate_terms: bool = True
         enable_corruption: bool = False
+        history_length: Any = None    # an int overrides history_length and flatten_history_dim of every term
+        flatten_history_dim: bool = True
 
     @configclass
     class AdditiveUniformNoiseCfg:

@@ -167,3 +167,19 @@ for _name, _cfg in (("Randomized", "Solo12ServoRandomizedFlatEnvCfg"), ("Referen
         disable_env_checker=True,
         kwargs={"env_cfg_entry_point": f"{__name__}.cat_flat_env_cfg:{_cfg}_PLAY", **_KW},
     )
+
+# the servo task with an observation history: the last three frames of every term, kept in the simulator's row by its own
+# launch ("History"); "Reference-History" is "Reference-Randomized" behind an actuator delay with that group
+for _name, _cfg in (("History", "Solo12ServoHistoryFlatEnvCfg"), ("Reference-History", "Solo12ServoReferenceHistoryFlatEnvCfg")):
+    register(
+        id=f"Isaac-Velocity-CaT-Flat-Solo12-Servo-{_name}-v0",
+        entry_point=CaTEnv,
+        disable_env_checker=True,
+        kwargs={"env_cfg_entry_point": f"{__name__}.cat_flat_env_cfg:{_cfg}", **_KW},
+    )
+    register(
+        id=f"Isaac-Velocity-CaT-Flat-Solo12-Servo-{_name}-Play-v0",
+        entry_point=CaTEnv,
+        disable_env_checker=True,
+        kwargs={"env_cfg_entry_point": f"{__name__}.cat_flat_env_cfg:{_cfg}_PLAY", **_KW},
+    )

@@ -570,6 +570,47 @@ class Solo12ServoReferenceRandomizedFlatEnvCfg_PLAY(Solo12ServoReferenceActuator
 
 
 @configclass
+class HistoryObservationsCfg:
+    """the reference's six terms, each with its last three processed frames, oldest first ("History"): 135 floats"""
+
+    @configclass
+    class PolicyCfg(ObservationsCfg.PolicyCfg):
+        history_length: int = 3
+
+    policy: PolicyCfg = PolicyCfg()
+
+
+@configclass
+class Solo12ServoHistoryFlatEnvCfg(Solo12ServoFlatEnvCfg):
+    """the servo task with an observation history: the simulator's launch keeps the last three frames of every term in its row"""
+    observations: HistoryObservationsCfg = HistoryObservationsCfg()
+
+
+@configclass
+class Solo12ServoHistoryFlatEnvCfg_PLAY(Solo12ServoHistoryFlatEnvCfg):
+    scene: SceneCfg = SceneCfg(num_envs=50, env_spacing=3.0)
+    curriculum: object = None
+
+    def __post_init__(self):
+        self.observations.policy.enable_corruption = False
+
+
+@configclass
+class Solo12ServoReferenceHistoryFlatEnvCfg(Solo12ServoReferenceRandomizedFlatEnvCfg):
+    """every MDP block of the reference's cfg, the reference's robot behind an actuator delay, the three randomisation terms,
+    and three frames of every observation term: what lets a policy tell the delayed, randomised robots apart"""
+    scene: SceneCfg = SceneCfg(num_envs=4096, env_spacing=3.0, robot=_delayed(SOLO12_MINIMAL_CFG, 0, 4))
+    observations: HistoryObservationsCfg = HistoryObservationsCfg()
+
+
+@configclass
+class Solo12ServoReferenceHistoryFlatEnvCfg_PLAY(Solo12ServoReferenceRandomizedFlatEnvCfg_PLAY):
+    """randomisation stays on, pushes and observation noise off (the inherited ``__post_init__``)"""
+    scene: SceneCfg = SceneCfg(num_envs=50, env_spacing=3.0, robot=_delayed(SOLO12_MINIMAL_CFG, 0, 4))
+    observations: HistoryObservationsCfg = HistoryObservationsCfg()
+
+
+@configclass
 class Solo12FlatEnvCfg_PLAY(Solo12FlatEnvCfg):
     scene: SceneCfg = SceneCfg(num_envs=50, env_spacing=3.0)
     curriculum: object = None

@@ -185,7 +185,7 @@ class Solo12ServoSim(SyntheticSolo12Sim):
     def __init__(self, num_envs: int, obs_dim: int, device, seed: int, syn, dt: float, decimation: int,
                  max_episode_length: int, episode_length: torch.Tensor, reset: torch.Tensor, env_offset: int = 0,
                  policy_obs_dim: int = 0, events: bool = False, commands: bool = False, terminations: bool = False,
-                 actions: bool = False, actuators: bool = False, randomize: bool = False):
+                 actions: bool = False, actuators: bool = False, randomize: bool = False, history_floats: int = 0):
         """``policy_obs_dim`` = P > 0: the row gets a second observation field ``policy_obs`` of P floats (padded to a
         multiple of 4) that ``set_observation_table`` configures; the raw field ``obs`` stays what it is.
         ``events``: the descriptor carries the event descriptor, too, and ``set_event_block`` configures it.
@@ -200,7 +200,17 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         actions), the descriptor carries the action and the actuator descriptors and ``set_actuator_table`` configures the
         latter (per-joint gains, inertia, effort limits, DC-motor clamps and the actuator delay).
         ``randomize``: the descriptor carries the actuator and the randomisation descriptors and ``set_randomize_block``
-        configures the latter (per-env gains, joint friction, armature and base mass); the row is that of ``actuators``"""
+        configures the latter (per-env gains, joint friction, armature and base mass); the row is that of ``actuators``.
+        ``history_floats`` = T > 0 (needs ``policy_obs_dim``): the row gets a second policy field ``policy_obs_hist`` of T
+        floats (padded to a multiple of 4) behind ``row_floats``, the part of the row the kernel stages in LDS, so ``F``, the
+        stride of the state buffers, exceeds ``row_floats``; the descriptor carries all eight descriptors and
+        ``set_history_table`` configures the last (which float of the field shows which float of the current frame, and how
+        far the next slot is).  The row is that of ``randomize``"""
+        self.T = int(history_floats)
+        if self.T and not (int(policy_obs_dim) and 1 <= self.T <= native.SERVO_OBS_HISTORY_MAX_FLOATS):
+            raise ValueError(f"an observation history needs a policy observation and 1 <= floats <= "
+                             f"{native.SERVO_OBS_HISTORY_MAX_FLOATS} (got policy_obs_dim {policy_obs_dim}, floats {self.T})")
+        randomize = bool(randomize or self.T)
         actuators = bool(actuators or randomize)
         actions = bool(actions or actuators)
         self.N, self.D, self.device = num_envs, obs_dim, torch.device(device)
@@ -231,6 +241,10 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         if actuators:
             self.off["act_hist"] = (self.F, native.SERVO_ACT_HIST_FLOATS)
             self.F += native.SERVO_ACT_HIST_FLOATS
+        self.row_floats = self.F                                        # what the kernel assembles in LDS
+        if self.T:                                                      # behind it, written straight to memory
+            self.off["policy_obs_hist"] = (self.F, self.T)
+            self.F += (self.T + 3) // 4 * 4
         self.cur = torch.zeros(num_envs, self.F, device=self.device)
         self._slabs = [torch.zeros(num_envs, self.F, device=self.device) for _ in range(2)]
         self.cursor = -1
@@ -238,10 +252,10 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         self._episode_length, self._reset = episode_length, reset       # referenced by the descriptor: keep alive
         self._nat = native.get(self.device)
         # with a policy observation the descriptor carries the observation descriptor behind its 368 bytes
-        d = self._desc = (native.ServoSimRandomize() if randomize else native.ServoSimActuators() if actuators else native.ServoSimActions() if actions else native.ServoSimTerminations() if terminations
+        d = self._desc = (native.ServoSimHistory() if self.T else native.ServoSimRandomize() if randomize else native.ServoSimActuators() if actuators else native.ServoSimActions() if actions else native.ServoSimTerminations() if terminations
                           else native.ServoSimCommands() if commands else native.ServoSimEvents() if events
                           else native.ServoSimObs() if self.P else native.ServoSimRewards())
-        d.N, d.env_offset, d.row_stride, d.row_floats = num_envs, int(env_offset), self.F, self.F
+        d.N, d.env_offset, d.row_stride, d.row_floats = num_envs, int(env_offset), self.F, self.row_floats
         d.obs_dim, d.H, d.B = obs_dim, H, B
         names = {"projected_gravity": "projected_gravity_b", "root_pos": "root_pos_w"}
         for n in native.SERVO_OFFSETS:
@@ -272,6 +286,7 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         self._actuator_table, self._actuator_entries = None, []         # device table of the actuator descriptor
         self._randomize = bool(randomize)
         self._randomize_block, self._randomize_words = None, None       # device block of the randomisation descriptor, its host copy
+        self._history_map, self._history_words = None, None             # device map of the history descriptor, its host copy
         self._build_scene()
 
     def _table(self, t, width, what, lead=()):
@@ -440,7 +455,8 @@ class Solo12ServoSim(SyntheticSolo12Sim):
 
     def _announce(self):
         """``reserved`` names the descriptors behind the 368 bytes that are configured by now"""
-        self._desc.reserved = (native.SERVO_EXT_RANDOMIZE if self._randomize_block is not None
+        self._desc.reserved = (native.SERVO_EXT_HISTORY if self._history_map is not None
+                               else native.SERVO_EXT_RANDOMIZE if self._randomize_block is not None
                                else native.SERVO_EXT_ACTUATORS if self._actuator_table is not None
                                else native.SERVO_EXT_ACTIONS if self._action_table is not None
                                else native.SERVO_EXT_TERMINATIONS if self._term_table is not None
@@ -678,6 +694,71 @@ class Solo12ServoSim(SyntheticSolo12Sim):
             self._randomize_block.copy_(torch.from_numpy(words.copy()))
         self._randomize_words = words.copy()
 
+    def neutral_randomize_words(self):
+        """the block that must change nothing: the switch off, no quantity, the simulator's own mass and servo inertia"""
+        import numpy as np
+        W = native.SERVO_RANDOMIZE_WORDS
+        words = np.zeros(native.SERVO_RANDOMIZE_FLOATS, np.float32)
+        words[W["m0"]] = np.float32(float(self._desc.weight) / 9.81)
+        words[W["g"]], words[W["servo_inertia"]] = np.float32(9.81), np.float32(self._desc.inertia)
+        return words
+
+    def set_history_table(self, words):
+        """``words``: the T words ``cur | w << 8 | newest << 16`` of the history map, one per float of the row's
+        ``policy_obs_hist`` field (``mdp.observation_manager.history_map``): ``cur`` the float of the current frame that the
+        float shows when it is new, ``w`` the frame width of its term (the float one slot later is ``w`` floats on), ``newest``
+        set in a term's last slot.  Every following launch, init launches included, writes the field: the first frame of an
+        episode fills every slot, any other step moves the input row's slots one back and puts the current frame last.  The
+        map lives on the device and is rewritten here and nowhere else, in stream order.  ``set_observation_table`` comes
+        first; a simulator without a robot gets the identity action and actuator tables and a switched-off randomisation
+        block here.  Every word is checked here - the library cannot read them (the kernel clamps ``cur`` and ``i + w``
+        anyway)."""
+        import numpy as np
+        if not self.T:
+            raise ValueError("this simulator was built without a history field (history_floats = 0)")
+        if self._obs_table is None:
+            raise ValueError("the history shows the policy observation's frames: set_observation_table comes first")
+        words = np.ascontiguousarray(words, np.uint32)
+        if words.shape != (self.T,):
+            raise ValueError(f"the history map has one word per float of the field ({self.T}), got shape {words.shape}")
+        cur, w, newest = words & 0xFF, (words >> 8) & 0xFF, (words >> 16) & 1
+        if (words >> 17).any():
+            raise ValueError("history map: the bits above 16 must be zero")
+        i = 0
+        while i < self.T:
+            # one term: H slots of w floats each, slot s float k shows cur0 + k; only the last slot is the newest
+            wi, c0 = int(w[i]), int(cur[i])
+            if not 1 <= wi <= self.P:
+                raise ValueError(f"history map: word {i} has frame width {wi}, the current frame has {self.P} floats")
+            j, slots = i, 0
+            while j < self.T and int(w[j]) == wi and int(cur[j]) == c0 and (slots == 0 or not newest[j - 1]):
+                blk = slice(j, j + wi)
+                ok = (j + wi <= self.T and (w[blk] == wi).all() and (cur[blk] == c0 + np.arange(wi)).all()
+                      and c0 + wi <= self.P and (newest[blk] == newest[j]).all())
+                if not ok:
+                    raise ValueError(f"history map: the {wi} words from {j} on are not one slot of a term "
+                                     f"(cur {c0} .. {c0 + wi - 1}, one width, one newest bit)")
+                j, slots = j + wi, slots + 1
+            if not newest[j - 1] or slots > native.SERVO_OBS_HISTORY_MAX_DEPTH:
+                raise ValueError(f"history map: the term from word {i} on has {slots} slots and "
+                                 f"{'no' if not newest[j - 1] else 'a'} newest one (at most "
+                                 f"{native.SERVO_OBS_HISTORY_MAX_DEPTH} slots, the last one the newest)")
+            i = j
+        if self._history_map is None:
+            if self._randomize_block is None:                           # the neutral block (byte-identical to none)
+                self.set_randomize_block(self.neutral_randomize_words())
+            self._history_map = torch.zeros((self.T + 3) // 4 * 4, dtype=torch.int32, device=self.device)
+            h = self._desc.hist
+            h.map, h.off_hist, h.floats = self._history_map.data_ptr(), self.off["policy_obs_hist"][0], self.T
+            self._announce()                                            # from now on every launch writes the field
+        self._history_map[:self.T].copy_(torch.from_numpy(words.view(np.int32).copy()))
+        self._history_words = words.copy()
+
+    @property
+    def history_words(self):
+        """the history map as last written (a host copy), or None"""
+        return None if self._history_words is None else self._history_words.copy()
+
     @property
     def randomize_words(self):
         """the randomisation block as last written (a host copy), or None"""
@@ -862,6 +943,11 @@ class CaTEnv:
                                              action_terms=None if self._action_table is None else
                                              {n: t["slice"] for n, t in self._action_table[1].items()})
             self._obs_field, self.obs_dim = "policy_obs", len(self._obs_table[0])
+            self._frame_dim = self.obs_dim
+            # history_length on a term or the group: the policy reads a second field of the row that the same launch shifts and
+            # fills ("History"); with every depth 1 nothing changes
+            if self._obs_table.has_history:
+                self._obs_field, self.obs_dim = "policy_obs_hist", self._obs_table.history_floats
         # cfg.events: pushes, reset ranges and traction are evaluated inside the simulator's launch, too (DESIGN section 9,
         # "Events"); the block is built before the simulator because an error in the cfg should cost no device memory
         self._event_block = None
@@ -937,7 +1023,8 @@ class CaTEnv:
             self.sim = Solo12ServoSim(self.num_envs, int(syn.obs_dim), self.device, seed + int(syn.seed_offset), syn,
                                       cfg.sim.dt, cfg.decimation, self.max_episode_length, self.episode_length_buf,
                                       self.reset_buf, env_offset=int(getattr(cfg.scene, "env_offset", 0) or 0),
-                                      policy_obs_dim=self.obs_dim if self._obs_table is not None else 0,
+                                      policy_obs_dim=self._frame_dim if self._obs_table is not None else 0,
+                                      history_floats=self.obs_dim if self._obs_field == "policy_obs_hist" else 0,
                                       events=self._event_pack, commands=self._command_block is not None,
                                       terminations=self._term_table is not None, actions=self._action_table is not None,
                                       actuators=self._actuator_table is not None, randomize=self._randomization is not None)
@@ -1007,7 +1094,8 @@ class CaTEnv:
             print("[INFO] Reward Manager: ", self.reward_manager)
         if self._obs_table is not None:
             from cat_envs.tasks.utils.mdp.observation_manager import ObservationManager
-            self.observation_manager = ObservationManager(self.cfg.observations, self, *self._obs_table)
+            self.observation_manager = ObservationManager(self.cfg.observations, self, *self._obs_table,
+                                                          depths=self._obs_table.depths)
             print("[INFO] Observation Manager: ", self.observation_manager)
         if self._event_block is not None:
             from cat_envs.tasks.utils.mdp.event_manager import EventManager

@@ -200,7 +200,9 @@ def export_policy(state_dict, directory: str, observation_spec=None, action_spec
                   randomization_spec=None) -> Dict[str, str]:
     """``<directory>/model.onnx`` + ``<directory>/model.pt`` (play.py:111-135).  ``observation_spec`` (a dict, see
     ``ObservationManager.spec``): also ``<directory>/observations.json``, the input contract of the deployed policy -
-    term names, slices, sources, scales, clips and the joint order of the vector the models take.  ``action_spec`` (a dict,
+    term names, slices, sources, scales, clips and the joint order of the vector the models take; with an observation history
+    (``history_length`` per term, ``frame_order``) the models take the whole ring and the file says that the deployer owns it:
+    the last ``history_length`` processed frames of every term, oldest first, the first frame of an episode in every slot.  ``action_spec`` (a dict,
     see ``ActionManager.spec``): also ``<directory>/actions.json``, the output contract - per column of the vector the models
     give: the action term, the joint it drives, the kind of target, scale, offset and clip.  ``actuator_spec`` (a dict, see
     ``ActuatorModel.spec``): ``actions.json`` gets the key ``"actuators"`` - per joint the gains and limits the policy was

@@ -5,6 +5,11 @@ concatenates.  This one calls none: it turns the policy group of an ``Observatio
 kernel evaluates in a post-pass of its own launch (``Solo12ServoSim.set_observation_table``); the policy observation is a
 field of the simulator's row, next to the raw one.  ``set_corruption`` rewrites the entries' noise bits on the device, in
 stream order: the next launch - a replayed graph's, too - reads them.
+
+History ("History"; PARITY UNPINNED: restated from IsaacLab's published ``ObservationManager`` and
+``CircularBuffer``): a term's ``history_length`` H keeps its last H processed frames, oldest first, in a second field of the
+row that the same launch shifts and fills; a group's ``history_length`` overrides every term's.  The table then comes with a
+map of one word per float of that field (``Solo12ServoSim.set_history_table``).
 """
 from __future__ import annotations
 
@@ -18,6 +23,9 @@ from cat_envs.shim import AdditiveUniformNoiseCfg, ObservationTermCfg
 from . import observations as O
 
 MAX_WIDTH = native.SERVO_OBS_MAX_WIDTH
+MAX_HISTORY_FLOATS, MAX_DEPTH = native.SERVO_OBS_HISTORY_MAX_FLOATS, native.SERVO_OBS_HISTORY_MAX_DEPTH
+NEWEST = native.SERVO_HISTORY_NEWEST
+SWITCHES = ("concatenate_terms", "enable_corruption", "history_length", "flatten_history_dim")
 BIAS, NOISE, CLIP = native.SERVO_OBS_BIAS, native.SERVO_OBS_NOISE, native.SERVO_OBS_CLIP
 ENTRY_FIELDS = ("src", "flags", "bias", "noise_lo", "noise_width", "clip_lo", "clip_hi", "scale")
 
@@ -31,18 +39,73 @@ def _switch(group_cfg, name, default) -> bool:
 
 
 def group_items(group_cfg):
-    """(name, ObsTerm) of a group cfg in definition order; the group's own switches and unset terms are left out"""
+    """(name, ObsTerm) of a group cfg in definition order; unset terms and the group's own switches are left out (the
+    switches are read by ``build_table``, history among them)"""
     items = group_cfg.items() if isinstance(group_cfg, dict) else group_cfg.__dict__.items()
-    return [(n, t) for n, t in items if t is not None and n not in ("concatenate_terms", "enable_corruption", "history_length",
-                                                                    "flatten_history_dim")]
+    return [(n, t) for n, t in items if t is not None and n not in SWITCHES]
+
+
+def _group_value(group_cfg, name, default):
+    return group_cfg.get(name, default) if isinstance(group_cfg, dict) else getattr(group_cfg, name, default)
+
+
+def term_depth(group_cfg, name, term) -> int:
+    """the effective depth H = max(history_length, 1) of a term; the group's ``history_length``, when it is not None, overrides
+    the term's ``history_length`` and ``flatten_history_dim``.  ``ValueError``s name the term"""
+    length, flatten = getattr(term, "history_length", 0), getattr(term, "flatten_history_dim", True)
+    group_length = _group_value(group_cfg, "history_length", None)
+    if group_length is not None:
+        length, flatten = group_length, _group_value(group_cfg, "flatten_history_dim", True)
+    if isinstance(length, bool) or not isinstance(length, int):
+        raise ValueError(f"observation term '{name}': history_length must be an int, got {length!r}")
+    if length < 0:
+        raise ValueError(f"observation term '{name}': history_length must be >= 0, got {length}")
+    depth = max(length, 1)
+    if depth > MAX_DEPTH:
+        raise ValueError(f"observation term '{name}': history_length {length} is above the {MAX_DEPTH} frames a term keeps")
+    if depth > 1 and not flatten:
+        raise ValueError(f"observation term '{name}': flatten_history_dim=False is not supported; the policy observation is "
+                         f"one flat field of the simulator's row")
+    return depth
+
+
+def history_map(widths, depths):
+    """one word per float of the history field, ``cur | w << 8 | newest << 16``: a term of frame width w and depth H owns
+    H * w consecutive floats, oldest frame first; ``cur`` is the float of the current frame a float shows when it is new"""
+    words, at = [], 0
+    for w, depth in zip(widths, depths):
+        for slot in range(depth):
+            words += [(at + k) | w << 8 | (NEWEST if slot == depth - 1 else 0) for k in range(w)]
+        at += w
+    return words
+
+
+class ObsTable(tuple):
+    """what ``build_table`` returns: the pair ``(entries, group_obs_term_dim)`` with the history beside it - ``depths``
+    ``{term name: H}``, ``widths`` ``{term name: frame width}`` and ``history`` the map's words (``history_map``)"""
+
+    def __new__(cls, entries, dims, depths, widths):
+        self = super().__new__(cls, (entries, dims))
+        self.depths, self.widths = dict(depths), dict(widths)
+        self.history = history_map(list(widths.values()), list(depths.values()))
+        return self
+
+    @property
+    def history_floats(self) -> int:
+        return len(self.history)
+
+    @property
+    def has_history(self) -> bool:
+        return any(h > 1 for h in self.depths.values())
 
 
 def build_table(group_cfg, joint_names, default_joint_pos=None, action_terms=None):
     """(entries, group_obs_term_dim) from an observation group cfg and the robot's joint names; pure, needs no device.
-    ``entries``: one ``(src, flags, bias, noise_lo, noise_width, clip_lo, clip_hi, scale)`` per float of the policy
-    observation, terms concatenated in cfg order, every float already rounded to fp32; the noise bit is set for every term
-    that has a noise cfg (the corruption switch masks it later).  ``group_obs_term_dim``: ``{term name: (width,)}`` in the
-    same order.  ``ValueError``s name the term.  ``action_terms`` (envs with ``cfg.actions``): ``{term: (first column, end)}``
+    ``entries``: one ``(src, flags, bias, noise_lo, noise_width, clip_lo, clip_hi, scale)`` per float of the current frame
+    of the policy observation, terms concatenated in cfg order, every float already rounded to fp32; the noise bit is set for every term
+    that has a noise cfg (the corruption switch masks it later).  ``group_obs_term_dim``: ``{term name: (H * width,)}`` in the
+    same order, H the term's depth (``term_depth``); the returned pair is an ``ObsTable`` that also carries the depths and the
+    history map.  ``ValueError``s name the term.  ``action_terms`` (envs with ``cfg.actions``): ``{term: (first column, end)}``
     of the action block - a ``last_action`` term then has the block's width, or with ``action_name`` that term's columns."""
     import types
     if default_joint_pos is None:
@@ -52,7 +115,7 @@ def build_table(group_cfg, joint_names, default_joint_pos=None, action_terms=Non
                          "concatenated field of the simulator's row")
     env = types.SimpleNamespace(scene={"robot": types.SimpleNamespace(joint_names=list(joint_names), body_names=[])},
                                 default_joint_pos=[float(v) for v in default_joint_pos], action_terms=action_terms)
-    entries, dims = [], {}
+    entries, dims, depths, widths, total = [], {}, {}, {}, 0
     for name, term in group_items(group_cfg):
         if not isinstance(term, ObservationTermCfg):
             raise TypeError(f"Configuration for observation term '{name}' is not ObservationTermCfg. Received: '{type(term)}'.")
@@ -66,6 +129,7 @@ def build_table(group_cfg, joint_names, default_joint_pos=None, action_terms=Non
         except KeyError as e:
             raise ValueError(f"observation term '{name}': {e.args[0]}") from e
         width = len(pairs)
+        depth = term_depth(group_cfg, name, term)
         scale = term.scale
         if scale is None:
             scales = [1.0] * width
@@ -99,14 +163,18 @@ def build_table(group_cfg, joint_names, default_joint_pos=None, action_terms=Non
                 raise ValueError(f"observation term '{name}': source index {src} outside the raw {O.RAW_WIDTH}-float observation")
             entries.append((int(src), flags | (BIAS if bias is not None else 0), _f32(0.0 if bias is None else bias),
                             noise_lo, noise_width, clip_lo, clip_hi, _f32(s)))
-        dims[name] = (width,)
+        dims[name], depths[name], widths[name] = (depth * width,), depth, width
+        total += depth * width
         if len(entries) > MAX_WIDTH:
             raise ValueError(f"observation term '{name}': the policy observation reaches {len(entries)} floats, the simulator "
                              f"evaluates at most {MAX_WIDTH}")
+        if total > MAX_HISTORY_FLOATS:
+            raise ValueError(f"observation term '{name}': with its history the policy observation reaches {total} floats, the "
+                             f"simulator's row keeps at most {MAX_HISTORY_FLOATS}")
     if not entries:
         raise ValueError("the observation group has no term: nothing to evaluate (leave cfg.observations unset for the "
                          "simulator's raw observation)")
-    return entries, dims
+    return ObsTable(entries, dims, depths, widths)
 
 
 def policy_group(observations_cfg):
@@ -125,37 +193,62 @@ def with_corruption(entries, on: bool):
     return list(entries) if on else [(e[0], e[1] & ~NOISE, *e[2:]) for e in entries]
 
 
-def observation_spec(dims, entries, joint_names):
+def observation_spec(dims, entries, joint_names, depths=None):
     """the input contract of a deployed policy: per term its slice of the policy observation, raw sources (named), bias,
-    scale, clip and noise range; JSON-serialisable"""
+    scale, clip and noise range; JSON-serialisable.  ``depths`` ``{term: H}``: a term's slice then holds its last H processed
+    frames, oldest first (``frame_slice``: the term's floats within one frame)"""
+    depths = {n: 1 for n in dims} if depths is None else depths
     raw = (["base_ang_vel_" + a for a in "xyz"] + ["projected_gravity_" + a for a in "xyz"]
            + ["command_" + a for a in ("vx", "vy", "wz")] + ["joint_pos_rel:" + j for j in joint_names]
            + ["joint_vel:" + j for j in joint_names] + ["last_action:" + j for j in joint_names])
-    terms, at = [], 0
-    for name, (w,) in dims.items():
+    terms, at, col = [], 0, 0
+    for name, (hw,) in dims.items():
+        w = hw // depths[name]
         rows = entries[at:at + w]
         e0 = rows[0]
-        terms.append({"name": name, "slice": [at, at + w], "src": [r[0] for r in rows], "src_names": [raw[r[0]] for r in rows],
+        terms.append({"name": name, "slice": [col, col + hw], "history_length": depths[name], "frame_slice": [at, at + w],
+                      "src": [r[0] for r in rows], "src_names": [raw[r[0]] for r in rows],
                       "bias": [r[2] if r[1] & BIAS else 0.0 for r in rows], "scale": [r[7] for r in rows],
                       "clip": [e0[5], e0[6]] if e0[1] & CLIP else None,
                       "noise": [e0[3], _f32(np.float32(e0[3]) + np.float32(e0[4]))] if e0[1] & NOISE else None})
-        at += w
-    return {"obs_dim": at, "order": "noise, clip, scale (IsaacLab ObservationManager)", "joint_order": list(joint_names),
+        at, col = at + w, col + hw
+    return {"obs_dim": col, "frame_dim": at, "frame_order": "oldest first",
+            "history": "a term's slice holds its last history_length processed frames (each with the noise it was drawn "
+                       "with), oldest first; the first frame of an episode fills every slot.  The deployer owns this ring: "
+                       "the exported model takes the obs_dim floats as they are",
+            "order": "noise, clip, scale (IsaacLab ObservationManager)", "joint_order": list(joint_names),
             "raw_observation": raw, "terms": terms}
 
 
 class ObservationManager:
-    def __init__(self, cfg: object, env, entries=None, dims=None):
+    def __init__(self, cfg: object, env, entries=None, dims=None, depths=None):
+        """``entries``, ``dims``, ``depths``: what ``build_table`` has returned for the policy group (``dims`` per term
+        ``(H * width,)``; ``depths`` None: every term at depth 1); without them the table is built here"""
         self.cfg, self._env = cfg, env
         group = policy_group(cfg)
         if entries is None:
-            entries, dims = build_table(group, env.scene["robot"].joint_names)
+            table = build_table(group, env.scene["robot"].joint_names)
+            (entries, dims), depths = table, table.depths
         self._entries, self._dims = list(entries), dict(dims)
+        self._depths = {n: 1 for n in self._dims} if depths is None else dict(depths)
+        self._widths = {n: hw // self._depths[n] for n, (hw,) in self._dims.items()}
         self._corruption = _switch(group, "enable_corruption", False)
         self._push()
+        # with every depth 1 no history descriptor is attached: the policy reads the current frame, as it always has
+        if self.has_history:
+            self._env.sim.set_history_table(history_map(list(self._widths.values()), list(self._depths.values())))
 
     def _push(self):
         self._env.sim.set_observation_table(with_corruption(self._entries, self._corruption))
+
+    @property
+    def has_history(self) -> bool:
+        return any(h > 1 for h in self._depths.values())
+
+    @property
+    def history_lengths(self) -> dict:
+        """``{term name: H}``, the effective depth of every term"""
+        return dict(self._depths)
 
     # ------------------------------------------------------------------ IsaacLab's names
     @property
@@ -164,7 +257,7 @@ class ObservationManager:
 
     @property
     def group_obs_dim(self) -> dict:
-        return {"policy": (len(self._entries),)}
+        return {"policy": (sum(hw for hw, in self._dims.values()),)}
 
     @property
     def group_obs_term_dim(self) -> dict:
@@ -180,7 +273,8 @@ class ObservationManager:
         return self._corruption
 
     def set_corruption(self, on: bool):
-        """noise on or off from the next launch on: one stream-ordered copy of the table; nothing already computed moves"""
+        """noise on or off from the next launch on: one stream-ordered copy of the table; nothing already computed moves -
+        the frames a history holds keep the noise they were drawn with"""
         on = bool(on)
         if on != self._corruption:
             self._corruption = on
@@ -188,32 +282,35 @@ class ObservationManager:
 
     def compute(self) -> dict:
         """launches nothing: the simulator's launch of this step has filled the field"""
-        return {"policy": self._env.sim.view("policy_obs")}
+        return {"policy": self._env.sim.view("policy_obs_hist" if self.has_history else "policy_obs")}
 
     def reset(self, env_ids=None):
         return {}
 
     def spec(self) -> dict:
-        return observation_spec(self._dims, self._entries, self._env.scene["robot"].joint_names)
+        return observation_spec(self._dims, self._entries, self._env.scene["robot"].joint_names, self._depths)
 
     def __str__(self) -> str:
-        msg = f"<ObservationManager> contains 1 group, {len(self._dims)} terms, {len(self._entries)} floats " \
-              f"(corruption {'on' if self._corruption else 'off'}).\n"
+        msg = f"<ObservationManager> contains 1 group, {len(self._dims)} terms, {self.group_obs_dim['policy'][0]} floats " \
+              f"({len(self._entries)} per frame; corruption {'on' if self._corruption else 'off'}).\n"
         at = 0
-        for name, (w,) in self._dims.items():
+        for name, w in self._widths.items():
             e = self._entries[at]
             noise = f"U({e[3]:g}, {e[3] + e[4]:g})" if e[1] & NOISE else "-"
             clip = f"[{e[5]:g}, {e[6]:g}]" if e[1] & CLIP else "-"
-            msg += f"  {at:2d}:{at + w:2d}  {name:<20s} noise {noise:<18s} clip {clip:<12s} scale {[x[7] for x in self._entries[at:at + w]]}\n"
+            msg += f"  {at:2d}:{at + w:2d}  {name:<20s} history {self._depths[name]:<2d} noise {noise:<18s} clip {clip:<12s} scale {[x[7] for x in self._entries[at:at + w]]}\n"
             at += w
         return msg
 
     # ------------------------------------------------------------------ run state
     def fingerprint(self) -> list:
-        """names and the whole table (noise bits as configured): what a loaded state's policy observation was made with"""
+        """names, the whole table (noise bits as configured) and every depth above 1: what a loaded state's policy
+        observation was made with (a term at depth 1 keeps the entry it had before there was a history)"""
         out, at = [], 0
-        for name, (w,) in self._dims.items():
+        for name, w in self._widths.items():
             out.append([name, [[int(e[0]), int(e[1]), *(float(v) for v in e[2:])] for e in self._entries[at:at + w]]])
+            if self._depths[name] > 1:
+                out[-1].append(int(self._depths[name]))
             at += w
         return out
 

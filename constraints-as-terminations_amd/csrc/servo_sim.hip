@@ -10,7 +10,8 @@
 //   tree16: x += xor-shuffle 8, 4, 2, 1 (width 16)     tree4 (feet): x += xor-shuffle 1, 2
 // The kernel template is servo_sim_kernel.h; this unit holds the entry point and the instances of the packs without an action
 // table, servo_sim_actions.hip those with one, servo_sim_actuators.hip those with an actuator table behind it,
-// servo_sim_randomize.hip those with a randomisation block behind that.
+// servo_sim_randomize.hip those with a randomisation block behind that, servo_sim_history.hip those with a history
+// descriptor behind that.
 #include "servo_sim_kernel.h"
 
 // the descriptor's size is part of the ABI: cat_envs/native.py (ServoSimRewards) and tests/test_servo_reward_twin.py pin it
@@ -46,6 +47,11 @@ static_assert(offsetof(catppo_servo_sim_randomize, actu) == 456 && offsetof(catp
                   sizeof(catppo_servo_randomize) == 16 && offsetof(catppo_servo_randomize, reserved) == 8 &&
                   sizeof(catppo_servo_sim_randomize) == 488 && CATPPO_SERVO_RANDOMIZE_FLOATS == 32,
               "catppo_servo_sim_randomize: the randomisation descriptor behind the actuator descriptor");
+static_assert(offsetof(catppo_servo_sim_history, rnd) == 472 && offsetof(catppo_servo_sim_history, hist) == 488 &&
+                  sizeof(catppo_servo_history) == 16 && offsetof(catppo_servo_history, off_hist) == 8 &&
+                  offsetof(catppo_servo_history, floats) == 12 && sizeof(catppo_servo_sim_history) == 504 &&
+                  CATPPO_SERVO_OBS_HISTORY_MAX_FLOATS == 512 && CATPPO_SERVO_OBS_HISTORY_MAX_DEPTH == 16,
+              "catppo_servo_sim_history: the history descriptor behind the randomisation descriptor");
 
 extern "C" int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* desc, void* stream) {
   CATPPO_CHECK_ARG(ctx, ctx != nullptr);
@@ -58,7 +64,9 @@ extern "C" int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* de
   // ... or all five of a catppo_servo_sim_actions (whose termination descriptor may be empty, too)
   // ... or all six of a catppo_servo_sim_actuators (whose action descriptor is never empty)
   // ... or all seven of a catppo_servo_sim_randomize (whose actuator descriptor is never empty)
-  const bool ext_rnd = d.reserved == CATPPO_SERVO_EXT_RANDOMIZE;
+  // ... or all eight of a catppo_servo_sim_history (whose observation and randomisation descriptors are never empty)
+  const bool ext_hist = d.reserved == CATPPO_SERVO_EXT_HISTORY;
+  const bool ext_rnd = d.reserved == CATPPO_SERVO_EXT_RANDOMIZE || ext_hist;
   const bool ext_actu = d.reserved == CATPPO_SERVO_EXT_ACTUATORS || ext_rnd;
   const bool ext_act = d.reserved == CATPPO_SERVO_EXT_ACTIONS || ext_actu;
   const bool ext_term = d.reserved == CATPPO_SERVO_EXT_TERMINATIONS || ext_act;
@@ -77,6 +85,7 @@ extern "C" int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* de
   if (ac && tm->table == nullptr && tm->terms == 0) tm = nullptr;
   const catppo_servo_actuators* au = ext_actu ? &reinterpret_cast<const catppo_servo_sim_actuators*>(desc)->actu : nullptr;
   const catppo_servo_randomize* rn = ext_rnd ? &reinterpret_cast<const catppo_servo_sim_randomize*>(desc)->rnd : nullptr;
+  const catppo_servo_history* hs = ext_hist ? &reinterpret_cast<const catppo_servo_sim_history*>(desc)->hist : nullptr;
   CATPPO_CHECK_ARG(ctx, d.N >= 1 && d.N < (int64_t(1) << 31) && d.env_offset >= 0 && d.env_offset + d.N < (int64_t(1) << 32));
   CATPPO_CHECK_ARG(ctx, d.state_in && d.state_out && d.episode_length);
   CATPPO_CHECK_ARG(ctx, d.init || (d.action && d.reset && d.state_in != d.state_out));
@@ -246,12 +255,47 @@ extern "C" int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* de
         {tm ? (uintptr_t)tm->rec : 0, (uintptr_t)d.N * CATPPO_SERVO_TERM_FLOATS * sizeof(float)}};
     for (const auto& sp : span) CATPPO_CHECK_ARG(ctx, sp[0] == 0 || b1 <= sp[0] || sp[0] + sp[1] <= b0);
   }
+  if (hs) {
+    CATPPO_CHECK_ARG(ctx, obs != nullptr);
+    CATPPO_CHECK_ARG(ctx, hs->floats >= 1 && hs->floats <= CATPPO_SERVO_OBS_HISTORY_MAX_FLOATS);
+    // the field: pad4(T) floats of the row on a 16-byte boundary, behind the part that is staged in LDS, inside the stride
+    const int64_t ho = hs->off_hist, padded = ((int64_t)hs->floats + 3) / 4 * 4;
+    CATPPO_CHECK_ARG(ctx, ho % 4 == 0 && ho >= d.row_floats && ho + padded <= d.row_stride);
+    // the words are device memory: their writer checks them (Solo12ServoSim.set_history_table); whatever they hold the
+    // launch stays inside its row (cur and i + w are clamped in the kernel)
+    const void* mp = hs->map;
+    CATPPO_CHECK_ARG(ctx, mp != nullptr && ((uintptr_t)mp % 16) == 0);
+    const void* others[] = {d.state_in, d.state_out, d.eval, d.trace, d.fixed_command, d.reward_rec, (const void*)d.reward_table,
+                            d.action, d.reset, d.episode_length, (const void*)obs->table, tm ? (const void*)tm->table : nullptr};
+    for (const void* o : others) CATPPO_CHECK_ARG(ctx, mp != o);
+    // the map's T words overlap no slab, block, table or record
+    const uintptr_t m0 = (uintptr_t)mp, m1 = m0 + sizeof(uint32_t) * (uintptr_t)hs->floats;
+    const uintptr_t slab = (uintptr_t)d.N * (uintptr_t)d.row_stride * sizeof(float);
+    const uintptr_t span[][2] = {
+        {(uintptr_t)d.state_in, slab},
+        {(uintptr_t)d.state_out, slab},
+        {(uintptr_t)obs->table, sizeof(catppo_servo_obs_entry) * (uintptr_t)obs->width},
+        {(uintptr_t)rn->block, sizeof(float) * CATPPO_SERVO_RANDOMIZE_FLOATS},
+        {(uintptr_t)au->table, sizeof(catppo_servo_actuator_entry) * kJoints},
+        {(uintptr_t)ac->table, sizeof(catppo_servo_action_entry) * kJoints},
+        {d.reward_terms > 0 ? (uintptr_t)d.reward_table : 0, sizeof(catppo_servo_reward_term) * CATPPO_SERVO_REWARD_MAX_TERMS},
+        {d.reward_terms > 0 ? (uintptr_t)d.reward_rec : 0, (uintptr_t)d.N * CATPPO_SERVO_REWARD_FLOATS * sizeof(float)},
+        {ev ? (uintptr_t)ev->block : 0, sizeof(float) * CATPPO_SERVO_EVENT_FLOATS},
+        {cm ? (uintptr_t)cm->block : 0, sizeof(float) * CATPPO_SERVO_COMMAND_FLOATS},
+        {tm ? (uintptr_t)tm->table : 0, sizeof(catppo_servo_term_entry) * CATPPO_SERVO_TERM_MAX_TERMS},
+        {tm ? (uintptr_t)tm->rec : 0, (uintptr_t)d.N * CATPPO_SERVO_TERM_FLOATS * sizeof(float)},
+        {(uintptr_t)d.eval, (uintptr_t)d.N * CATPPO_SERVO_EVAL_FLOATS * sizeof(float)},
+        {(uintptr_t)d.trace, (uintptr_t)d.trace_capacity * (uintptr_t)d.trace_envs * CATPPO_SERVO_TRACE_FLOATS * sizeof(float)},
+        {(uintptr_t)d.fixed_command, (uintptr_t)(d.fixed_segments > 1 ? d.fixed_segments : 1) * (uintptr_t)d.N * 3 * sizeof(float)}};
+    for (const auto& sp : span) CATPPO_CHECK_ARG(ctx, sp[0] == 0 || m1 <= sp[0] || sp[0] + sp[1] <= m0);
+  }
   const unsigned nblk = (unsigned)cdiv64(d.N, kEnvsPerBlock);
   const size_t lds_bytes = (size_t)d.row_floats * kEnvsPerBlock * sizeof(float);
   const int mode = (d.trace || d.fixed_segments > 1) ? kStepResponse : (d.fixed_command || d.eval) ? kEvaluate : kTrain;
   const bool rew = d.reward_terms > 0;
   const hipStream_t st = static_cast<hipStream_t>(stream);
-  if (rn) catppo_internal_servo_sim_launch_randomize(mode, rew, nblk, lds_bytes, st, d, obs, ev, cm, tm, *ac, *au, *rn);
+  if (hs) catppo_internal_servo_sim_launch_history(mode, rew, nblk, lds_bytes, st, d, *obs, ev, cm, tm, *ac, *au, *rn, *hs);
+  else if (rn) catppo_internal_servo_sim_launch_randomize(mode, rew, nblk, lds_bytes, st, d, obs, ev, cm, tm, *ac, *au, *rn);
   else if (au) catppo_internal_servo_sim_launch_actuators(mode, rew, nblk, lds_bytes, st, d, obs, ev, cm, tm, *ac, *au);
   else if (ac) catppo_internal_servo_sim_launch_actions(mode, rew, nblk, lds_bytes, st, d, obs, ev, cm, tm, *ac);
   else if (tm && cm && obs && ev) launch(mode, rew, nblk, lds_bytes, st, d, *obs, *ev, *cm, *tm);

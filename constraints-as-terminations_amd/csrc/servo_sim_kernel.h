@@ -1,7 +1,8 @@
 // The servo simulator's kernel template, its helpers and launch(): included by servo_sim.hip (the packs without an action
 // table, and the entry point), by servo_sim_actions.hip (the packs with one) and by servo_sim_actuators.hip (the packs with
-// an actuator table behind it) and by servo_sim_randomize.hip (the packs with a randomisation block behind that), so that the
-// four sets of instances compile side by side.  Everything here has internal linkage.
+// an actuator table behind it) and by servo_sim_randomize.hip (the packs with a randomisation block behind that) and by
+// servo_sim_history.hip (the packs with a history descriptor behind that), so that the five sets of instances compile side by
+// side.  Everything here has internal linkage.
 #pragma once
 #include <type_traits>
 
@@ -432,6 +433,11 @@ __device__ __forceinline__ void randomize(const catppo_servo_sim& d, const ActuR
 // env's own gains, joint inertia, joint friction, foot load and velocity-lag gain, re-derived in every step from stateless
 // draws, stand where the actuator entry's and the descriptor's stand.  Orthogonal to the rest, compiled out without it: 64
 // more instances (16 packs, evaluation folded as above), compiled in servo_sim_randomize.hip.
+// catppo_servo_history, last in the pack and only behind catppo_servo_randomize and with catppo_servo_obs (DESIGN section 9,
+// "History"): after the observation post-pass the env's 16 lanes write the row's second policy field, T floats outside the
+// LDS-staged part of the row: per float the current frame's (the first frame of an episode fills every slot) or the input
+// row's float one slot later.  Selects and copies, no arithmetic.  Orthogonal to the rest, compiled out without it: 32 more
+// instances (8 packs, evaluation folded as above), compiled in servo_sim_history.hip.
 template <int kMode, bool kRew, typename... Ext>
 __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeof...(Ext) == 0) ? 8 : 1) void servo_sim_kernel(
     const catppo_servo_sim d, const Ext... ext) {
@@ -444,6 +450,8 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
   static_assert(kAct || !kActu, "the actuator descriptor comes only behind the action descriptor");
   constexpr bool kRnd = (std::is_same_v<Ext, catppo_servo_randomize> || ...);
   static_assert(kActu || !kRnd, "the randomisation descriptor comes only behind the actuator descriptor");
+  constexpr bool kHist = (std::is_same_v<Ext, catppo_servo_history> || ...);
+  static_assert((kRnd && kObs) || !kHist, "the history descriptor comes only behind the randomisation descriptor, with observations");
   constexpr bool kEval = kMode != kTrain;
   RndRegs<kRnd> RR;                      // declared first: further down it reorders register initialisations of older instances
   ActuRegs<kActu> UR;                    // likewise
@@ -535,6 +543,8 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
   float* obs = row + d.off_obs;
   // (episode, episode length) of the state the observation describes: the key of its noise
   uint32_t obs_ep = 0u, obs_t = 0u;
+  // history: the frame the post-pass produces is the first of an episode and fills every slot
+  bool hist_fill = init;
   // evaluation record: lane k < 12 of a live lane group owns field k of its env (one 48-byte access per env); the spare
   // groups past N, which recompute env N - 1, neither read nor write it
   const bool rec = kEval && d.eval != nullptr && e0 + grp < d.N && isj;
@@ -810,6 +820,7 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
     const bool ends = t + 1 >= d.max_episode_length || gone_of(TR, fallen);
     const uint32_t ep_out = ep + (ends ? 1u : 0u);
     if constexpr (kObs) obs_ep = ep_out, obs_t = ends ? 0u : (uint32_t)(t + 1);
+    if constexpr (kHist) hist_fill = ends;
     // ---- reward terms: value_k = (raw_k * weight_k) * step_dt in table order, summed from 0.f; lane k keeps value_k
     float rsum = 0.f, mine = 0.f;
     if constexpr (kRew) {
@@ -1042,6 +1053,32 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
     __syncthreads();
   }
 
+  // ---- observation history: float i of the field is the current frame's float cur(i) when the frame fills every slot or i
+  // lies in its term's newest slot, else the input row's float one slot later; registers to memory, neighbouring lanes write
+  // neighbouring floats, the spare lane groups past N write nothing.  cur and i + w are clamped: the launch stays in its row
+  if constexpr (kHist) {
+    const catppo_servo_history& hs = ext_of<catppo_servo_history>(ext...);
+    const catppo_servo_obs& o = ext_of<catppo_servo_obs>(ext...);
+    if (e0 + grp < d.N) {
+      const float* hin = in + hs.off_hist;
+      const float* frame = row + o.off_policy_obs;
+      float* hout = d.state_out + e * d.row_stride + hs.off_hist;
+      const int T = hs.floats, T4 = (T + 3) / 4 * 4;
+      for (int i = lane; i < T4; i += 16) {
+        float v = 0.f;                                   // the floats past T of the padded field
+        if (i < T) {
+          const uint32_t m = hs.map[i];
+          int c = (int)(m & 0xFFu), nx = i + (int)((m >> 8) & 0xFFu);
+          c = c < o.width ? c : o.width - 1;
+          nx = nx < T ? nx : T - 1;
+          if (hist_fill || (m & CATPPO_SERVO_HISTORY_NEWEST)) v = frame[c];
+          else v = hin[nx];
+        }
+        hout[i] = v;
+      }
+    }
+  }
+
   const int F4 = F >> 2;
   const int64_t stride4 = d.row_stride >> 2;
   float4* out4 = reinterpret_cast<float4*>(d.state_out);
@@ -1059,7 +1096,8 @@ void launch(int mode, bool rew, unsigned nblk, size_t lds_bytes, hipStream_t str
   // command table through two wave-uniform branches and compute the same bits): a third fewer instances to compile
   // (packs with an action table likewise)
   constexpr int kEvalAs = ((std::is_same_v<Ext, catppo_servo_terminations> || std::is_same_v<Ext, catppo_servo_actions> ||
-                            std::is_same_v<Ext, catppo_servo_actuators> || std::is_same_v<Ext, catppo_servo_randomize>) || ...)
+                            std::is_same_v<Ext, catppo_servo_actuators> || std::is_same_v<Ext, catppo_servo_randomize> ||
+                            std::is_same_v<Ext, catppo_servo_history>) || ...)
                               ? kStepResponse : kEvaluate;
   const Kernel table[3][2] = {{servo_sim_kernel<kTrain, false, Ext...>, servo_sim_kernel<kTrain, true, Ext...>},
                               {servo_sim_kernel<kEvalAs, false, Ext...>, servo_sim_kernel<kEvalAs, true, Ext...>},
@@ -1089,3 +1127,12 @@ void catppo_internal_servo_sim_launch_randomize(int mode, bool rew, unsigned nbl
                                                 const catppo_servo_events* ev, const catppo_servo_commands* cm,
                                                 const catppo_servo_terminations* tm, const catppo_servo_actions& act,
                                                 const catppo_servo_actuators& actu, const catppo_servo_randomize& rnd);
+
+// servo_sim_history.hip: the launch of a pack that holds the observation descriptor and ends with the action, actuator,
+// randomisation and history descriptors
+void catppo_internal_servo_sim_launch_history(int mode, bool rew, unsigned nblk, size_t lds_bytes, hipStream_t stream,
+                                              const catppo_servo_sim& d, const catppo_servo_obs& obs,
+                                              const catppo_servo_events* ev, const catppo_servo_commands* cm,
+                                              const catppo_servo_terminations* tm, const catppo_servo_actions& act,
+                                              const catppo_servo_actuators& actu, const catppo_servo_randomize& rnd,
+                                              const catppo_servo_history& hist);

@@ -729,7 +729,7 @@ typedef struct catppo_servo_sim {
   const uint8_t* reset;                  /* [N] */
   const int64_t* episode_length;         /* [N], before this step's increment */
   int64_t max_episode_length;
-  int32_t decimation, resample_steps, init, reserved;   /* reserved: 0 or one of CATPPO_SERVO_EXT_OBS / _EVENTS / _COMMANDS / _TERMINATIONS / _ACTIONS / _ACTUATORS / _RANDOMIZE (see below) */
+  int32_t decimation, resample_steps, init, reserved;   /* reserved: 0 or one of CATPPO_SERVO_EXT_OBS / _EVENTS / _COMMANDS / _TERMINATIONS / _ACTIONS / _ACTUATORS / _RANDOMIZE / _HISTORY (see below) */
   uint64_t seed;
   float default_joint_pos[12];
   float dt, kp, kd, inertia, tau_max, action_scale, vel_alpha, tilt_beta, tilt_max, reward_scale, foot_clearance,
@@ -1104,6 +1104,48 @@ typedef struct catppo_servo_sim_randomize {
   catppo_servo_actuators actu;            /* table never NULL */
   catppo_servo_randomize rnd;
 } catppo_servo_sim_randomize;
+
+/* Observation history ("History").  PARITY UNPINNED: the rule restates IsaacLab's ObservationManager and
+ * CircularBuffer (history_length on a term or group) from their published form.  desc->reserved == CATPPO_SERVO_EXT_HISTORY:
+ * `desc` is the head of a catppo_servo_sim_history, i.e. the catppo_servo_sim_randomize above with a history descriptor
+ * behind it.  The seven descriptors before it are checked and used exactly as under CATPPO_SERVO_EXT_RANDOMIZE, except that
+ * the observation descriptor is never empty (a launch without a robot passes the identity action and actuator tables and a
+ * switched-off randomisation block).  Every older value of `reserved` keeps its meaning.
+ * The row gets a second policy field, policy_obs_hist: hist.floats = T floats (1 .. CATPPO_SERVO_OBS_HISTORY_MAX_FLOATS) at
+ * hist.off_hist, a multiple of 4 at or past sim.row_floats with off_hist + pad4(T) <= sim.row_stride: it lies outside the
+ * part of the row that is staged in LDS and leaves with registers-to-memory dword stores.  A term of frame width w and depth
+ * H owns H * w consecutive floats, oldest frame first, terms in table order; the current frame stays in obs.off_policy_obs.
+ * hist.map is a DEVICE array of T 32-bit words, 16-byte aligned, read by every launch (a word the host rewrites in stream
+ * order is in the next launch):  word i = cur | w << 8 | newest << 16
+ *   cur     0 .. obs.width - 1: the float of the current frame that float i shows when it is new
+ *   w       the frame width of float i's term: the float one slot later is float i + w
+ *   newest  1: float i lies in the last slot of its term
+ * After the observation post-pass, lane l of an env writes floats i = l, l + 16, ... < T of the output row:
+ *   out[off_hist + i] = (fill || newest) ? policy_obs[cur] : in[off_hist + i + w]
+ * fill: an init launch, or a step that ends its episode (policy_obs then shows the first state of the next one): the first
+ * frame of an episode fills every slot.  A step after a reset shifts like any other: its input row holds the filled history.
+ * The kernel clamps cur to 0 .. obs.width - 1 and i + w to < T: whatever the map holds the launch stays inside its row.  The
+ * floats between T and pad4(T) are written as zeros.  The map's writer checks every word (Solo12ServoSim.set_history_table). */
+#define CATPPO_SERVO_EXT_HISTORY 0x48535431        /* "HST1": value of catppo_servo_sim.reserved that announces catppo_servo_sim_history */
+#define CATPPO_SERVO_OBS_HISTORY_MAX_FLOATS 512
+#define CATPPO_SERVO_OBS_HISTORY_MAX_DEPTH 16
+#define CATPPO_SERVO_HISTORY_NEWEST 0x10000u
+typedef struct catppo_servo_history {
+  const uint32_t* map;                    /* DEVICE array [floats], 16-byte aligned */
+  int32_t off_hist;                       /* the row's policy_obs_hist field: in [row_floats, row_stride), a multiple of 4 */
+  int32_t floats;                         /* T */
+} catppo_servo_history;
+typedef struct catppo_servo_sim_history {
+  catppo_servo_sim sim;                   /* sim.reserved = CATPPO_SERVO_EXT_HISTORY */
+  catppo_servo_obs obs;                   /* never empty */
+  catppo_servo_events ev;                 /* block NULL and floats 0: no events */
+  catppo_servo_commands cmd;              /* block NULL and floats 0: no commands */
+  catppo_servo_terminations term;         /* table NULL and terms 0: no terminations */
+  catppo_servo_actions act;               /* table never NULL */
+  catppo_servo_actuators actu;            /* table never NULL */
+  catppo_servo_randomize rnd;             /* block never NULL */
+  catppo_servo_history hist;
+} catppo_servo_sim_history;
 
 /* ---- test hook (ABI 0.6) ------------------------------------------------------------------------------------------
  * buf != NULL ([2][M] int32, device): the head / loss kernel of every following catppo_ppo_minibatch_* call writes the clip

@@ -17,7 +17,8 @@ names the instance of the servo simulator's kernel a task's training step launch
 servo_sim_actuators.hip).
 The servo tasks are ``...-Solo12-Servo-v0`` and its ``-Rewards``, ``-Obs``, ``-Events``, ``-Full``, ``-Commands``, ``-Reference``,
 ``-Terminations``, ``-Reference-Terminations``, ``-Actions``, ``-Reference-Actions``, ``-Actuators``, ``-Reference-Actuators``,
-``-DelayedActuators``, ``-Randomized`` (servo_sim_randomize.hip) and ``-Reference-Randomized`` variants."""
+``-DelayedActuators``, ``-Randomized`` (servo_sim_randomize.hip), ``-Reference-Randomized``, ``-History`` (servo_sim_history.hip) and
+``-Reference-History`` variants."""
 import argparse
 import os
 import sys
@@ -84,12 +85,26 @@ def explain_task(task):
         pack += ([] if has["actions"] else ["catppo_servo_actions"]) + ["catppo_servo_actuators"]
     if rnd_terms:                                # ... and the randomisation descriptor behind an actuator descriptor, likewise
         pack += ["catppo_servo_randomize"]
+    # history_length above 1 on a term or the group: the history descriptor comes last, behind the identity tables if need be
+    history = None
+    if has["observations"]:
+        import cat_envs.tasks.utils.cat.cat_env as E
+        from cat_envs.tasks.utils.mdp import observation_manager as OM
+        table = OM.build_table(OM.policy_group(cfg.observations), E.SOLO12_JOINTS, E.DEFAULT_JOINT_POS)
+        history = table if table.has_history else None
+    if history is not None:
+        pack += [n for n in ("catppo_servo_actions", "catppo_servo_actuators", "catppo_servo_randomize") if n not in pack]
+        pack += ["catppo_servo_history"]
     row = 308 + (48 if has["observations"] else 0) + (4 if has["commands"] else 0) + (4 if has["terminations"] else 0)
-    row += 48 if robot is not None or rnd_terms else 0
+    row += 48 if robot is not None or rnd_terms or history is not None else 0
     has["scene.robot"] = robot is not None
     out = [f"== {task}: " + ", ".join(f"cfg.{k} {'set' if v else 'unset'}" for k, v in has.items()),
            f"servo_sim_kernel<kTrain, {'true' if has['rewards'] else 'false'}{''.join(', ' + n for n in pack)}>: row of {row} floats "
            f"(with the reference's 45-float policy observation), {row * 64} bytes of LDS per workgroup"]
+    if history is not None:
+        T = history.history_floats
+        out.append(f"observation history (servo_sim_history.hip): {T} floats behind the row (stride {row + (T + 3) // 4 * 4}), "
+                   f"outside LDS; depths " + ", ".join(f"'{n}' {h} x {history.widths[n]}" for n, h in history.depths.items()))
     if has["commands"]:
         from cat_envs.tasks.utils.mdp import command_manager as KM
         b = KM.build_block(cfg.commands, cfg.sim.dt, cfg.episode_length_s)

@@ -46,6 +46,11 @@ run listed.
 (Isaac-Velocity-CaT-Flat-Solo12-Servo-Reference-Randomized-v0), so that the simulator's launch is the randomisation-on training
 instance of the full pack.  profiles/servo_randomize_kernel_stats.csv: the parent's library without a robot and with
 --actuators reference, this library likewise and with --randomize, alternating in one session, every run listed.
+--history H runs the task with the reference's observation block at group ``history_length`` H
+(Isaac-Velocity-CaT-Flat-Solo12-Servo-History-v0 at H = 3), so that the simulator's launch is the history-on training instance
+(observations, identity action and actuator tables, a switched-off randomisation block, the history descriptor).
+profiles/servo_history_kernel_stats.csv: the parent's library and this library without a flag and with --randomize, and this
+library with --obs, --history 3 and --history 5, alternating in one session, every run listed.
 
 Per env step the trace shows servo_sim_kernel (the simulator), the two launches of catppo_rollout_pre, the one of
 catppo_rollout_post and the policy forward."""
@@ -77,8 +82,10 @@ def main():
                     help="... and the reference's robot, or its gains behind an actuator delay of 0 .. 4 physics steps")
     ap.add_argument("--randomize", action="store_true",
                     help="... and RandomizationEventCfg's three terms on top of the reference's robot (-Reference-Randomized)")
+    ap.add_argument("--history", type=int, default=0,
+                    help="the task with ObservationsCfg at group history_length H: the observation history inside the simulator launch")
     a = ap.parse_args()
-    if a.obs + a.rewards + a.events + a.commands + a.terminations + a.actions + a.reference_actions + (a.actuators is not None) + a.randomize > 1:
+    if a.obs + a.rewards + a.events + a.commands + a.terminations + a.actions + a.reference_actions + (a.actuators is not None) + a.randomize + (a.history > 0) > 1:
         ap.error("--obs, --rewards, --events, --commands, --terminations, --actions, --reference-actions and --actuators are "
                  "separate arms")
     import cat_envs.tasks  # noqa: F401
@@ -93,11 +100,14 @@ def main():
             "Isaac-Velocity-CaT-Flat-Solo12-Servo-Reference-Actions-v0" if a.reference_actions else
             "Isaac-Velocity-CaT-Flat-Solo12-Servo-Reference-Actuators-v0" if a.actuators else
             "Isaac-Velocity-CaT-Flat-Solo12-Servo-Reference-Randomized-v0" if a.randomize else
+            "Isaac-Velocity-CaT-Flat-Solo12-Servo-History-v0" if a.history else
             "Isaac-Velocity-CaT-Flat-Solo12-Servo-v0")
     env_cfg = load_cfg_from_registry(task, "env_cfg_entry_point")
     if a.rewards:
         from cat_envs.tasks.locomotion.velocity.config.solo12.cat_flat_env_cfg import ShapedRewardsCfg
         env_cfg.rewards = ShapedRewardsCfg()
+    if a.history:
+        env_cfg.observations.policy.history_length = a.history
     if a.events:
         push = env_cfg.events.push_robot
         push.params = {**push.params, "probability": 0.01}
@@ -163,6 +173,11 @@ def main():
     if a.randomize:
         em, sim = env_u.event_manager, env_u.sim
         print(f"randomisation: {em.active_terms}, row of {sim.F} floats, flags {int(sim.randomize_words.view('int32')[0]):#x}")
+    if a.history:
+        sim = env_u.sim
+        h = sim.view("policy_obs_hist")
+        print(f"history: {env_u.obs_dim} floats ({sim.P} per frame), row of {sim.row_floats} floats, stride {sim.F}, newest slot of "
+              f"base_ang_vel differs from the one before in {float((h[:, 3 * a.history - 3] != h[:, 3 * a.history - 6]).float().mean()):.3f} of the envs")
     if a.eval or a.trace:
         steps = record[:, 0].cpu()
         assert float(steps.min()) == float(steps.max()) == a.rollouts * trainer.T, (float(steps.min()), float(steps.max()))
