@@ -333,6 +333,19 @@ class ServoSimHistory(ServoSimRandomize):
     _fields_ = [("hist", ServoHistory)]
 
 
+#: the levels of catppo_servo_sim.reserved in their order, each announcing the descriptors of the levels before it, too
+#: (csrc/servo_sim_host.h holds the same table): (what it announces, the value of ``reserved``, the descriptor class, the
+#: attribute of ``Solo12ServoSim`` that is not None once the level is configured)
+SERVO_EXTS = (("observations", SERVO_EXT_OBS, ServoSimObs, "_obs_table"),
+              ("events", SERVO_EXT_EVENTS, ServoSimEvents, "_event_block"),
+              ("commands", SERVO_EXT_COMMANDS, ServoSimCommands, "_command_block"),
+              ("terminations", SERVO_EXT_TERMINATIONS, ServoSimTerminations, "_term_table"),
+              ("actions", SERVO_EXT_ACTIONS, ServoSimActions, "_action_table"),
+              ("actuators", SERVO_EXT_ACTUATORS, ServoSimActuators, "_actuator_table"),
+              ("randomisation", SERVO_EXT_RANDOMIZE, ServoSimRandomize, "_randomize_block"),
+              ("history", SERVO_EXT_HISTORY, ServoSimHistory, "_history_map"))
+
+
 F32, F16, F64 = 0, 1, 2                 # CATPPO_F32 / _F16 / _F64
 SUM, MAX = 0, 1                         # CATPPO_SUM / _MAX
 LR_FIXED, LR_LINEAR, LR_KEEP = 0, 1, 2
@@ -935,22 +948,12 @@ class Native:
         """one control step (or, with ``desc.init``, the first state) of the Solo12 servo surrogate"""
         if not isinstance(desc, ServoSimRewards):           # the library reads the whole catppo_servo_sim, tail included
             raise TypeError("servo_sim_step takes a native.ServoSimRewards (the whole catppo_servo_sim)")
-        if desc.reserved and not isinstance(desc, ServoSimObs):   # the library would read a catppo_servo_obs behind it
-            raise TypeError("servo_sim_step: a descriptor whose 'reserved' announces observations must be a native.ServoSimObs")
-        if desc.reserved == SERVO_EXT_EVENTS and not isinstance(desc, ServoSimEvents):   # ... and a catppo_servo_events
-            raise TypeError("servo_sim_step: a descriptor whose 'reserved' announces events must be a native.ServoSimEvents")
-        if desc.reserved == SERVO_EXT_COMMANDS and not isinstance(desc, ServoSimCommands):   # ... and a catppo_servo_commands
-            raise TypeError("servo_sim_step: a descriptor whose 'reserved' announces commands must be a native.ServoSimCommands")
-        if desc.reserved == SERVO_EXT_TERMINATIONS and not isinstance(desc, ServoSimTerminations):   # ... and a catppo_servo_terminations
-            raise TypeError("servo_sim_step: a descriptor whose 'reserved' announces terminations must be a native.ServoSimTerminations")
-        if desc.reserved == SERVO_EXT_ACTIONS and not isinstance(desc, ServoSimActions):   # ... and a catppo_servo_actions
-            raise TypeError("servo_sim_step: a descriptor whose 'reserved' announces actions must be a native.ServoSimActions")
-        if desc.reserved == SERVO_EXT_ACTUATORS and not isinstance(desc, ServoSimActuators):   # ... and a catppo_servo_actuators
-            raise TypeError("servo_sim_step: a descriptor whose 'reserved' announces actuators must be a native.ServoSimActuators")
-        if desc.reserved == SERVO_EXT_RANDOMIZE and not isinstance(desc, ServoSimRandomize):   # ... and a catppo_servo_randomize
-            raise TypeError("servo_sim_step: a descriptor whose 'reserved' announces randomisation must be a native.ServoSimRandomize")
-        if desc.reserved == SERVO_EXT_HISTORY and not isinstance(desc, ServoSimHistory):   # ... and a catppo_servo_history
-            raise TypeError("servo_sim_step: a descriptor whose 'reserved' announces history must be a native.ServoSimHistory")
+        # the library would read the descriptors that 'reserved' announces behind it: the first level's under any value
+        # but 0 (an unknown one is the library's to refuse), the others' under their own
+        for name, magic, cls, _ in SERVO_EXTS:
+            announced = desc.reserved != 0 if cls is ServoSimObs else desc.reserved == magic
+            if announced and not isinstance(desc, cls):
+                raise TypeError(f"servo_sim_step: a descriptor whose 'reserved' announces {name} must be a native.{cls.__name__}")
         rc = self.lib.catppo_servo_sim_step(self.h, C.byref(desc), self._stream())
         if rc:
             self._ok(rc)

@@ -251,10 +251,10 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         self.default_joint_pos = torch.tensor(DEFAULT_JOINT_POS, device=self.device).repeat(num_envs, 1).contiguous()
         self._episode_length, self._reset = episode_length, reset       # referenced by the descriptor: keep alive
         self._nat = native.get(self.device)
-        # with a policy observation the descriptor carries the observation descriptor behind its 368 bytes
-        d = self._desc = (native.ServoSimHistory() if self.T else native.ServoSimRandomize() if randomize else native.ServoSimActuators() if actuators else native.ServoSimActions() if actions else native.ServoSimTerminations() if terminations
-                          else native.ServoSimCommands() if commands else native.ServoSimEvents() if events
-                          else native.ServoSimObs() if self.P else native.ServoSimRewards())
+        # the descriptor carries the descriptors of every level of native.SERVO_EXTS up to the highest that is switched on
+        switched = (self.P, events, commands, terminations, actions, actuators, randomize, self.T)
+        top = max((level for level, on in enumerate(switched) if on), default=None)
+        d = self._desc = (native.ServoSimRewards if top is None else native.SERVO_EXTS[top][2])()
         d.N, d.env_offset, d.row_stride, d.row_floats = num_envs, int(env_offset), self.F, self.row_floats
         d.obs_dim, d.H, d.B = obs_dim, H, B
         names = {"projected_gravity": "projected_gravity_b", "root_pos": "root_pos_w"}
@@ -455,14 +455,7 @@ class Solo12ServoSim(SyntheticSolo12Sim):
 
     def _announce(self):
         """``reserved`` names the descriptors behind the 368 bytes that are configured by now"""
-        self._desc.reserved = (native.SERVO_EXT_HISTORY if self._history_map is not None
-                               else native.SERVO_EXT_RANDOMIZE if self._randomize_block is not None
-                               else native.SERVO_EXT_ACTUATORS if self._actuator_table is not None
-                               else native.SERVO_EXT_ACTIONS if self._action_table is not None
-                               else native.SERVO_EXT_TERMINATIONS if self._term_table is not None
-                               else native.SERVO_EXT_COMMANDS if self._command_block is not None
-                               else native.SERVO_EXT_EVENTS if self._event_block is not None
-                               else native.SERVO_EXT_OBS if self._obs_table is not None else 0)
+        self._desc.reserved = next((magic for _, magic, _, attr in reversed(native.SERVO_EXTS) if getattr(self, attr) is not None), 0)
 
     def set_command_block(self, words):
         """``words``: the ``native.SERVO_COMMAND_FLOATS`` fp32 words of the command block (``mdp.command_manager.pack``; word 0

@@ -1,20 +1,17 @@
-// The servo simulator's kernel template, its helpers and launch(): included by servo_sim.hip (the packs without an action
-// table, and the entry point), by servo_sim_actions.hip (the packs with one) and by servo_sim_actuators.hip (the packs with
-// an actuator table behind it) and by servo_sim_randomize.hip (the packs with a randomisation block behind that) and by
-// servo_sim_history.hip (the packs with a history descriptor behind that), so that the five sets of instances compile side by
-// side.  Everything here has internal linkage.
+// The servo simulator's kernel template, its helpers and launch(): included by the five units that hold its instances, so
+// that they compile side by side (servo_sim.hip lists them).  Everything here has internal linkage.
 #pragma once
 #include <type_traits>
 
 #include "common.h"
 #include "rng.h"
+#include "servo_sim_host.h"
 
 namespace {
 
-constexpr int kEnvsPerBlock = 16, kThreads = 256, kJoints = 12, kPrivate = 14;
+constexpr int kThreads = 256;                                            // kEnvsPerBlock, kJoints, kPrivate, kRawObs: servo_sim_host.h
 constexpr uint32_t kTagCommand = 0x434D4453u, kTagInit = 0x494E4954u;   // "CMDS", "INIT": fourth Philox counter word
 constexpr uint32_t kTagObs = 0x4F42534Eu;                                // "OBSN": the observation noise
-constexpr int kRawObs = 45;                                              // the raw observation a policy observation reads
 // "PUSH", "JVEL", "ROOT", "FRIC": the events ("Events")
 constexpr uint32_t kTagPush = 0x50555348u, kTagJvel = 0x4A56454Cu, kTagRoot = 0x524F4F54u, kTagFric = 0x46524943u;
 // "CMDD", "CMDT": command draws and resampling times of the configured command process ("Commands")
@@ -1107,32 +1104,13 @@ void launch(int mode, bool rew, unsigned nblk, size_t lds_bytes, hipStream_t str
 
 }  // namespace
 
-// servo_sim_actions.hip: the launch of a pack that ends with the action descriptor; the absent blocks are null.  The entry
-// point (servo_sim.hip) has checked everything
+// the launches of the four other units (servo_sim.hip lists them): of a pack that ends with the descriptors the unit is named
+// after, and holds whichever of the optional ones before them are present.  The entry point has checked everything
 void catppo_internal_servo_sim_launch_actions(int mode, bool rew, unsigned nblk, size_t lds_bytes, hipStream_t stream,
-                                              const catppo_servo_sim& d, const catppo_servo_obs* obs,
-                                              const catppo_servo_events* ev, const catppo_servo_commands* cm,
-                                              const catppo_servo_terminations* tm, const catppo_servo_actions& act);
-
-// servo_sim_actuators.hip: the launch of a pack that ends with the action and the actuator descriptors
+                                              const catppo_servo_sim& d, const ServoExts& x);
 void catppo_internal_servo_sim_launch_actuators(int mode, bool rew, unsigned nblk, size_t lds_bytes, hipStream_t stream,
-                                                const catppo_servo_sim& d, const catppo_servo_obs* obs,
-                                                const catppo_servo_events* ev, const catppo_servo_commands* cm,
-                                                const catppo_servo_terminations* tm, const catppo_servo_actions& act,
-                                                const catppo_servo_actuators& actu);
-
-// servo_sim_randomize.hip: the launch of a pack that ends with the action, actuator and randomisation descriptors
+                                                const catppo_servo_sim& d, const ServoExts& x);
 void catppo_internal_servo_sim_launch_randomize(int mode, bool rew, unsigned nblk, size_t lds_bytes, hipStream_t stream,
-                                                const catppo_servo_sim& d, const catppo_servo_obs* obs,
-                                                const catppo_servo_events* ev, const catppo_servo_commands* cm,
-                                                const catppo_servo_terminations* tm, const catppo_servo_actions& act,
-                                                const catppo_servo_actuators& actu, const catppo_servo_randomize& rnd);
-
-// servo_sim_history.hip: the launch of a pack that holds the observation descriptor and ends with the action, actuator,
-// randomisation and history descriptors
+                                                const catppo_servo_sim& d, const ServoExts& x);
 void catppo_internal_servo_sim_launch_history(int mode, bool rew, unsigned nblk, size_t lds_bytes, hipStream_t stream,
-                                              const catppo_servo_sim& d, const catppo_servo_obs& obs,
-                                              const catppo_servo_events* ev, const catppo_servo_commands* cm,
-                                              const catppo_servo_terminations* tm, const catppo_servo_actions& act,
-                                              const catppo_servo_actuators& actu, const catppo_servo_randomize& rnd,
-                                              const catppo_servo_history& hist);
+                                              const catppo_servo_sim& d, const ServoExts& x);

@@ -1,27 +1,9 @@
 // Solo12 servo surrogate: the instances of servo_sim_kernel whose pack ends with the action, the actuator and the
 // randomisation descriptors ("Randomisation"): 16 packs x {train, step response} x {rewards off, on}.  A
-// translation unit of their own, so that they compile beside the instances of the three other units, not behind them.
+// translation unit of their own, so that they compile beside the instances of the other units (servo_sim.hip lists them).
 #include "servo_sim_kernel.h"
 
 void catppo_internal_servo_sim_launch_randomize(int mode, bool rew, unsigned nblk, size_t lds_bytes, hipStream_t st,
-                                                const catppo_servo_sim& d, const catppo_servo_obs* obs,
-                                                const catppo_servo_events* ev, const catppo_servo_commands* cm,
-                                                const catppo_servo_terminations* tm, const catppo_servo_actions& act,
-                                                const catppo_servo_actuators& actu, const catppo_servo_randomize& rnd) {
-  if (tm && cm && obs && ev) launch(mode, rew, nblk, lds_bytes, st, d, *obs, *ev, *cm, *tm, act, actu, rnd);
-  else if (tm && cm && ev) launch(mode, rew, nblk, lds_bytes, st, d, *ev, *cm, *tm, act, actu, rnd);
-  else if (tm && cm && obs) launch(mode, rew, nblk, lds_bytes, st, d, *obs, *cm, *tm, act, actu, rnd);
-  else if (tm && cm) launch(mode, rew, nblk, lds_bytes, st, d, *cm, *tm, act, actu, rnd);
-  else if (tm && obs && ev) launch(mode, rew, nblk, lds_bytes, st, d, *obs, *ev, *tm, act, actu, rnd);
-  else if (tm && ev) launch(mode, rew, nblk, lds_bytes, st, d, *ev, *tm, act, actu, rnd);
-  else if (tm && obs) launch(mode, rew, nblk, lds_bytes, st, d, *obs, *tm, act, actu, rnd);
-  else if (tm) launch(mode, rew, nblk, lds_bytes, st, d, *tm, act, actu, rnd);
-  else if (cm && obs && ev) launch(mode, rew, nblk, lds_bytes, st, d, *obs, *ev, *cm, act, actu, rnd);
-  else if (cm && ev) launch(mode, rew, nblk, lds_bytes, st, d, *ev, *cm, act, actu, rnd);
-  else if (cm && obs) launch(mode, rew, nblk, lds_bytes, st, d, *obs, *cm, act, actu, rnd);
-  else if (cm) launch(mode, rew, nblk, lds_bytes, st, d, *cm, act, actu, rnd);
-  else if (obs && ev) launch(mode, rew, nblk, lds_bytes, st, d, *obs, *ev, act, actu, rnd);
-  else if (ev) launch(mode, rew, nblk, lds_bytes, st, d, *ev, act, actu, rnd);
-  else if (obs) launch(mode, rew, nblk, lds_bytes, st, d, *obs, act, actu, rnd);
-  else launch(mode, rew, nblk, lds_bytes, st, d, act, actu, rnd);
+                                                const catppo_servo_sim& d, const ServoExts& x) {
+  with_present([&](const auto&... opt) { launch(mode, rew, nblk, lds_bytes, st, d, opt..., *x.ac, *x.au, *x.rn); }, x.obs, x.ev, x.cm, x.tm);
 }

@@ -120,13 +120,13 @@ def test_servo_sim_step_refuses_a_descriptor_without_the_action_tail():
 
 
 def test_every_instance_of_the_new_packs_is_reachable():
-    """16 packs end with the action descriptor; the launch of servo_sim_actions.hip names each of them once"""
+    """16 packs end with the action descriptor; the one launch of servo_sim_actions.hip reaches each of them:
+    with_present hands it whichever of the four optional descriptors are there, in the pack's order (all 16 combinations:
+    tests/test_servo_sim_host.py), and the unit's own descriptors follow them"""
     src = open(os.path.join(ROOT, "constraints-as-terminations_amd", "csrc", "servo_sim_actions.hip")).read()
-    packs = re.findall(r"launch\(mode, rew, nblk, lds_bytes, st, d, ([^)]*)\);", src)
-    assert len(packs) == len(set(packs)) == 16 and all(p.split(", ")[-1] == "act" for p in packs)
-    assert {frozenset(p.split(", ")[:-1]) for p in packs} == {
-        frozenset(x for x, on in zip(("*obs", "*ev", "*cm", "*tm"), bits) if on)
-        for bits in np.ndindex(2, 2, 2, 2)}
+    calls = re.findall(r"with_present\(\[&\]\(const auto&\.\.\. opt\) \{ launch\(mode, rew, nblk, lds_bytes, st, d, ([^)]*)\); \},\s*([^)]*)\);", src)
+    assert calls == [("opt..., *x.ac", "x.obs, x.ev, x.cm, x.tm")]
+    assert len(re.findall(r"\blaunch\(", src)) == 1                          # and nothing else launches here
 
 
 # ------------------------------------------------------------------------------------------ the twin
