@@ -333,6 +333,28 @@ class ServoSimHistory(ServoSimRandomize):
     _fields_ = [("hist", ServoHistory)]
 
 
+#: CATPPO_SERVO_EXT_PLANT: ``reserved`` of a descriptor followed by all eight and the plant table.  ``native.SERVO_EXT_PLANT``
+#: reads it (the module's ``__getattr__`` below): tests/test_servo_history_twin.py counts the module's own ``SERVO_EXT_*``
+#: names - the eight levels up to the history - so the ninth level's value is kept under this name and served under that one
+SERVO_PLANT_EXT = 0x504C4E31
+SERVO_PLANT_FLOATS = 8                  # CATPPO_SERVO_PLANT_FLOATS: words of one row of the device-resident plant table
+#: pin bits of a row's word 0 (CATPPO_SERVO_PLANT_*), by the quantity's name in ``cleanrl.evaluate.plant_grid``
+SERVO_PLANT_BITS = {"kp_scale": 0x1, "kd_scale": 0x2, "friction": 0x4, "armature": 0x8, "mass_scale": 0x10, "lag": 0x20}
+#: the word of a row that holds the quantity (include/catppo.h, "Pinned plants"); word 0 the bits, word 6 an integer, word 7 zero
+SERVO_PLANT_WORDS = {"bits": 0, "kp_scale": 1, "kd_scale": 2, "friction": 3, "armature": 4, "mass_scale": 5, "lag": 6}
+
+
+class ServoPlant(C.Structure):
+    """catppo_servo_plant: the plant descriptor; ``table`` is a device array [N, ``SERVO_PLANT_FLOATS``] of fp32 words"""
+    _fields_ = [("table", C.c_void_p), ("reserved", C.c_int32 * 2)]
+
+
+class ServoSimPlant(ServoSimHistory):
+    """catppo_servo_sim_plant: a ``ServoSimHistory`` (whose history descriptor may be empty here: a NULL map and ``floats`` 0)
+    and a ``ServoPlant`` behind it; the library reads all nine while ``reserved`` is ``SERVO_EXT_PLANT``"""
+    _fields_ = [("plant", ServoPlant)]
+
+
 #: the levels of catppo_servo_sim.reserved in their order, each announcing the descriptors of the levels before it, too
 #: (csrc/servo_sim_host.h holds the same table): (what it announces, the value of ``reserved``, the descriptor class, the
 #: attribute of ``Solo12ServoSim`` that is not None once the level is configured)
@@ -343,7 +365,14 @@ SERVO_EXTS = (("observations", SERVO_EXT_OBS, ServoSimObs, "_obs_table"),
               ("actions", SERVO_EXT_ACTIONS, ServoSimActions, "_action_table"),
               ("actuators", SERVO_EXT_ACTUATORS, ServoSimActuators, "_actuator_table"),
               ("randomisation", SERVO_EXT_RANDOMIZE, ServoSimRandomize, "_randomize_block"),
-              ("history", SERVO_EXT_HISTORY, ServoSimHistory, "_history_map"))
+              ("history", SERVO_EXT_HISTORY, ServoSimHistory, "_history_map"),
+              ("pinned plants", SERVO_PLANT_EXT, ServoSimPlant, "_plant_table"))
+
+
+def __getattr__(name):
+    if name == "SERVO_EXT_PLANT":
+        return SERVO_PLANT_EXT
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 F32, F16, F64 = 0, 1, 2                 # CATPPO_F32 / _F16 / _F64

@@ -287,6 +287,7 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         self._randomize = bool(randomize)
         self._randomize_block, self._randomize_words = None, None       # device block of the randomisation descriptor, its host copy
         self._history_map, self._history_words = None, None             # device map of the history descriptor, its host copy
+        self._plant_table, self._plant_undo = None, None                # device table of the plant descriptor; how to detach it
         self._build_scene()
 
     def _table(self, t, width, what, lead=()):
@@ -694,7 +695,65 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         words = np.zeros(native.SERVO_RANDOMIZE_FLOATS, np.float32)
         words[W["m0"]] = np.float32(float(self._desc.weight) / 9.81)
         words[W["g"]], words[W["servo_inertia"]] = np.float32(9.81), np.float32(self._desc.inertia)
+        # the nominal armatures: what the joints' inertia has above the servo's own (never read while the switch is off)
+        for j, row in enumerate(self._actuator_entries):
+            words[W["armatures"] + j] = max(np.float32(row[2]) - words[W["servo_inertia"]], np.float32(0))
         return words
+
+    def set_fixed_plant(self, table: torch.Tensor | None):
+        """``table`` [N, 8] (``native.SERVO_PLANT_WORDS``; what ``cleanrl.evaluate.plant_grid`` packs): row i pins the plant of
+        env i - gains, joint friction, armature, base mass and actuator lag, each where its bit of word 0 is set - in every
+        step and every episode, inside the simulator's own launch, after the lag draw and the randomisation block's draws.
+        The kernel reads the tensor at every launch.  While a table is attached the descriptor is a ``native.ServoSimPlant``
+        and the launch an evaluation launch, so a fixed-command table, an evaluation record or a trace must be attached when
+        the simulator steps; a simulator without a robot gets the identity action and actuator tables and a switched-off
+        randomisation block for the time.  None: back to exactly the descriptor class and ``reserved`` the simulator had.
+        Every row is checked here (``mdp.randomization.check_plant_table``) - the library cannot read them."""
+        if table is None:
+            if self._plant_table is None:
+                return
+            cls, installed = self._plant_undo
+            self._plant_table = self._plant_undo = None
+            for attrs, field in installed:                              # what was installed for the table's time goes with it
+                for name, empty in attrs:
+                    setattr(self, name, empty)
+                C.memset(C.addressof(getattr(self._desc, field)), 0, C.sizeof(getattr(self._desc, field)))
+            old = cls()
+            C.memmove(C.addressof(old), C.addressof(self._desc), C.sizeof(old))
+            self._desc = old
+            self._announce()
+            return
+        from cat_envs.tasks.utils.mdp import randomization as RZ
+        if not self._actuators:
+            raise ValueError("a plant table needs the row's act_hist field: this simulator was built without an actuator "
+                             "descriptor (actuators = False)")
+        t = self._table(table, native.SERVO_PLANT_FLOATS, "the plant table")
+        entries = self._actuator_entries or [(float(self._desc.kp), float(self._desc.kd), float(self._desc.inertia))] * self.J
+        si = float(self._desc.inertia) if self._randomize_words is None else float(self._randomize_words[native.SERVO_RANDOMIZE_WORDS["servo_inertia"]])
+        RZ.check_plant_table(t.cpu().numpy(), int(self._desc.decimation), float(self._desc.dt),
+                             [dict(kp=e[0], kd=e[1], inertia=e[2]) for e in entries], si)
+        if self._plant_table is None:
+            cls, new = type(self._desc), native.ServoSimPlant()
+            C.memmove(C.addressof(new), C.addressof(self._desc), C.sizeof(self._desc))
+            self._desc, installed = new, []
+            had = self._action_table is None, self._actuator_table is None, self._randomize_block is None
+            self._randomize, was = True, self._randomize
+            try:
+                if had[2]:                                              # installs the identity tables where they are missing, too
+                    self.set_randomize_block(self.neutral_randomize_words())
+            finally:
+                self._randomize = was
+            if had[0]:
+                installed.append(((("_action_table", None), ("_action_entries", []), ("action_width", self.J)), "act"))
+            if had[1]:
+                installed.append(((("_actuator_table", None), ("_actuator_entries", [])), "actu"))
+            if had[2]:
+                installed.append(((("_randomize_block", None), ("_randomize_words", None)), "rnd"))
+            self._plant_undo = (cls, installed)
+        self._plant_table = t
+        p = self._desc.plant
+        p.table, p.reserved[0], p.reserved[1] = t.data_ptr(), 0, 0
+        self._announce()
 
     def set_history_table(self, words):
         """``words``: the T words ``cur | w << 8 | newest << 16`` of the history map, one per float of the row's
@@ -809,6 +868,9 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         return {"servo": fp}
 
     def state_dict(self) -> dict:
+        if self._plant_table is not None:
+            raise RuntimeError("run state: a plant table is attached to the simulator; an evaluation is not a resumable state "
+                               "(detach it before saving)")
         if self._fixed_command is not None or self._eval_record is not None or self._trace is not None:
             raise RuntimeError("run state: a fixed-command table, an evaluation record or a trace is attached to the simulator; "
                                "an evaluation is not a resumable state (detach them before saving)")
@@ -1113,6 +1175,11 @@ class CaTEnv:
         """per-env commands [N, 3], or a schedule [S, N, 3] of ``segment_steps`` control steps per segment, that replace
         the simulator's own draws (None: back to the draws)"""
         self._servo_sim().set_fixed_command(commands, segment_steps)
+
+    def set_fixed_plant(self, table: torch.Tensor | None):
+        """per-env pinned plants [N, 8] (``cleanrl.evaluate.plant_grid``): gains, joint friction, armature, base mass and
+        actuator lag of env i are what row i pins, whatever the randomisation draws (None: back to the draws)"""
+        self._servo_sim().set_fixed_plant(table)
 
     def set_trace(self, trace: torch.Tensor | None):
         """attach (or, with None, detach) the simulator's step trace [T, K, 72]"""

@@ -6,6 +6,11 @@ per-env table of fixed commands (``catppo_servo_sim.fixed_command``).  Nothing i
 tables come back once, at the end, and ``aggregate`` - pure numpy, no device - turns them into metrics in fp64.
 DESIGN section 9, "Evaluation".
 
+Robustness ("Robustness"): ``plant`` is a per-env table of pinned plants (``plant_grid``; gains, joint
+friction, armature, base mass and actuator lag, ``catppo_servo_plant``) that the simulator's launch puts in the place of the
+randomised or nominal robot; ``sweep`` crosses it with a command grid, ``EvalResult.by_plant`` and ``robustness`` - pure
+numpy again - say where in the range the policy breaks.
+
 Step responses ("Step responses"): ``commands`` may be a schedule ``[S, N, 3]`` of ``segment_steps``
 control steps per segment (``command_sequence``), and ``trace_envs = K`` has the simulator write one row of 72 floats per
 step for each of its first K envs (``catppo_servo_sim.trace``, inside the same launch).  ``step_response`` - pure numpy
@@ -20,6 +25,9 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from cat_envs.native import SERVO_EVAL_FIELDS as FIELDS
+from cat_envs.native import SERVO_PLANT_BITS as PLANT_BITS
+from cat_envs.native import SERVO_PLANT_FLOATS as PLANT_FLOATS
+from cat_envs.native import SERVO_PLANT_WORDS as PLANT_WORDS
 from cat_envs.native import SERVO_TRACE_FIELDS as TRACE_FIELDS
 from cat_envs.native import SERVO_TRACE_FLOATS as TRACE_FLOATS
 from cat_envs.native import SERVO_TRACE_PUSHED as TRACE_PUSHED
@@ -42,6 +50,121 @@ def command_grid(vx=(-0.3, 1.0, 1), vy=(-0.7, 0.7, 1), wz=(-0.78, 0.78, 1), num_
     pts = np.stack([g.reshape(-1) for g in np.meshgrid(*axes, indexing="ij")], 1).astype(np.float32)
     idx = np.arange(int(num_envs), dtype=np.int64) % len(pts)
     return np.ascontiguousarray(pts[idx]), idx
+
+
+PLANT_QUANTITIES = tuple(PLANT_BITS)         # kp_scale kd_scale friction armature mass_scale lag, in the order of their words
+
+
+def pack_plant(named: dict) -> np.ndarray:
+    """the ``[P, 8]`` fp32 packing of a named table: ``named[q]`` is ``[P]`` fp64 for every pinned quantity ``q`` (NaN: this row
+    leaves ``q`` alone), absent or None for a quantity nobody pins.  Word 0 holds the pin bits and word 6 the lag as integers"""
+    cols = {q: np.asarray(v, np.float64).reshape(-1) for q, v in named.items() if q in PLANT_BITS and v is not None}
+    unknown = [q for q in named if q not in PLANT_BITS and q != "packed"]
+    if unknown:
+        raise ValueError(f"unknown plant quantities {unknown} (known: {list(PLANT_QUANTITIES)})")
+    if not cols:
+        raise ValueError("a plant table pins at least one quantity")
+    rows = {len(v) for v in cols.values()}
+    if len(rows) != 1:
+        raise ValueError(f"the quantities of a plant table have one length, got {sorted(rows)}")
+    t = np.zeros((rows.pop(), PLANT_FLOATS), np.float32)
+    ints = t.view(np.int32)
+    for q, v in cols.items():
+        on = ~np.isnan(v)
+        ints[on, PLANT_WORDS["bits"]] |= PLANT_BITS[q]
+        if q == "lag":
+            if (v[on] != np.round(v[on])).any():
+                raise ValueError("the lag of a plant is a whole number of physics steps")
+            ints[on, PLANT_WORDS[q]] = v[on].astype(np.int32)
+        else:
+            t[on, PLANT_WORDS[q]] = v[on].astype(np.float32)
+    return t
+
+
+def plant_grid(kp_scale=None, kd_scale=None, friction=None, armature=None, mass_scale=None, lag=None, num_envs: int = 1) -> dict:
+    """A named table of pinned plants: ``{quantity: [num_envs] fp64 for every pinned quantity, "packed": [num_envs, 8] fp32}``.
+    Each argument is None (not pinned: the env keeps its draw or its nominal value), a scalar, or ``(lo, hi, n)`` like an axis
+    of ``command_grid`` (both ends included, ``n = 1`` the midpoint; the lag's points are rounded to whole physics steps).  The
+    table is the full product of the axes, ``kp_scale`` slowest and ``lag`` fastest; env ``i`` gets point ``i % n_points``."""
+    given = dict(kp_scale=kp_scale, kd_scale=kd_scale, friction=friction, armature=armature, mass_scale=mass_scale, lag=lag)
+    axes = {}
+    for q, a in given.items():
+        if a is None:
+            continue
+        if np.ndim(a) == 0:
+            pts = np.array([float(a)])
+        else:
+            if len(a) != 3:
+                raise ValueError(f"plant_grid: {q} is None, a scalar or (lo, hi, n), got {a!r}")
+            lo, hi, n = float(a[0]), float(a[1]), int(a[2])
+            if n < 1:
+                raise ValueError(f"plant_grid: the axis {q} needs at least one point")
+            pts = np.array([(lo + hi) / 2.0]) if n == 1 else np.linspace(lo, hi, n)
+        if not np.isfinite(pts).all():
+            raise ValueError(f"plant_grid: {q} must be finite, got {a!r}")
+        axes[q] = np.round(pts) if q == "lag" else pts
+    if not axes:
+        raise ValueError("plant_grid: at least one quantity must be pinned")
+    if int(num_envs) < 1:
+        raise ValueError("num_envs must be at least 1")
+    mesh = np.meshgrid(*axes.values(), indexing="ij")
+    idx = np.arange(int(num_envs), dtype=np.int64) % mesh[0].size
+    named = {q: np.ascontiguousarray(g.reshape(-1)[idx]) for q, g in zip(axes, mesh)}
+    named["packed"] = pack_plant(named)
+    return named
+
+
+def parse_plant_axes(specs) -> dict:
+    """the keyword arguments of ``plant_grid`` from command-line words ``name=value`` or ``name=lo:hi:n`` (play.py --eval_plant)"""
+    axes = {}
+    for spec in specs:
+        name, eq, text = str(spec).partition("=")
+        parts = text.split(":")
+        if not eq or name not in PLANT_BITS or name in axes or len(parts) not in (1, 3):
+            raise ValueError(f"--eval_plant takes name=value or name=lo:hi:n with each name of {list(PLANT_QUANTITIES)} at most once, "
+                             f"got '{spec}'")
+        try:
+            axes[name] = float(parts[0]) if len(parts) == 1 else (float(parts[0]), float(parts[1]), int(parts[2]))
+        except ValueError:
+            raise ValueError(f"--eval_plant: '{spec}' holds no numbers (name=value or name=lo:hi:n)") from None
+    return axes
+
+
+def _plant_rows(plant) -> np.ndarray:
+    """``[P, 8]`` fp32 of a named table, or of a packing handed over as it is"""
+    if isinstance(plant, dict):
+        return np.ascontiguousarray(plant["packed"] if "packed" in plant else pack_plant(plant), np.float32)
+    rows = np.ascontiguousarray(plant, np.float32)
+    if rows.ndim != 2 or rows.shape[1] != PLANT_FLOATS:
+        raise ValueError(f"a plant table is a plant_grid() dict or [P, {PLANT_FLOATS}] fp32, got shape {rows.shape}")
+    return rows
+
+
+def sweep(commands, plants):
+    """``(commands [C * P, 3] fp32, plant table)`` for N = C x P envs from ``commands`` [C, 3] and ``plants`` (a
+    ``plant_grid`` dict or a packing [P, 8]): env ``i`` gets command ``i % C`` and plant ``i // C``.  The plant table comes
+    back as it came: a named dict (every array repeated, ``packed`` included) or a packing"""
+    cmd = np.asarray(commands, np.float32)
+    if cmd.ndim != 2 or cmd.shape[1] != 3 or len(cmd) < 1:
+        raise ValueError(f"sweep: commands are [C, 3] with C >= 1, got {cmd.shape}")
+    rows = _plant_rows(plants)
+    if len(rows) < 1:
+        raise ValueError("sweep: the plant table needs at least one row")
+    C, P = len(cmd), len(rows)
+    tiled = np.ascontiguousarray(np.tile(cmd, (P, 1)))
+    if isinstance(plants, dict):
+        out = {q: np.repeat(np.asarray(v), C, axis=0) for q, v in plants.items() if q != "packed" and v is not None}
+        out["packed"] = np.ascontiguousarray(np.repeat(rows, C, axis=0))
+        return tiled, out
+    return tiled, np.ascontiguousarray(np.repeat(rows, C, axis=0))
+
+
+def plant_of_row(row) -> dict:
+    """``{quantity: value}`` of the quantities one packed row pins (the lag an int)"""
+    row = np.ascontiguousarray(row, np.float32)
+    bits = int(row.view(np.int32)[PLANT_WORDS["bits"]])
+    return {q: (int(row.view(np.int32)[PLANT_WORDS[q]]) if q == "lag" else float(row[PLANT_WORDS[q]]))
+            for q in PLANT_QUANTITIES if bits & PLANT_BITS[q]}
 
 
 def command_sequence(points, num_envs: int):
@@ -214,6 +337,7 @@ class EvalResult:
     segment_steps: int | None = None              # control steps per segment when ``commands`` is a schedule
     pushes: bool = False                          # the env has cfg.events and ran with its interval events on
     termination_share: dict | None = None         # envs with cfg.terminations: {term: share of the ended episodes it ended}
+    plant: np.ndarray | None = None               # [N, 8] fp32: the pinned plants (``plant_grid``), or None
 
     def push_recovery(self, tolerance: float = 0.1) -> list:
         """``push_recovery`` of this evaluation's trace (needs a trace)"""
@@ -246,6 +370,43 @@ class EvalResult:
                         "metrics": self._aggregate(rows)})
         return out
 
+    def by_plant(self) -> list:
+        """the metrics per distinct plant row, in order of first appearance: ``{"plant", "envs", "metrics"}``, ``plant`` being
+        ``{quantity: value}`` of what the row pins; without a plant table one group with ``plant`` None"""
+        if self.plant is None:
+            return [{"plant": None, "envs": int(len(self.per_env)), "metrics": dict(self.metrics)}]
+        _, first, inverse = np.unique(self.plant.view(np.uint32), axis=0, return_index=True, return_inverse=True)
+        inverse = np.asarray(inverse).reshape(-1)
+        out = []
+        for g in np.argsort(first):
+            rows = np.nonzero(inverse == g)[0]
+            out.append({"plant": plant_of_row(self.plant[rows[0]]), "envs": int(len(rows)), "metrics": self._aggregate(rows)})
+        return out
+
+    def robustness(self, metric: str = "reward_per_step") -> dict:
+        """where in the pinned range the policy breaks, from ``by_plant()`` in fp64: per pinned quantity ``metric`` against
+        each value of it (the mean over the groups that share the value, values ascending), the best and the worst group with
+        their plants, and the spread best - worst.  Groups whose ``metric`` is None (no step, no ended episode) are left out"""
+        if self.plant is None:
+            raise ValueError("robustness needs a plant table (evaluate_policy(plant=...))")
+        groups = [g for g in self.by_plant() if g["metrics"].get(metric) is not None]
+        if not groups:
+            if metric not in self.metrics:
+                raise ValueError(f"unknown metric '{metric}' (known: {sorted(self.metrics)})")
+            return {"metric": metric, "groups": 0, "by_quantity": {}, "best": None, "worst": None, "spread": None}
+        value = np.array([g["metrics"][metric] for g in groups], np.float64)
+        by_quantity = {}
+        for q in PLANT_QUANTITIES:
+            pinned = [(g["plant"][q], v) for g, v in zip(groups, value) if q in g["plant"]]
+            if pinned:
+                xs = sorted({x for x, _ in pinned})
+                by_quantity[q] = [{"value": x, "groups": sum(1 for y, _ in pinned if y == x),
+                                   metric: float(np.mean([v for y, v in pinned if y == x]))} for x in xs]
+        hi, lo = int(np.argmax(value)), int(np.argmin(value))
+        pick = lambda i: {"plant": groups[i]["plant"], "envs": groups[i]["envs"], metric: float(value[i])}   # noqa: E731
+        return {"metric": metric, "groups": len(groups), "by_quantity": by_quantity, "best": pick(hi), "worst": pick(lo),
+                "spread": float(value[hi] - value[lo])}
+
     def to_json(self, by_command: bool = True) -> str:
         d = {"metrics": self.metrics, "num_envs": int(len(self.per_env)), "fields": list(self.fields)}
         if by_command and self.commands is not None:
@@ -259,13 +420,16 @@ class EvalResult:
             d["push_recovery"] = {"summary": summarise_push_recovery(rows), "pushes": rows}
         if self.termination_share is not None:
             d["termination_share"] = dict(self.termination_share)
+        if self.plant is not None:
+            d["by_plant"] = self.by_plant()
+            d["robustness"] = self.robustness()
         return json.dumps(d)
 
 
 def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool = True,
                     fresh_cat_state: bool = False, segment_steps: int | None = None, trace_envs: int = 0,
                     corruption: bool | None = None, pushes: bool | None = None,
-                    randomization: bool | None = None) -> EvalResult:
+                    randomization: bool | None = None, plant=None) -> EvalResult:
     """Roll ``policy`` out for ``steps`` control steps from a fresh reset and measure it.
 
     ``policy`` is an ``Agent`` - its observations are normalised by the frozen ``obs_rms`` and the action is the mean
@@ -296,6 +460,12 @@ def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool 
 
     ``randomization`` (envs whose ``cfg.events`` randomises the robot): None leaves the switch as it is; a bool sets it for
     the evaluation (False: the nominal robot) and puts it back afterwards, likewise.
+
+    ``plant`` (a ``plant_grid`` dict or a packing [N, 8]): env i's plant is what row i pins - gains, joint friction, armature,
+    base mass, actuator lag - for the whole evaluation, inside the simulator's launch (``CaTEnv.set_fixed_plant``); the table
+    is attached for the call and detached afterwards, also when the roll-out raises.  Orthogonal to ``randomization``: a
+    quantity that a row does not pin keeps the env's draw, or its nominal value with the switch off.  ``EvalResult.plant``,
+    ``by_plant()`` and ``robustness()`` read the result per plant.
 
     On an env with ``cfg.terminations`` the result carries ``termination_share``: per term, the share of the episodes that
     ended during the evaluation whose last step had the term set (the termination manager's record, which the reset zeroes
@@ -328,6 +498,12 @@ def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool 
     elif commands is not None:
         table = torch.as_tensor(np.asarray(commands.detach().cpu() if isinstance(commands, torch.Tensor) else commands,
                                            np.float32)).reshape(*lead, n, 3).contiguous().to(dev)
+    plant_table = None
+    if plant is not None:
+        rows = _plant_rows(plant)
+        if len(rows) != n:
+            raise ValueError(f"the plant table has {len(rows)} rows, the env {n} envs (plant_grid(..., num_envs={n}))")
+        plant_table = torch.from_numpy(rows.copy()).to(dev)
     if isinstance(policy, Agent):
         agent = policy
 
@@ -380,6 +556,8 @@ def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool 
             u.set_fixed_commands(table)
         if trace is not None:
             u.set_trace(trace)
+        if plant_table is not None:
+            u.set_fixed_plant(plant_table)                           # ValueError names the row and the quantity
         obs = env.reset()[0]["policy"]
         with torch.no_grad():
             for _ in range(steps):
@@ -398,6 +576,8 @@ def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool 
                     viol[:, -1].add_(hit.any(1))
     finally:
         frozen.close()
+        if plant_table is not None:
+            u.set_fixed_plant(None)
         if trace is not None:
             u.set_trace(None)
         u.set_eval_record(None)
@@ -411,7 +591,8 @@ def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool 
     res = EvalResult(per_env=record.cpu().numpy(), commands=None if table is None else table.cpu().numpy(),
                      cat_reward=cat_reward.cpu().numpy(), termination_prob=term_prob.cpu().numpy(),
                      violations=viol.cpu().numpy(), term_names=names, trace=None if trace is None else trace.cpu().numpy(),
-                     segment_steps=segment_steps if lead else None, pushes=pushes_on)
+                     segment_steps=segment_steps if lead else None, pushes=pushes_on,
+                     plant=None if plant_table is None else plant_table.cpu().numpy())
     res.metrics = res._aggregate()
     tm = getattr(u, "termination_manager", None)
     if tm is not None:

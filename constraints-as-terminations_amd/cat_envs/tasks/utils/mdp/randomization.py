@@ -100,6 +100,57 @@ def check_corners(block, actuator_entries, sim_dt):
                                  f"on {block['m0']:g} kg)")
 
 
+#: a row of the plant table (include/catppo.h, "Pinned plants"): the quantity's pin bit and the word that holds its value
+PLANT_BITS = {"kp_scale": 0x1, "kd_scale": 0x2, "friction": 0x4, "armature": 0x8, "mass_scale": 0x10, "lag": 0x20}
+PLANT_WORDS = {"kp_scale": 1, "kd_scale": 2, "friction": 3, "armature": 4, "mass_scale": 5, "lag": 6}
+PLANT_FLOATS = 8
+
+
+def check_plant_table(table, decimation, sim_dt, actuator_entries, servo_inertia):
+    """every row of a plant table [N, 8] (fp32; words 0 and 6 integers): ``ValueError`` naming the row and the quantity unless
+    all values are finite, no unknown bit is set, kp_scale, kd_scale, friction and armature are >= 0, mass_scale > 0, the lag
+    lies in 0 .. 3 * decimation, and every joint stays stable at the pinned kp', kd' and inertia' (``check_corners``' condition
+    2 a + b < 4 with a = kd' dt / I', b = kp' dt^2 / I'; an unpinned quantity counts with the actuator entry's value).  Pure,
+    needs no device.  What a row holds for a quantity whose bit is clear is not read by the launch, but must be finite"""
+    t = np.ascontiguousarray(table, np.float32)
+    if t.ndim != 2 or t.shape[1] != PLANT_FLOATS:
+        raise ValueError(f"the plant table has {PLANT_FLOATS} words per row, got shape {t.shape}")
+    ints = t.view(np.int32)
+    dt, max_lag = float(sim_dt), min(3 * int(decimation), 255)
+    f32 = np.float32
+    for i in range(t.shape[0]):
+        bits, lag = int(ints[i, 0]), int(ints[i, PLANT_WORDS["lag"]])
+        if bits & ~sum(PLANT_BITS.values()):
+            raise ValueError(f"plant table row {i}: pin bits {bits:#x} has unknown bits")
+        for name in ("kp_scale", "kd_scale", "friction", "armature", "mass_scale"):
+            v = float(t[i, PLANT_WORDS[name]])
+            if not math.isfinite(v):
+                raise ValueError(f"plant table row {i}: {name} must be finite, got {v}")
+            if name == "mass_scale":
+                if bits & PLANT_BITS[name] and not v > 0.0:
+                    raise ValueError(f"plant table row {i}: mass_scale must be > 0, got {v:g}")
+            elif bits & PLANT_BITS[name] and v < 0.0:
+                raise ValueError(f"plant table row {i}: {name} must be >= 0, got {v:g}")
+        if ints[i, 7] != 0:
+            raise ValueError(f"plant table row {i}: the spare word 7 must be zero")
+        if not 0 <= lag <= max_lag:
+            raise ValueError(f"plant table row {i}: lag must be in 0 .. {max_lag} physics steps (three control steps), got {lag}")
+        if bits & (PLANT_BITS["kp_scale"] | PLANT_BITS["kd_scale"] | PLANT_BITS["armature"]):
+            for j, e in enumerate(actuator_entries):
+                kp, kd, inertia = f32(e["kp"]), f32(e["kd"]), f32(e["inertia"])
+                if bits & PLANT_BITS["kp_scale"]:
+                    kp = kp * t[i, PLANT_WORDS["kp_scale"]]
+                if bits & PLANT_BITS["kd_scale"]:
+                    kd = kd * t[i, PLANT_WORDS["kd_scale"]]
+                if bits & PLANT_BITS["armature"]:
+                    inertia = f32(servo_inertia) + t[i, PLANT_WORDS["armature"]]
+                a, b = float(kd) * dt / float(inertia), float(kp) * dt * dt / float(inertia)
+                if not 2.0 * a + b < 4.0:
+                    raise ValueError(f"plant table row {i}: joint {j} is unstable at the pinned plant (stiffness {float(kp):g}, "
+                                     f"damping {float(kd):g}, inertia {float(inertia):g}, dt {dt:g}): 2 a + b = {2.0 * a + b:.4g} "
+                                     f"must stay below 4 (a = kd dt / I, b = kp dt^2 / I)")
+
+
 def build_randomization(events_cfg, actuator_entries, joint_names, synthetic_cfg, sim_dt, decimation, armatures=None):
     """(block, spec) of the randomisation terms of an ``EventCfg``, or (None, None) when it has none; pure, needs no device,
     every float already rounded to fp32.  ``actuator_entries``: the twelve entries of ``mdp.actuators.build_table`` (None: the

@@ -8,9 +8,9 @@
 // whole base state redundantly (the joint sums are butterflies, all lanes end up with the same bits), so no lane waits
 // for another except through the shuffles.  The next row is assembled in LDS and leaves as coalesced 16-byte stores.
 //   tree16: x += xor-shuffle 8, 4, 2, 1 (width 16)     tree4 (feet): x += xor-shuffle 1, 2
-// The kernel template is servo_sim_kernel.h, the host side of the launch servo_sim_host.h.  The instances compile in five
+// The kernel template is servo_sim_kernel.h, the host side of the launch servo_sim_host.h.  The instances compile in six
 // units, by the last descriptor of their pack: this one (none behind the terminations; it holds the entry point, too),
-// servo_sim_actions.hip, servo_sim_actuators.hip, servo_sim_randomize.hip and servo_sim_history.hip.
+// servo_sim_actions.hip, servo_sim_actuators.hip, servo_sim_randomize.hip, servo_sim_history.hip and servo_sim_plant.hip.
 #include "servo_sim_kernel.h"
 
 // the descriptor's size is part of the ABI: cat_envs/native.py (ServoSimRewards) and tests/test_servo_reward_twin.py pin it
@@ -51,6 +51,10 @@ static_assert(offsetof(catppo_servo_sim_history, rnd) == 472 && offsetof(catppo_
                   offsetof(catppo_servo_history, floats) == 12 && sizeof(catppo_servo_sim_history) == 504 &&
                   CATPPO_SERVO_OBS_HISTORY_MAX_FLOATS == 512 && CATPPO_SERVO_OBS_HISTORY_MAX_DEPTH == 16,
               "catppo_servo_sim_history: the history descriptor behind the randomisation descriptor");
+static_assert(offsetof(catppo_servo_sim_plant, hist) == 488 && offsetof(catppo_servo_sim_plant, plant) == 504 &&
+                  sizeof(catppo_servo_plant) == 16 && offsetof(catppo_servo_plant, reserved) == 8 &&
+                  sizeof(catppo_servo_sim_plant) == 520 && CATPPO_SERVO_PLANT_FLOATS == 8,
+              "catppo_servo_sim_plant: the plant descriptor behind the history descriptor");
 
 extern "C" int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* desc, void* stream) {
   CATPPO_CHECK_ARG(ctx, ctx != nullptr);
@@ -66,7 +70,8 @@ extern "C" int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* de
   const bool rew = d.reward_terms > 0;
   const hipStream_t st = static_cast<hipStream_t>(stream);
   // the unit that holds the instance: by the last descriptor of the pack
-  if (x.hs) catppo_internal_servo_sim_launch_history(mode, rew, nblk, lds_bytes, st, d, x);
+  if (x.pl) catppo_internal_servo_sim_launch_plant(mode, rew, nblk, lds_bytes, st, d, x);
+  else if (x.hs) catppo_internal_servo_sim_launch_history(mode, rew, nblk, lds_bytes, st, d, x);
   else if (x.rn) catppo_internal_servo_sim_launch_randomize(mode, rew, nblk, lds_bytes, st, d, x);
   else if (x.au) catppo_internal_servo_sim_launch_actuators(mode, rew, nblk, lds_bytes, st, d, x);
   else if (x.ac) catppo_internal_servo_sim_launch_actions(mode, rew, nblk, lds_bytes, st, d, x);

@@ -20,6 +20,7 @@ struct ServoExts {
   const catppo_servo_actuators* au = nullptr;
   const catppo_servo_randomize* rn = nullptr;
   const catppo_servo_history* hs = nullptr;
+  const catppo_servo_plant* pl = nullptr;
 };
 
 namespace {
@@ -28,18 +29,20 @@ constexpr int kEnvsPerBlock = 16, kJoints = 12, kPrivate = 14;
 constexpr int kRawObs = 45;                                              // the raw observation a policy observation reads
 
 // the level of `reserved` is its index here; it announces the descriptors of every level up to its own.
-// catppo_servo_sim_history is a superset of every shorter form (the static_asserts of servo_sim.hip)
-enum { kLvNone, kLvObs, kLvEvents, kLvCommands, kLvTerminations, kLvActions, kLvActuators, kLvRandomize, kLvHistory, kLevels };
+// catppo_servo_sim_plant is a superset of every shorter form (the static_asserts of servo_sim.hip)
+enum { kLvNone, kLvObs, kLvEvents, kLvCommands, kLvTerminations, kLvActions, kLvActuators, kLvRandomize, kLvHistory, kLvPlant,
+       kLevels };
 constexpr struct { int32_t magic; size_t offset; } kServoExtTable[kLevels] = {
     {0, 0},
-    {CATPPO_SERVO_EXT_OBS, offsetof(catppo_servo_sim_history, obs)},
-    {CATPPO_SERVO_EXT_EVENTS, offsetof(catppo_servo_sim_history, ev)},
-    {CATPPO_SERVO_EXT_COMMANDS, offsetof(catppo_servo_sim_history, cmd)},
-    {CATPPO_SERVO_EXT_TERMINATIONS, offsetof(catppo_servo_sim_history, term)},
-    {CATPPO_SERVO_EXT_ACTIONS, offsetof(catppo_servo_sim_history, act)},
-    {CATPPO_SERVO_EXT_ACTUATORS, offsetof(catppo_servo_sim_history, actu)},
-    {CATPPO_SERVO_EXT_RANDOMIZE, offsetof(catppo_servo_sim_history, rnd)},
-    {CATPPO_SERVO_EXT_HISTORY, offsetof(catppo_servo_sim_history, hist)}};
+    {CATPPO_SERVO_EXT_OBS, offsetof(catppo_servo_sim_plant, obs)},
+    {CATPPO_SERVO_EXT_EVENTS, offsetof(catppo_servo_sim_plant, ev)},
+    {CATPPO_SERVO_EXT_COMMANDS, offsetof(catppo_servo_sim_plant, cmd)},
+    {CATPPO_SERVO_EXT_TERMINATIONS, offsetof(catppo_servo_sim_plant, term)},
+    {CATPPO_SERVO_EXT_ACTIONS, offsetof(catppo_servo_sim_plant, act)},
+    {CATPPO_SERVO_EXT_ACTUATORS, offsetof(catppo_servo_sim_plant, actu)},
+    {CATPPO_SERVO_EXT_RANDOMIZE, offsetof(catppo_servo_sim_plant, rnd)},
+    {CATPPO_SERVO_EXT_HISTORY, offsetof(catppo_servo_sim_plant, hist)},
+    {CATPPO_SERVO_EXT_PLANT, offsetof(catppo_servo_sim_plant, plant)}};
 
 // fills `x` from what desc->reserved announces; returns nullptr, or the condition that failed
 inline const char* servo_exts_of(const catppo_servo_sim* desc, ServoExts& x) {
@@ -58,12 +61,15 @@ inline const char* servo_exts_of(const catppo_servo_sim* desc, ServoExts& x) {
   x.au = static_cast<const catppo_servo_actuators*>(at(kLvActuators));
   x.rn = static_cast<const catppo_servo_randomize*>(at(kLvRandomize));
   x.hs = static_cast<const catppo_servo_history*>(at(kLvHistory));
+  x.pl = static_cast<const catppo_servo_plant*>(at(kLvPlant));
   // an empty descriptor below the announced level is an absent one; the action, actuator and randomisation descriptors are
-  // never absent once announced, and a history needs its observations (servo_sim_check)
+  // never absent once announced, and a history needs its observations (servo_sim_check); the history descriptor itself may be
+  // empty from the plant level on
   if (level >= kLvEvents && x.obs->width == 0 && x.obs->table == nullptr) x.obs = nullptr;
   if (level >= kLvCommands && x.ev->block == nullptr && x.ev->floats == 0) x.ev = nullptr;
   if (level >= kLvTerminations && x.cm->block == nullptr && x.cm->floats == 0) x.cm = nullptr;
   if (level >= kLvActions && x.tm->table == nullptr && x.tm->terms == 0) x.tm = nullptr;
+  if (level >= kLvPlant && x.hs->map == nullptr && x.hs->floats == 0) x.hs = nullptr;
   return nullptr;
 }
 
@@ -139,6 +145,12 @@ inline const char* servo_sim_check(const catppo_servo_sim& d, const ServoExts& x
     const int64_t ho = x.hs->off_hist;
     SERVO_REQUIRE(ho % 4 == 0 && ho >= d.row_floats && ho + pad4(x.hs->floats) <= d.row_stride);
   }
+  if (x.pl) {
+    // a plant table is an evaluation input: the launch is the step-response instance of its pack
+    SERVO_REQUIRE(d.fixed_command != nullptr || d.eval != nullptr || d.trace != nullptr);
+    SERVO_REQUIRE(x.pl->reserved[0] == 0 && x.pl->reserved[1] == 0);
+    SERVO_REQUIRE(x.pl->table != nullptr && aligned16(x.pl->table));
+  }
 
   // every memory range the launch touches, by its byte extent (the tables of a variable number of entries by the most they
   // may hold); a NULL pointer is a buffer that is not there.  Every two of them are disjoint
@@ -163,7 +175,8 @@ inline const char* servo_sim_check(const catppo_servo_sim& d, const ServoExts& x
       {x.ac ? x.ac->table : nullptr, sizeof(catppo_servo_action_entry) * kJoints, "act.table"},
       {x.au ? x.au->table : nullptr, sizeof(catppo_servo_actuator_entry) * kJoints, "actu.table"},
       {x.rn ? x.rn->block : nullptr, f32 * CATPPO_SERVO_RANDOMIZE_FLOATS, "rnd.block"},
-      {x.hs ? x.hs->map : nullptr, sizeof(uint32_t) * (uintptr_t)(x.hs ? x.hs->floats : 0), "hist.map"}};
+      {x.hs ? x.hs->map : nullptr, sizeof(uint32_t) * (uintptr_t)(x.hs ? x.hs->floats : 0), "hist.map"},
+      {x.pl ? x.pl->table : nullptr, n * CATPPO_SERVO_PLANT_FLOATS * f32, "plant.table"}};
   constexpr int kRanges = sizeof(ranges) / sizeof(ranges[0]);
   for (int i = 0; i < kRanges; ++i)
     for (int j = i + 1; j < kRanges; ++j) {

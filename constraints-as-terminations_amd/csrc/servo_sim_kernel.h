@@ -1,4 +1,4 @@
-// The servo simulator's kernel template, its helpers and launch(): included by the five units that hold its instances, so
+// The servo simulator's kernel template, its helpers and launch(): included by the six units that hold its instances, so
 // that they compile side by side (servo_sim.hip lists them).  Everything here has internal linkage.
 #pragma once
 #include <type_traits>
@@ -395,6 +395,36 @@ __device__ __forceinline__ void randomize(const catppo_servo_sim& d, const ActuR
   }
 }
 
+// what a lane keeps of its env's row of the plant table (lane k < 8 of the env's 16: word k); empty without the table
+template <bool kOn>
+struct PlantRegs {};
+template <>
+struct PlantRegs<true> {
+  float mine = 0.f;
+};
+
+// the pinned plant of the env ("Robustness"): the quantities whose bit is set in word 0 of the env's row
+// stand where the lag draw and randomize() left theirs, on every joint.  Seven 16-wide shuffles up front (every lane of the env
+// takes part), then branches that the env's 16 lanes take together; one rounded operation each
+__device__ __forceinline__ void pin_plant(const catppo_servo_sim& d, const PlantRegs<true>& pr, ActuRegs<true>& ur, RndRegs<true>& rr) {
+  const uint32_t bits = (uint32_t)__float_as_int(__shfl(pr.mine, 0, 16));
+  const float t1 = __shfl(pr.mine, 1, 16), t2 = __shfl(pr.mine, 2, 16), t3 = __shfl(pr.mine, 3, 16);
+  const float t4 = __shfl(pr.mine, 4, 16), t5 = __shfl(pr.mine, 5, 16);
+  const uint32_t lag = (uint32_t)__float_as_int(__shfl(pr.mine, 6, 16));
+  if (bits & CATPPO_SERVO_PLANT_KP) rr.kp = ur.entry.kp * t1;
+  if (bits & CATPPO_SERVO_PLANT_KD) rr.kd = ur.entry.kd * t2;
+  if (bits & CATPPO_SERVO_PLANT_FRICTION) rr.fr = t3;
+  if (bits & CATPPO_SERVO_PLANT_ARMATURE) rr.inertia = ev_word(rr.mine, 18) + t4;
+  if (bits & (CATPPO_SERVO_PLANT_FRICTION | CATPPO_SERVO_PLANT_ARMATURE)) rr.df = (rr.fr / rr.inertia) * d.dt;
+  if (bits & CATPPO_SERVO_PLANT_MASS) {
+    const float m0 = ev_word(rr.mine, 16);
+    const float m = m0 * t5;
+    rr.weight = m * ev_word(rr.mine, 17);
+    rr.av = fminf(d.vel_alpha / (m / m0), 1.f);
+  }
+  if (bits & CATPPO_SERVO_PLANT_LAG) ur.L = (int)(lag < 255u ? lag : 255u);
+}
+
 // kMode = kTrain is the launch with all three evaluation pointers NULL: everything they add is compiled out of it, so
 // that a training step runs the code it ran before the fields existed.  kEvaluate: a fixed-command table [N, 3] or an
 // evaluation record, and nothing else - the evaluation that runs inside training keeps the code it had, too.
@@ -435,6 +465,10 @@ __device__ __forceinline__ void randomize(const catppo_servo_sim& d, const ActuR
 // LDS-staged part of the row: per float the current frame's (the first frame of an episode fills every slot) or the input
 // row's float one slot later.  Selects and copies, no arithmetic.  Orthogonal to the rest, compiled out without it: 32 more
 // instances (8 packs, evaluation folded as above), compiled in servo_sim_history.hip.
+// catppo_servo_plant, last in the pack and only behind catppo_servo_randomize, with or without catppo_servo_history (DESIGN
+// section 9, "Robustness"): the quantities that the env's row of the plant table pins stand where the lag draw and randomize()
+// left theirs.  An evaluation input: launch() takes the step-response instance whatever the mode.  Orthogonal to the rest,
+// compiled out without it: 48 more instances (16 packs without a history, 8 with one), compiled in servo_sim_plant.hip.
 template <int kMode, bool kRew, typename... Ext>
 __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeof...(Ext) == 0) ? 8 : 1) void servo_sim_kernel(
     const catppo_servo_sim d, const Ext... ext) {
@@ -449,6 +483,9 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
   static_assert(kActu || !kRnd, "the randomisation descriptor comes only behind the actuator descriptor");
   constexpr bool kHist = (std::is_same_v<Ext, catppo_servo_history> || ...);
   static_assert((kRnd && kObs) || !kHist, "the history descriptor comes only behind the randomisation descriptor, with observations");
+  constexpr bool kPlant = (std::is_same_v<Ext, catppo_servo_plant> || ...);
+  static_assert((kRnd && kMode == kStepResponse) || !kPlant,
+                "the plant descriptor comes only behind the randomisation descriptor, in the step-response instance");
   constexpr bool kEval = kMode != kTrain;
   RndRegs<kRnd> RR;                      // declared first: further down it reorders register initialisations of older instances
   ActuRegs<kActu> UR;                    // likewise
@@ -580,6 +617,12 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
     if ((tid & 63) < CATPPO_SERVO_RANDOMIZE_FLOATS && d.init == 0) RR.mine = blk[tid & 63];
     if (lane < kJoints && d.init == 0) RR.arm = blk[20 + lane];
   }
+  // lane k < 8 loads word k of its env's row of the plant table: 32 bytes per env; the spare lane groups past N read the row
+  // of env N - 1, which they recompute
+  PlantRegs<kPlant> PR;
+  if constexpr (kPlant)
+    if (lane < CATPPO_SERVO_PLANT_FLOATS && d.init == 0)
+      PR.mine = ext_of<catppo_servo_plant>(ext...).table[e * CATPPO_SERVO_PLANT_FLOATS + lane];
 
   if (init) {
     // the first state of episode 0: default pose + noise, at rest, four feet on the ground
@@ -672,6 +715,8 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
     }
     // randomisation: the robot of this env and episode
     if constexpr (kRnd) randomize(d, UR, gid, ep, lane, RR);
+    // pinned plant: after the lag draw and the randomisation
+    if constexpr (kPlant) pin_plant(d, PR, UR, RR);
     // ---- joints: `decimation` substeps of the clamped PD servo, semi-implicit Euler; the substep of largest |tau| is reported
     const float q_des = def + d.action_scale * a;
     float tau_w = 0.f;
@@ -1096,15 +1141,22 @@ void launch(int mode, bool rew, unsigned nblk, size_t lds_bytes, hipStream_t str
                             std::is_same_v<Ext, catppo_servo_actuators> || std::is_same_v<Ext, catppo_servo_randomize> ||
                             std::is_same_v<Ext, catppo_servo_history>) || ...)
                               ? kStepResponse : kEvaluate;
-  const Kernel table[3][2] = {{servo_sim_kernel<kTrain, false, Ext...>, servo_sim_kernel<kTrain, true, Ext...>},
-                              {servo_sim_kernel<kEvalAs, false, Ext...>, servo_sim_kernel<kEvalAs, true, Ext...>},
-                              {servo_sim_kernel<kStepResponse, false, Ext...>, servo_sim_kernel<kStepResponse, true, Ext...>}};
-  hipLaunchKernelGGL(table[mode][rew ? 1 : 0], dim3(nblk), dim3(kThreads), lds_bytes, stream, d, ext...);
+  // a plant table is an evaluation input (the entry point has checked that an evaluation pointer is set): its packs have the
+  // step-response instances only
+  if constexpr ((std::is_same_v<Ext, catppo_servo_plant> || ...)) {
+    const Kernel pinned[2] = {servo_sim_kernel<kStepResponse, false, Ext...>, servo_sim_kernel<kStepResponse, true, Ext...>};
+    hipLaunchKernelGGL(pinned[rew ? 1 : 0], dim3(nblk), dim3(kThreads), lds_bytes, stream, d, ext...);
+  } else {
+    const Kernel table[3][2] = {{servo_sim_kernel<kTrain, false, Ext...>, servo_sim_kernel<kTrain, true, Ext...>},
+                                {servo_sim_kernel<kEvalAs, false, Ext...>, servo_sim_kernel<kEvalAs, true, Ext...>},
+                                {servo_sim_kernel<kStepResponse, false, Ext...>, servo_sim_kernel<kStepResponse, true, Ext...>}};
+    hipLaunchKernelGGL(table[mode][rew ? 1 : 0], dim3(nblk), dim3(kThreads), lds_bytes, stream, d, ext...);
+  }
 }
 
 }  // namespace
 
-// the launches of the four other units (servo_sim.hip lists them): of a pack that ends with the descriptors the unit is named
+// the launches of the five other units (servo_sim.hip lists them): of a pack that ends with the descriptors the unit is named
 // after, and holds whichever of the optional ones before them are present.  The entry point has checked everything
 void catppo_internal_servo_sim_launch_actions(int mode, bool rew, unsigned nblk, size_t lds_bytes, hipStream_t stream,
                                               const catppo_servo_sim& d, const ServoExts& x);
@@ -1114,3 +1166,5 @@ void catppo_internal_servo_sim_launch_randomize(int mode, bool rew, unsigned nbl
                                                 const catppo_servo_sim& d, const ServoExts& x);
 void catppo_internal_servo_sim_launch_history(int mode, bool rew, unsigned nblk, size_t lds_bytes, hipStream_t stream,
                                               const catppo_servo_sim& d, const ServoExts& x);
+void catppo_internal_servo_sim_launch_plant(int mode, bool rew, unsigned nblk, size_t lds_bytes, hipStream_t stream,
+                                            const catppo_servo_sim& d, const ServoExts& x);

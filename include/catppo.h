@@ -729,7 +729,7 @@ typedef struct catppo_servo_sim {
   const uint8_t* reset;                  /* [N] */
   const int64_t* episode_length;         /* [N], before this step's increment */
   int64_t max_episode_length;
-  int32_t decimation, resample_steps, init, reserved;   /* reserved: 0 or one of CATPPO_SERVO_EXT_OBS / _EVENTS / _COMMANDS / _TERMINATIONS / _ACTIONS / _ACTUATORS / _RANDOMIZE / _HISTORY (see below) */
+  int32_t decimation, resample_steps, init, reserved;   /* reserved: 0 or one of CATPPO_SERVO_EXT_OBS / _EVENTS / _COMMANDS / _TERMINATIONS / _ACTIONS / _ACTUATORS / _RANDOMIZE / _HISTORY / _PLANT (see below) */
   uint64_t seed;
   float default_joint_pos[12];
   float dt, kp, kd, inertia, tau_max, action_scale, vel_alpha, tilt_beta, tilt_max, reward_scale, foot_clearance,
@@ -1146,6 +1146,59 @@ typedef struct catppo_servo_sim_history {
   catppo_servo_randomize rnd;             /* block never NULL */
   catppo_servo_history hist;
 } catppo_servo_sim_history;
+
+/* Pinned plants ("Robustness").  desc->reserved == CATPPO_SERVO_EXT_PLANT: `desc` is the head of a
+ * catppo_servo_sim_plant, i.e. the catppo_servo_sim_history above with a plant descriptor behind it.  The eight descriptors
+ * before it are checked and used exactly as under CATPPO_SERVO_EXT_HISTORY, except that an empty history descriptor (map NULL
+ * and floats 0) is an absent one and the observation descriptor may then be empty, too; a history that is present still needs
+ * its observations; act, actu and rnd are never absent.  Every older value of `reserved` keeps its meaning, and
+ * catppo_servo_randomize.reserved stays reserved and zero.  A plant table is an evaluation input: at least one of
+ * sim.fixed_command, sim.eval, sim.trace is set, and the launch is the step-response instance of its pack.
+ * plant.table is a DEVICE array [N, CATPPO_SERVO_PLANT_FLOATS = 8] of fp32 words, 16-byte aligned, row i for local env i (like
+ * fixed_command), read by every launch that is no init launch (a word the host rewrites in stream order is in the next launch).
+ *   word 0  pin bits (integer): CATPPO_SERVO_PLANT_KP | _KD | _FRICTION | _ARMATURE | _MASS | _LAG; the other bits zero
+ *   word 1  kp_scale            word 2  kd_scale
+ *   word 3  joint friction, N m (a Coulomb torque)          word 4  armature, kg m^2
+ *   word 5  mass_scale          word 6  lag in physics steps (integer)          word 7  zero
+ * Lane k < 8 of an env's 16 lanes loads word k (one 32-byte read per env, up front); the body reads word k through a 16-wide
+ * shuffle.  The spare lane groups past N read the row of the env they recompute, never a row >= N.
+ * The pins apply after the lag draw ("Actuators") and after the randomisation block's draws ("Randomisation"), to all twelve
+ * joints and all actuator groups, whatever the block's _ENABLE bit, quantity bits, masks and operations say.  fp32, unfused,
+ * one rounded operation each; t_k is word k of the env's row, block word k the randomisation block's:
+ *   _KP        kp' = entry.kp * t1
+ *   _KD        kd' = entry.kd * t2
+ *   _FRICTION  fr = t3
+ *   _ARMATURE  inertia' = block word 18 (servo_inertia) + t4
+ *   _FRICTION or _ARMATURE:  df = (fr / inertia') * dt, from the final fr and inertia'
+ *   _MASS      m = m0 * t5, weight = m * g, av = fminf(sim.vel_alpha / (m / m0), 1.f)   (m0, g: block words 16, 17)
+ *   _LAG       L = min(word 6, 255) for every joint (the substep's slot index is clamped as under "Actuators")
+ * A row with no bit set leaves its env exactly as the launch under CATPPO_SERVO_EXT_HISTORY (or _RANDOMIZE, without a
+ * history) computes it.  The row gets no new state.  The table's writer checks every row (Solo12ServoSim.set_fixed_plant);
+ * whatever the table holds the launch stays inside its rows: the values are floats and one clamped integer. */
+#define CATPPO_SERVO_EXT_PLANT 0x504C4E31          /* "PLN1": value of catppo_servo_sim.reserved that announces catppo_servo_sim_plant */
+#define CATPPO_SERVO_PLANT_FLOATS 8
+#define CATPPO_SERVO_PLANT_KP 0x1u
+#define CATPPO_SERVO_PLANT_KD 0x2u
+#define CATPPO_SERVO_PLANT_FRICTION 0x4u
+#define CATPPO_SERVO_PLANT_ARMATURE 0x8u
+#define CATPPO_SERVO_PLANT_MASS 0x10u
+#define CATPPO_SERVO_PLANT_LAG 0x20u
+typedef struct catppo_servo_plant {
+  const float* table;                     /* DEVICE array [N, 8], 16-byte aligned */
+  int32_t reserved[2];                    /* 0 */
+} catppo_servo_plant;
+typedef struct catppo_servo_sim_plant {
+  catppo_servo_sim sim;                   /* sim.reserved = CATPPO_SERVO_EXT_PLANT */
+  catppo_servo_obs obs;                   /* width 0 and table NULL: no observation table (only without a history) */
+  catppo_servo_events ev;                 /* block NULL and floats 0: no events */
+  catppo_servo_commands cmd;              /* block NULL and floats 0: no commands */
+  catppo_servo_terminations term;         /* table NULL and terms 0: no terminations */
+  catppo_servo_actions act;               /* table never NULL */
+  catppo_servo_actuators actu;            /* table never NULL */
+  catppo_servo_randomize rnd;             /* block never NULL */
+  catppo_servo_history hist;              /* map NULL and floats 0: no history */
+  catppo_servo_plant plant;
+} catppo_servo_sim_plant;
 
 /* ---- test hook (ABI 0.6) ------------------------------------------------------------------------------------------
  * buf != NULL ([2][M] int32, device): the head / loss kernel of every following catppo_ppo_minibatch_* call writes the clip

@@ -15,6 +15,12 @@ without it the simulator draws them.  ``--stochastic`` samples the actions inste
 step by step on the device.  With both, the ``[EVAL]`` line carries rise, settling, overshoot and steady-state error per
 command change (``"step_response"``), and ``<run>/eval/<checkpoint name>_trace.npz`` holds ``trace`` [steps, K, 72],
 ``fields``, ``commands`` and ``segment_steps``.
+
+``--eval_plant kp_scale=0.8:1.2:3 mass_scale=0.8:1.3:3 lag=0:8:3 ...`` (``name=value`` or ``name=lo:hi:n``; names ``kp_scale``
+``kd_scale`` ``friction`` ``armature`` ``mass_scale`` ``lag``) pins the plant of every env to a point of that grid inside the
+simulator's launch (``evaluate.plant_grid``), whatever the randomisation draws: the ``[EVAL]`` line then carries ``by_plant`` and
+``robustness``, and ``<run>/eval/<checkpoint name>_robustness.json`` holds the two blocks.  With ``--eval_grid`` the evaluation
+env has a whole multiple of (command points x plant points) envs, env i with command i % C and plant i // C (``evaluate.sweep``).
 """
 import argparse
 import os
@@ -58,6 +64,9 @@ def main(argv=None):
     parser.add_argument("--eval_schedule", type=float, nargs="+", default=None, metavar="V",
                         help="Command schedule VX VY WZ [VX VY WZ ...] that every env follows (instead of --eval_grid).")
     parser.add_argument("--eval_segment_steps", type=int, default=100, help="Control steps per segment of --eval_schedule.")
+    parser.add_argument("--eval_plant", type=str, nargs="+", default=None, metavar="NAME=LO:HI:N",
+                        help="Pinned plants: a grid over kp_scale, kd_scale, friction, armature, mass_scale, lag (name=value or "
+                             "name=lo:hi:n); combines with --eval_grid.")
     parser.add_argument("--trace_envs", type=int, default=0, help="Record the first K envs step by step (0: off).")
     parser.add_argument("--stochastic", action="store_true", default=False, help="Evaluate with sampled actions.")
     parser.add_argument("--obs_noise", choices=("on", "off"), default=None,
@@ -75,6 +84,13 @@ def main(argv=None):
             parser.error("--eval_schedule and --eval_grid are mutually exclusive")
         if len(args_cli.eval_schedule) % 3 != 0:
             parser.error("--eval_schedule takes a multiple of three values: VX VY WZ per segment")
+    plant_axes = None
+    if args_cli.eval_plant is not None:
+        from cat_envs.tasks.utils.cleanrl.evaluate import parse_plant_axes
+        try:
+            plant_axes = parse_plant_axes(args_cli.eval_plant)
+        except ValueError as e:
+            parser.error(str(e))
     import torch
 
     import cat_envs.tasks  # noqa: F401
@@ -147,18 +163,35 @@ def main(argv=None):
 
     if args_cli.eval_steps > 0:
         import numpy as np
-        from cat_envs.tasks.utils.cleanrl.evaluate import COMMAND_RANGES, command_grid, command_sequence, evaluate_policy
+        from cat_envs.tasks.utils.cleanrl.evaluate import (COMMAND_RANGES, command_grid, command_sequence, evaluate_policy,
+                                                           plant_grid, sweep)
+        plants, swept = None, None
+        if plant_axes is not None and args_cli.eval_grid is not None:
+            # N = C x P envs, as often as they fit into the env count asked for: env i gets command i % C and plant i // C
+            axes = [(lo, hi, n) for (lo, hi), n in zip(COMMAND_RANGES, args_cli.eval_grid)]
+            points = int(np.prod(args_cli.eval_grid))
+            product = points * int(np.prod([a[2] if isinstance(a, tuple) else 1 for a in plant_axes.values()]))
+            reps = max(1, int(env_cfg.scene.num_envs) // product)
+            cmd, table = sweep(command_grid(*axes, num_envs=points)[0],
+                               plant_grid(**plant_axes, num_envs=product // points))
+            swept = (np.tile(cmd, (reps, 1)), np.tile(table["packed"], (reps, 1)))
+            env_cfg.scene.num_envs = product * reps
+            print(f"[INFO] Evaluating {points} commands x {product // points} plants x {reps} on {product * reps} envs")
         eval_env = make(args_cli.task, cfg=env_cfg)               # a fresh env: the evaluator leaves it in the evaluated state
         commands, segment_steps = None, None
+        if swept is not None:
+            commands, plants = swept
+        elif plant_axes is not None:
+            plants = plant_grid(**plant_axes, num_envs=eval_env.unwrapped.num_envs)
         if args_cli.eval_schedule is not None:
             points = np.asarray(args_cli.eval_schedule, np.float32).reshape(-1, 3)
             commands, segment_steps = command_sequence(points, eval_env.unwrapped.num_envs), args_cli.eval_segment_steps
-        elif args_cli.eval_grid is not None:
+        elif args_cli.eval_grid is not None and swept is None:
             axes = [(lo, hi, n) for (lo, hi), n in zip(COMMAND_RANGES, args_cli.eval_grid)]
             commands = command_grid(*axes, num_envs=eval_env.unwrapped.num_envs)[0]
         result = evaluate_policy(eval_env, actor, args_cli.eval_steps, commands=commands,
                                  deterministic=not args_cli.stochastic, segment_steps=segment_steps,
-                                 trace_envs=args_cli.trace_envs)
+                                 trace_envs=args_cli.trace_envs, plant=plants)
         text = result.to_json()
         print(f"[EVAL] {text}")
         out_dir = os.path.join(os.path.dirname(resume_path), "eval")
@@ -167,6 +200,12 @@ def main(argv=None):
         with open(out_path, "w") as f:
             f.write(text + "\n")
         print(f"[INFO] Wrote evaluation to {out_path}")
+        if result.plant is not None:
+            import json
+            robust_path = os.path.splitext(out_path)[0] + "_robustness.json"
+            with open(robust_path, "w") as f:
+                f.write(json.dumps({"by_plant": result.by_plant(), "robustness": result.robustness()}) + "\n")
+            print(f"[INFO] Wrote robustness to {robust_path}")
         if result.trace is not None:
             trace_path = os.path.splitext(out_path)[0] + "_trace.npz"
             np.savez(trace_path, trace=result.trace, fields=np.array([name for name, _, _ in result.trace_fields]),

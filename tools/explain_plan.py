@@ -18,7 +18,8 @@ servo_sim_actuators.hip).
 The servo tasks are ``...-Solo12-Servo-v0`` and its ``-Rewards``, ``-Obs``, ``-Events``, ``-Full``, ``-Commands``, ``-Reference``,
 ``-Terminations``, ``-Reference-Terminations``, ``-Actions``, ``-Reference-Actions``, ``-Actuators``, ``-Reference-Actuators``,
 ``-DelayedActuators``, ``-Randomized`` (servo_sim_randomize.hip), ``-Reference-Randomized``, ``-History`` (servo_sim_history.hip) and
-``-Reference-History`` variants."""
+``-Reference-History`` variants.  ``--plant`` names the instance that an evaluation with a plant table launches instead
+(``evaluate_policy(plant=...)``; servo_sim_plant.hip, DESIGN section 9 "Robustness")."""
 import argparse
 import os
 import sys
@@ -66,8 +67,9 @@ def explain(obs, act, hidden, envs, mb, precision="fp32"):
     return "\n".join(out)
 
 
-def explain_task(task):
-    """the servo simulator's kernel instance of a task's training step, from its cfg alone"""
+def explain_task(task, plant=False):
+    """the servo simulator's kernel instance of a task's training step, from its cfg alone; ``plant``: of an evaluation with a
+    plant table as well"""
     import cat_envs.tasks  # noqa: F401
     from cat_envs.shim import load_cfg_from_registry
     cfg = load_cfg_from_registry(task, "env_cfg_entry_point")
@@ -105,6 +107,16 @@ def explain_task(task):
         T = history.history_floats
         out.append(f"observation history (servo_sim_history.hip): {T} floats behind the row (stride {row + (T + 3) // 4 * 4}), "
                    f"outside LDS; depths " + ", ".join(f"'{n}' {h} x {history.widths[n]}" for n, h in history.depths.items()))
+    if plant:
+        if robot is None and not rnd_terms and history is None:
+            out.append("pinned plants: not on this task - the row has no act_hist field (the task needs cfg.scene.robot, "
+                       "randomisation terms or an observation history)")
+        else:
+            pinned = pack + [n for n in ("catppo_servo_actions", "catppo_servo_actuators", "catppo_servo_randomize") if n not in pack]
+            pinned += ["catppo_servo_plant"]
+            out.append(f"pinned plants (servo_sim_plant.hip): an evaluation with a plant table launches servo_sim_kernel<kStepResponse, "
+                       f"{'true' if has['rewards'] else 'false'}{''.join(', ' + n for n in pinned)}> on the same row; the table is "
+                       f"[N, 8] fp32, 32 bytes per env beside a row of {row * 4} bytes")
     if has["commands"]:
         from cat_envs.tasks.utils.mdp import command_manager as KM
         b = KM.build_block(cfg.commands, cfg.sim.dt, cfg.episode_length_s)
@@ -169,9 +181,10 @@ if __name__ == "__main__":
     ap.add_argument("--precision", default="fp32", choices=("fp32", "bf16", "bf16x3"))
     ap.add_argument("--all", action="store_true")
     ap.add_argument("--task", default=None, help="name the servo simulator's kernel instance of this task (needs no device)")
+    ap.add_argument("--plant", action="store_true", help="with --task: name the instance of an evaluation with a plant table, too")
     a = ap.parse_args()
     if a.task:
-        print(explain_task(a.task))
+        print(explain_task(a.task, plant=a.plant))
     elif a.all:
         for name, *spec in BASELINE:
             print("#", name)

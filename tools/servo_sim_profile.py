@@ -51,6 +51,10 @@ instance of the full pack.  profiles/servo_randomize_kernel_stats.csv: the paren
 (observations, identity action and actuator tables, a switched-off randomisation block, the history descriptor).
 profiles/servo_history_kernel_stats.csv: the parent's library and this library without a flag and with --randomize, and this
 library with --obs, --history 3 and --history 5, alternating in one session, every run listed.
+--plant (with --trace and one of --randomize, --actuators, --history) attaches a plant table, too: a grid of 27 pinned plants
+(kp_scale 0.8 .. 1.2, mass_scale 0.8 .. 1.3, lag 0 .. 8 physics steps), so that the simulator's launch is the plant instance of the
+pack whose step-response instance the same arm without --plant launches.  profiles/servo_plant_kernel_stats.csv: the two arms
+alternating in one session, every run listed.
 
 Per env step the trace shows servo_sim_kernel (the simulator), the two launches of catppo_rollout_pre, the one of
 catppo_rollout_post and the policy forward."""
@@ -84,7 +88,11 @@ def main():
                     help="... and RandomizationEventCfg's three terms on top of the reference's robot (-Reference-Randomized)")
     ap.add_argument("--history", type=int, default=0,
                     help="the task with ObservationsCfg at group history_length H: the observation history inside the simulator launch")
+    ap.add_argument("--plant", action="store_true",
+                    help="with --trace on a task with a robot: pin every env's plant to a point of a 3 x 3 x 3 grid (the plant instance)")
     a = ap.parse_args()
+    if a.plant and not (a.trace and (a.randomize or a.actuators or a.history)):
+        ap.error("--plant goes with --trace and one of --randomize, --actuators, --history")
     if a.obs + a.rewards + a.events + a.commands + a.terminations + a.actions + a.reference_actions + (a.actuators is not None) + a.randomize + (a.history > 0) > 1:
         ap.error("--obs, --rewards, --events, --commands, --terminations, --actions, --reference-actions and --actuators are "
                  "separate arms")
@@ -130,6 +138,10 @@ def main():
         env_u.set_eval_record(record)
         env_u.set_fixed_commands(torch.from_numpy(command_sequence(points, a.num_envs)).to(env_u.device), 50)
         env_u.set_trace(trace)
+        if a.plant:
+            from cat_envs.tasks.utils.cleanrl.evaluate import plant_grid
+            plants = plant_grid(kp_scale=(0.8, 1.2, 3), mass_scale=(0.8, 1.3, 3), lag=(0, 8, 3), num_envs=a.num_envs)
+            env_u.set_fixed_plant(torch.from_numpy(plants["packed"]).to(env_u.device))
     elif a.eval:
         from cat_envs.tasks.utils.cleanrl.evaluate import COMMAND_RANGES, command_grid
         record = torch.zeros(a.num_envs, 12, device=env_u.device)
@@ -178,6 +190,11 @@ def main():
         h = sim.view("policy_obs_hist")
         print(f"history: {env_u.obs_dim} floats ({sim.P} per frame), row of {sim.row_floats} floats, stride {sim.F}, newest slot of "
               f"base_ang_vel differs from the one before in {float((h[:, 3 * a.history - 3] != h[:, 3 * a.history - 6]).float().mean()):.3f} of the envs")
+    if a.plant:
+        from cat_envs import native
+        assert env_u.sim._desc.reserved == native.SERVO_EXT_PLANT
+        print(f"pinned plants: {len({r.tobytes() for r in plants['packed']})} distinct rows of {native.SERVO_PLANT_FLOATS} floats, "
+              f"row of {env_u.sim.F} floats")
     if a.eval or a.trace:
         steps = record[:, 0].cpu()
         assert float(steps.min()) == float(steps.max()) == a.rollouts * trainer.T, (float(steps.min()), float(steps.max()))
