@@ -182,6 +182,11 @@ SERVO_EVENT_PUSH, SERVO_EVENT_JOINT_SCALE, SERVO_EVENT_JOINT_OFFSET, SERVO_EVENT
 SERVO_EVENT_WORDS = {"flags": 0, "p": 1, "num_buckets": 2, "push": 4, "joint_pos": 14, "joint_vel": 16, "root_pos": 18,
                      "root_vel": 22, "friction": 28}
 SERVO_TRACE_PUSHED = 14                 # float of a trace row: 1.f in a step whose env was pushed (events on)
+# the extended block (include/catppo.h, "Disturbances"): 64 words, words 0 .. 31 as above; the three bits count only there
+SERVO_EVENT_FLOATS_EXT = 64             # CATPPO_SERVO_EVENT_FLOATS_EXT: the second accepted value of ``ServoEvents.floats``
+SERVO_EVENT_PUSH_TIMED, SERVO_EVENT_WRENCH, SERVO_EVENT_WRENCH_RESET = 32, 64, 128
+#: word offsets of the extended block's new words; (lo, width) pairs, words 38 .. 63 are zero
+SERVO_EVENT_WORDS_EXT = {"T_lo": 32, "T_width": 33, "force": 34, "torque": 36}
 
 
 class ServoEvents(C.Structure):

@@ -183,3 +183,20 @@ for _name, _cfg in (("History", "Solo12ServoHistoryFlatEnvCfg"), ("Reference-His
         disable_env_checker=True,
         kwargs={"env_cfg_entry_point": f"{__name__}.cat_flat_env_cfg:{_cfg}_PLAY", **_KW},
     )
+
+# the servo task under IsaacLab's stock disturbances: a push on the env's own timer and a constant external wrench per episode,
+# both inside the simulator's launch ("Disturbances"); "Reference-Disturbances" is all six MDP blocks and the robot
+for _name, _cfg in (("Disturbances", "Solo12ServoDisturbancesFlatEnvCfg"),
+                    ("Reference-Disturbances", "Solo12ServoReferenceDisturbancesFlatEnvCfg")):
+    register(
+        id=f"Isaac-Velocity-CaT-Flat-Solo12-Servo-{_name}-v0",
+        entry_point=CaTEnv,
+        disable_env_checker=True,
+        kwargs={"env_cfg_entry_point": f"{__name__}.cat_flat_env_cfg:{_cfg}", **_KW},
+    )
+    register(
+        id=f"Isaac-Velocity-CaT-Flat-Solo12-Servo-{_name}-Play-v0",
+        entry_point=CaTEnv,
+        disable_env_checker=True,
+        kwargs={"env_cfg_entry_point": f"{__name__}.cat_flat_env_cfg:{_cfg}_PLAY", **_KW},
+    )

@@ -570,6 +570,46 @@ class Solo12ServoReferenceRandomizedFlatEnvCfg_PLAY(Solo12ServoReferenceActuator
 
 
 @configclass
+class DisturbanceEventCfg(EventCfg):
+    """the reference's event block with IsaacLab's stock disturbances ("Disturbances"): the push on a timer of
+    the env's own, and a constant external force on the base per episode"""
+    # IsaacLab's velocity task pushes every 10 .. 15 s; an episode here is 10 s long, so that timer would fire at most once per
+    # episode and in most episodes never: 2 .. 4 s gives two to four pushes per episode
+    push_robot = EventTerm(func=events.push_by_setting_velocity, mode="interval", interval_range_s=(2.0, 4.0),
+                           params={"velocity_range": {"x": (-0.5, 0.5), "y": (-0.5, 0.5)}})
+    # IsaacLab's stock term has both ranges (0, 0); up to an eighth of the robot's weight, in every direction
+    base_external_force_torque = EventTerm(func=events.apply_external_force_torque, mode="reset",
+                                           params={"asset_cfg": SceneEntityCfg("robot", body_names="base_link"),
+                                                   "force_range": (-3.0, 3.0), "torque_range": (-0.3, 0.3)})
+
+
+@configclass
+class Solo12ServoDisturbancesFlatEnvCfg(Solo12ServoFlatEnvCfg):
+    """the servo task under timed pushes and an external wrench: the simulator's launch evaluates both"""
+    events: DisturbanceEventCfg = DisturbanceEventCfg()
+
+
+@configclass
+class Solo12ServoDisturbancesFlatEnvCfg_PLAY(Solo12ServoDisturbancesFlatEnvCfg):
+    """reset and startup terms and the wrench stay; the env runs with pushes off"""
+    scene: SceneCfg = SceneCfg(num_envs=50, env_spacing=3.0)
+    curriculum: object = None
+    pushes: bool = False
+
+
+@configclass
+class Solo12ServoReferenceDisturbancesFlatEnvCfg(Solo12ServoReferenceActuatorsFlatEnvCfg):
+    """every MDP block of the reference's cfg and the reference's robot, under timed pushes and an external wrench"""
+    events: DisturbanceEventCfg = DisturbanceEventCfg()
+
+
+@configclass
+class Solo12ServoReferenceDisturbancesFlatEnvCfg_PLAY(Solo12ServoReferenceActuatorsFlatEnvCfg_PLAY):
+    """the wrench stays on, pushes off (inherited)"""
+    events: DisturbanceEventCfg = DisturbanceEventCfg()
+
+
+@configclass
 class HistoryObservationsCfg:
     """the reference's six terms, each with its last three processed frames, oldest first ("History"): 135 floats"""
 

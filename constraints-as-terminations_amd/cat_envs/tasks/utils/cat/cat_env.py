@@ -185,7 +185,8 @@ class Solo12ServoSim(SyntheticSolo12Sim):
     def __init__(self, num_envs: int, obs_dim: int, device, seed: int, syn, dt: float, decimation: int,
                  max_episode_length: int, episode_length: torch.Tensor, reset: torch.Tensor, env_offset: int = 0,
                  policy_obs_dim: int = 0, events: bool = False, commands: bool = False, terminations: bool = False,
-                 actions: bool = False, actuators: bool = False, randomize: bool = False, history_floats: int = 0):
+                 actions: bool = False, actuators: bool = False, randomize: bool = False, history_floats: int = 0,
+                 disturbances: bool = False, event_timer: bool | None = None):
         """``policy_obs_dim`` = P > 0: the row gets a second observation field ``policy_obs`` of P floats (padded to a
         multiple of 4) that ``set_observation_table`` configures; the raw field ``obs`` stays what it is.
         ``events``: the descriptor carries the event descriptor, too, and ``set_event_block`` configures it.
@@ -205,7 +206,15 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         floats (padded to a multiple of 4) behind ``row_floats``, the part of the row the kernel stages in LDS, so ``F``, the
         stride of the state buffers, exceeds ``row_floats``; the descriptor carries all eight descriptors and
         ``set_history_table`` configures the last (which float of the field shows which float of the current frame, and how
-        far the next slot is).  The row is that of ``randomize``"""
+        far the next slot is).  The row is that of ``randomize``.
+        ``disturbances`` (implies ``events``): the event block is the extended one of ``native.SERVO_EVENT_FLOATS_EXT`` words
+        (a timed push, an external wrench); ``event_timer`` (default: as ``disturbances``) gives the row one more 16-byte field
+        ``ev_state`` (float 0: the time left until the env's next timed push), which the timed push needs"""
+        self._disturbances = bool(disturbances)
+        self._event_timer = self._disturbances if event_timer is None else bool(event_timer)
+        if self._event_timer and not self._disturbances:
+            raise ValueError("the ev_state field goes with the extended event block (disturbances = True)")
+        events = bool(events or self._disturbances)
         self.T = int(history_floats)
         if self.T and not (int(policy_obs_dim) and 1 <= self.T <= native.SERVO_OBS_HISTORY_MAX_FLOATS):
             raise ValueError(f"an observation history needs a policy observation and 1 <= floats <= "
@@ -241,6 +250,9 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         if actuators:
             self.off["act_hist"] = (self.F, native.SERVO_ACT_HIST_FLOATS)
             self.F += native.SERVO_ACT_HIST_FLOATS
+        if self._event_timer:
+            self.off["ev_state"] = (self.F, 4)
+            self.F += 4
         self.row_floats = self.F                                        # what the kernel assembles in LDS
         if self.T:                                                      # behind it, written straight to memory
             self.off["policy_obs_hist"] = (self.F, self.T)
@@ -421,14 +433,30 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         if not self._events:
             raise ValueError("this simulator was built without an event descriptor (events = False)")
         words = np.ascontiguousarray(words, np.float32)
-        if words.shape != (native.SERVO_EVENT_FLOATS,):
-            raise ValueError(f"the event block has {native.SERVO_EVENT_FLOATS} words, got shape {words.shape}")
-        W = native.SERVO_EVENT_WORDS
+        floats = native.SERVO_EVENT_FLOATS_EXT if self._disturbances else native.SERVO_EVENT_FLOATS
+        if words.shape != (floats,):
+            raise ValueError(f"the event block has {floats} words, got shape {words.shape}")
+        W, WX = native.SERVO_EVENT_WORDS, native.SERVO_EVENT_WORDS_EXT
         ints = words.view(np.int32)
         flags, buckets = int(ints[W["flags"]]), int(ints[W["num_buckets"]])
         both = native.SERVO_EVENT_JOINT_SCALE | native.SERVO_EVENT_JOINT_OFFSET
         if flags & ~31 or flags & both == both:
-            raise ValueError(f"event block: flags {flags:#x} (known bits 1 .. 16; at most one joint-reset mode)")
+            timed, wrench, per_ep = native.SERVO_EVENT_PUSH_TIMED, native.SERVO_EVENT_WRENCH, native.SERVO_EVENT_WRENCH_RESET
+            if not self._disturbances or flags & ~(31 | timed | wrench | per_ep) or flags & both == both:
+                raise ValueError(f"event block: flags {flags:#x} (known bits 1 .. 16; at most one joint-reset mode)")
+            if flags & timed and flags & native.SERVO_EVENT_PUSH:
+                raise ValueError(f"event block: flags {flags:#x} name both pushes; at most one is evaluated")
+            if flags & timed and not self._event_timer:
+                raise ValueError("event block: the timed push needs the row's ev_state field (event_timer = True)")
+            if flags & per_ep and not flags & wrench:
+                raise ValueError(f"event block: flags {flags:#x}: the per-episode bit goes with the wrench bit")
+        if self._disturbances:
+            if (words[[WX["T_width"], WX["force"] + 1, WX["torque"] + 1]] < 0).any() or words[WX["torque"] + 2:].any():
+                raise ValueError("event block: every width of the extended words must be >= 0 and the spare words zero")
+            # the timer's range is read whenever the timed bit is set, by a later copy of the flag word, too
+            t_set = flags & native.SERVO_EVENT_PUSH_TIMED or words[[WX["T_lo"], WX["T_width"]]].any()
+            if t_set and not float(words[WX["T_lo"]]) > 0.0:
+                raise ValueError(f"event block: the timed push needs T_lo > 0, got {float(words[WX['T_lo']])}")
         if buckets < 1:
             raise ValueError(f"event block: num_buckets must be >= 1, got {buckets}")
         vals = np.delete(words, [W["flags"], W["num_buckets"]])
@@ -443,9 +471,10 @@ class Solo12ServoSim(SyntheticSolo12Sim):
         if int(self._desc.max_episode_length) >= 2 ** 27:
             raise ValueError("events need max_episode_length < 2^27: the step index is part of a Philox counter word")
         if self._event_block is None:
-            self._event_block = torch.zeros(native.SERVO_EVENT_FLOATS, dtype=torch.float32, device=self.device)
+            self._event_block = torch.zeros(floats, dtype=torch.float32, device=self.device)
             d = self._desc
-            d.ev.block, d.ev.floats, d.ev.reserved = self._event_block.data_ptr(), native.SERVO_EVENT_FLOATS, 0
+            d.ev.block, d.ev.floats = self._event_block.data_ptr(), floats
+            d.ev.reserved = self.off["ev_state"][0] if self._event_timer else 0      # off_ev_state
             self._announce()                                            # from now on every launch reads the block
         old = self._event_words
         if old is not None and (old.view(np.int32)[1:] == ints[1:]).all():
@@ -828,7 +857,7 @@ class Solo12ServoSim(SyntheticSolo12Sim):
 
     @property
     def event_words(self):
-        """the host copy of the event block as last written (fp32 [32]) or None"""
+        """the host copy of the event block as last written (fp32 [32], or [64] of an extended block) or None"""
         return None if self._event_words is None else self._event_words.copy()
 
     def reset(self):
@@ -1082,7 +1111,10 @@ class CaTEnv:
                                       history_floats=self.obs_dim if self._obs_field == "policy_obs_hist" else 0,
                                       events=self._event_pack, commands=self._command_block is not None,
                                       terminations=self._term_table is not None, actions=self._action_table is not None,
-                                      actuators=self._actuator_table is not None, randomize=self._randomization is not None)
+                                      actuators=self._actuator_table is not None, randomize=self._randomization is not None,
+                                      # the extended block and the timer field only when the cfg needs them
+                                      disturbances=self._event_block is not None and bool(self._event_block.get("flags_ext", 0)),
+                                      event_timer=self._event_block is not None and "interval_range" in self._event_block)
             self.scene = self.sim.scene
         self.obs_buf = {"policy": self.sim.view(self._obs_field)}
         self._rstep = None
@@ -1196,6 +1228,12 @@ class CaTEnv:
         if not hasattr(self, "event_manager"):
             raise TypeError("pushes need cfg.events")
         self.event_manager.set_interval_enabled(on)
+
+    def set_wrench(self, on: bool):
+        """the external wrench on or off from the next step on (needs apply_external_force_torque in cfg.events)"""
+        if not hasattr(self, "event_manager"):
+            raise TypeError("the wrench needs cfg.events with apply_external_force_torque")
+        self.event_manager.set_wrench_enabled(on)
 
     def set_randomization(self, on: bool):
         """the randomised robot on or off (off: the nominal robot) from the next step on (needs such terms in cfg.events)"""

@@ -429,7 +429,7 @@ class EvalResult:
 def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool = True,
                     fresh_cat_state: bool = False, segment_steps: int | None = None, trace_envs: int = 0,
                     corruption: bool | None = None, pushes: bool | None = None,
-                    randomization: bool | None = None, plant=None) -> EvalResult:
+                    randomization: bool | None = None, plant=None, wrench: bool | None = None) -> EvalResult:
     """Roll ``policy`` out for ``steps`` control steps from a fresh reset and measure it.
 
     ``policy`` is an ``Agent`` - its observations are normalised by the frozen ``obs_rms`` and the action is the mean
@@ -460,6 +460,9 @@ def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool 
 
     ``randomization`` (envs whose ``cfg.events`` randomises the robot): None leaves the switch as it is; a bool sets it for
     the evaluation (False: the nominal robot) and puts it back afterwards, likewise.
+
+    ``wrench`` (envs whose ``cfg.events`` has ``apply_external_force_torque``): None leaves the switch as it is; a bool sets it
+    for the evaluation (False: no external force or torque) and puts it back afterwards, likewise.
 
     ``plant`` (a ``plant_grid`` dict or a packing [N, 8]): env i's plant is what row i pins - gains, joint friction, armature,
     base mass, actuator lag - for the whole evaluation, inside the simulator's launch (``CaTEnv.set_fixed_plant``); the table
@@ -535,10 +538,14 @@ def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool 
     if randomization is not None and (em is None or em.randomization is None):
         u.set_eval_record(None)
         raise TypeError("evaluate_policy(randomization=...) needs an env whose cfg.events randomises the robot")
+    if wrench is not None and (em is None or "wrench" not in em.block):
+        u.set_eval_record(None)
+        raise TypeError("evaluate_policy(wrench=...) needs an env whose cfg.events has apply_external_force_torque")
+    wrench_before = None if em is None else em.wrench_enabled
     randomization_before = None if em is None else em.randomization_enabled
     pushes_before = None if em is None else em.interval_enabled
     pushes_on = bool(em is not None and (pushes_before if pushes is None else pushes)
-                     and em.block["flags"] & 1)        # the env has a push term and it is on for this evaluation
+                     and (em.block["flags"] & 1 or "interval_range" in em.block))   # a push term (per step or timed) is on
     frozen = contextlib.ExitStack()
     if fresh_cat_state:
         u.fresh_cat_state()
@@ -550,6 +557,8 @@ def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool 
             em.set_interval_enabled(pushes)
         if randomization is not None:
             em.set_randomization_enabled(randomization)
+        if wrench is not None:
+            em.set_wrench_enabled(wrench)
         if lead:
             u.set_fixed_commands(table, segment_steps)
         else:
@@ -588,6 +597,8 @@ def evaluate_policy(env, policy, steps: int, commands=None, deterministic: bool 
             em.set_interval_enabled(pushes_before)
         if randomization is not None:
             em.set_randomization_enabled(randomization_before)
+        if wrench is not None:
+            em.set_wrench_enabled(wrench_before)
     res = EvalResult(per_env=record.cpu().numpy(), commands=None if table is None else table.cpu().numpy(),
                      cat_reward=cat_reward.cpu().numpy(), termination_prob=term_prob.cpu().numpy(),
                      violations=viol.cpu().numpy(), term_names=names, trace=None if trace is None else trace.cpu().numpy(),

@@ -76,6 +76,39 @@ def push_by_setting_velocity_with_random_envs(env, env_ids, velocity_range, asse
     _refuse("push_by_setting_velocity_with_random_envs")
 
 
+def _describe_push_timed(name, sim_dt, max_episode_length_s, velocity_range=None, asset_cfg=None):
+    r = _axes(name, "velocity_range", velocity_range, ("x", "y", "yaw", "roll", "pitch"))
+    # the interval is the term's own (interval_range_s): the event manager reads it
+    return {"kind": "push_timed", "mode": "interval", "ranges": [r[k] for k in ("x", "y", "yaw", "roll", "pitch")], "inert": []}
+
+
+@_term(_describe_push_timed)
+def push_by_setting_velocity(env, env_ids, velocity_range, asset_cfg=None):
+    """whenever the env's own timer runs out (``interval_range_s`` of the term, ``is_global_time=False``), samples of
+    ``velocity_range`` are ADDED to its planar and yaw velocities (an absent key is (0, 0)), roll / pitch rates kick the tilt
+    ("Disturbances")"""
+    _refuse("push_by_setting_velocity")
+
+
+def _describe_wrench(name, sim_dt, max_episode_length_s, force_range=None, torque_range=None, asset_cfg=None):
+    import re
+    if force_range is None or torque_range is None:
+        raise ValueError(f"event term '{name}': force_range and torque_range are required")
+    bodies = _names(asset_cfg, "body_names")
+    if bodies is not None and not any(re.fullmatch(p, b) for p in bodies for b in ("base_link", "base")):
+        raise ValueError(f"event term '{name}': asset_cfg.body_names {bodies} must match 'base_link' or 'base', the surrogate "
+                         f"takes a wrench on its base only")
+    return {"kind": "wrench", "mode": None, "ranges": [_pair(name, "force_range", force_range),
+                                                        _pair(name, "torque_range", torque_range)], "inert": []}
+
+
+@_term(_describe_wrench)
+def apply_external_force_torque(env, env_ids, force_range, torque_range, asset_cfg=None):
+    """one force and one torque on the base, each component a sample of its range, constant for the episode (mode "reset") or
+    for the env's whole life (mode "startup") ("Disturbances")"""
+    _refuse("apply_external_force_torque")
+
+
 def _describe_joints(kind):
     def describe(name, sim_dt, max_episode_length_s, position_range=None, velocity_range=None, asset_cfg=None):
         if position_range is None or velocity_range is None:

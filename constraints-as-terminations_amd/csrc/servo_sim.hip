@@ -11,6 +11,7 @@
 // The kernel template is servo_sim_kernel.h, the host side of the launch servo_sim_host.h.  The instances compile in six
 // units, by the last descriptor of their pack: this one (none behind the terminations; it holds the entry point, too),
 // servo_sim_actions.hip, servo_sim_actuators.hip, servo_sim_randomize.hip, servo_sim_history.hip and servo_sim_plant.hip.
+// The instances on an extended event block compile in two more, servo_sim_disturb.hip and servo_sim_disturb_robot.hip.
 #include "servo_sim_kernel.h"
 
 // the descriptor's size is part of the ABI: cat_envs/native.py (ServoSimRewards) and tests/test_servo_reward_twin.py pin it
@@ -69,8 +70,12 @@ extern "C" int catppo_servo_sim_step(catppo_ctx* ctx, const catppo_servo_sim* de
   const int mode = (d.trace || d.fixed_segments > 1) ? kStepResponse : (d.fixed_command || d.eval) ? kEvaluate : kTrain;
   const bool rew = d.reward_terms > 0;
   const hipStream_t st = static_cast<hipStream_t>(stream);
-  // the unit that holds the instance: by the last descriptor of the pack
-  if (x.pl) catppo_internal_servo_sim_launch_plant(mode, rew, nblk, lds_bytes, st, d, x);
+  // the unit that holds the instance: of a pack with an extended event block ("Disturbances") one of two,
+  // else by the last descriptor of the pack
+  if (x.ev && x.ev->floats == CATPPO_SERVO_EVENT_FLOATS_EXT) {
+    if (x.rn) catppo_internal_servo_sim_launch_disturb_robot(mode, rew, nblk, lds_bytes, st, d, x);
+    else catppo_internal_servo_sim_launch_disturb(mode, rew, nblk, lds_bytes, st, d, x);
+  } else if (x.pl) catppo_internal_servo_sim_launch_plant(mode, rew, nblk, lds_bytes, st, d, x);
   else if (x.hs) catppo_internal_servo_sim_launch_history(mode, rew, nblk, lds_bytes, st, d, x);
   else if (x.rn) catppo_internal_servo_sim_launch_randomize(mode, rew, nblk, lds_bytes, st, d, x);
   else if (x.au) catppo_internal_servo_sim_launch_actuators(mode, rew, nblk, lds_bytes, st, d, x);

@@ -114,7 +114,9 @@ inline const char* servo_sim_check(const catppo_servo_sim& d, const ServoExts& x
     SERVO_REQUIRE(x.obs->table != nullptr && aligned16(x.obs->table));
   }
   if (x.ev) {
-    SERVO_REQUIRE(x.ev->floats == CATPPO_SERVO_EVENT_FLOATS && x.ev->reserved == 0);
+    SERVO_REQUIRE(x.ev->floats == CATPPO_SERVO_EVENT_FLOATS || x.ev->floats == CATPPO_SERVO_EVENT_FLOATS_EXT);
+    // reserved is off_ev_state: only an extended block keeps a timer in the row (the field itself: with the others below)
+    SERVO_REQUIRE(x.ev->reserved == 0 || x.ev->floats == CATPPO_SERVO_EVENT_FLOATS_EXT);
     SERVO_REQUIRE(x.ev->block != nullptr && aligned16(x.ev->block));
   }
   if (x.cm) {
@@ -168,7 +170,7 @@ inline const char* servo_sim_check(const catppo_servo_sim& d, const ServoExts& x
       {d.reward_rec, n * CATPPO_SERVO_REWARD_FLOATS * f32, "reward_rec"},
       {d.reward_table, sizeof(catppo_servo_reward_term) * CATPPO_SERVO_REWARD_MAX_TERMS, "reward_table"},
       {x.obs ? x.obs->table : nullptr, sizeof(catppo_servo_obs_entry) * (uintptr_t)(x.obs ? x.obs->width : 0), "obs.table"},
-      {x.ev ? x.ev->block : nullptr, f32 * CATPPO_SERVO_EVENT_FLOATS, "ev.block"},
+      {x.ev ? x.ev->block : nullptr, f32 * (uintptr_t)(x.ev ? x.ev->floats : 0), "ev.block"},
       {x.cm ? x.cm->block : nullptr, f32 * CATPPO_SERVO_COMMAND_FLOATS, "cmd.block"},
       {x.tm ? x.tm->table : nullptr, sizeof(catppo_servo_term_entry) * CATPPO_SERVO_TERM_MAX_TERMS, "term.table"},
       {x.tm ? x.tm->rec : nullptr, n * CATPPO_SERVO_TERM_FLOATS * f32, "term.rec"},
@@ -205,7 +207,8 @@ inline const char* servo_sim_check(const catppo_servo_sim& d, const ServoExts& x
       {x.obs != nullptr, false, {x.obs ? x.obs->off_policy_obs : 0, pad4(x.obs ? x.obs->width : 0)}},
       {x.cm != nullptr, true, {x.cm ? x.cm->off_cmd_state : 0, 4}},
       {x.tm != nullptr, true, {x.tm ? x.tm->off_term_state : 0, 4}},
-      {x.au != nullptr, true, {x.au ? x.au->off_act_hist : 0, CATPPO_SERVO_ACT_HIST_FLOATS}}};
+      {x.au != nullptr, true, {x.au ? x.au->off_act_hist : 0, CATPPO_SERVO_ACT_HIST_FLOATS}},
+      {x.ev != nullptr && x.ev->reserved != 0, true, {x.ev ? x.ev->reserved : 0, 4}}};
   const auto apart = [](const Field& a, const Field& b) { return a.off + a.width <= b.off || a.off >= b.off + b.width; };
   for (const auto& e : ext) {
     if (!e.present) continue;

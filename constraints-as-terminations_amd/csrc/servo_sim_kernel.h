@@ -19,6 +19,8 @@ constexpr uint32_t kTagCmdDraw = 0x434D4444u, kTagCmdTime = 0x434D4454u;
 constexpr uint32_t kTagActDelay = 0x41444C59u;                           // "ADLY": the actuator lag ("Actuators")
 // "AGAN", "JPAR", "MASS": the randomised gains, joint parameters and base mass ("Randomisation")
 constexpr uint32_t kTagGains = 0x4147414Eu, kTagJointPar = 0x4A504152u, kTagMass = 0x4D415353u;
+// "PSHT", "WRNC": the timer of the timed push and the external wrench ("Disturbances")
+constexpr uint32_t kTagPushTime = 0x50534854u, kTagWrench = 0x57524E43u;
 
 // G[k][lane]: the fixed 5 x 12 matrix of the base model (rows vx, vy, wz, roll, pitch)
 __device__ __forceinline__ float gain(int k, int lane) {
@@ -167,6 +169,49 @@ __device__ __forceinline__ float traction_of(const catppo_servo_sim& d, const Ev
   bucket = bucket > 0 ? bucket : 0;
   const float mu = E.fric[0] + rng::uniform_open(ev_block(d, (uint32_t)bucket, 0u, 1u, kTagFric).x) * E.fric[1];
   return mu < 1.f ? mu : 1.f;
+}
+
+// an event descriptor whose block is the extended one of CATPPO_SERVO_EVENT_FLOATS_EXT words (DESIGN section 9,
+// "Disturbances"): a type of its own in the kernel's pack, so that the timed push and the wrench are a template parameter of
+// the events path - the instances over catppo_servo_events itself compile without a line of them
+struct ServoEventsExt {
+  catppo_servo_events ev;
+};
+
+// what the wave keeps of words 32 .. 37 of an extended block (wave lane k < 64 has loaded word k), the three flag bits and the
+// row offset of ev_state (0: the block keeps no timer, and the timed bit is ignored); empty without one
+template <bool kOn>
+struct DisturbRegs {};
+template <>
+struct DisturbRegs<true> {
+  uint32_t flags = 0u;
+  float timer[2] = {0.f, 0.f}, force[2] = {0.f, 0.f}, torque[2] = {0.f, 0.f};      // (lo, width) pairs
+  int off_state = 0;
+};
+
+__device__ __forceinline__ DisturbRegs<true> disturb_of(float mine, int off_state) {
+  DisturbRegs<true> X;
+  X.flags = (uint32_t)__float_as_int(ev_word(mine, 0)) &
+            (CATPPO_SERVO_EVENT_PUSH_TIMED | CATPPO_SERVO_EVENT_WRENCH | CATPPO_SERVO_EVENT_WRENCH_RESET);
+  X.off_state = off_state;
+  if (off_state == 0) X.flags &= ~CATPPO_SERVO_EVENT_PUSH_TIMED;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) X.timer[i] = ev_word(mine, 32 + i), X.force[i] = ev_word(mine, 34 + i), X.torque[i] = ev_word(mine, 36 + i);
+  return X;
+}
+
+// the time until the next timed push, drawn at the start of (env, episode) (third = 0) and after the push of the step that
+// starts at episode length t (third = t + 1)
+__device__ __forceinline__ float push_time(const catppo_servo_sim& d, const DisturbRegs<true>& X, uint32_t gid, uint32_t ep,
+                                           uint32_t third) {
+  return X.timer[0] + rng::uniform_open(ev_block(d, gid, ep, third, kTagPushTime).x) * X.timer[1];
+}
+
+// the event descriptor of the pack, plain or extended
+template <bool kDist, typename... Ext>
+__device__ __forceinline__ const catppo_servo_events& events_desc(const Ext&... ext) {
+  if constexpr (kDist) return ext_of<ServoEventsExt>(ext...).ev;
+  else return ext_of<catppo_servo_events>(ext...);
 }
 
 // the command block as the wave holds it: wave lane k < 16 has loaded word k, every lane reads word k through readlane, so
@@ -469,11 +514,18 @@ __device__ __forceinline__ void pin_plant(const catppo_servo_sim& d, const Plant
 // section 9, "Robustness"): the quantities that the env's row of the plant table pins stand where the lag draw and randomize()
 // left theirs.  An evaluation input: launch() takes the step-response instance whatever the mode.  Orthogonal to the rest,
 // compiled out without it: 48 more instances (16 packs without a history, 8 with one), compiled in servo_sim_plant.hip.
+// ServoEventsExt in the place of catppo_servo_events ("Disturbances"): the event block has
+// CATPPO_SERVO_EVENT_FLOATS_EXT words and carries a timed push (the env's own timer, kept in the row field ev.reserved names) and
+// an external wrench on the base.  A template parameter of the events path: every instance over catppo_servo_events compiles
+// without a line of it; inside, the branches on the flag word are wave-uniform, and a block with neither bit set computes the
+// bytes of the 32-word launch.  168 more instances (every events-on pack, evaluation folded as above), compiled in
+// servo_sim_disturb.hip and servo_sim_disturb_robot.hip.
 template <int kMode, bool kRew, typename... Ext>
 __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeof...(Ext) == 0) ? 8 : 1) void servo_sim_kernel(
     const catppo_servo_sim d, const Ext... ext) {
   constexpr bool kObs = (std::is_same_v<Ext, catppo_servo_obs> || ...);
-  constexpr bool kEv = (std::is_same_v<Ext, catppo_servo_events> || ...);
+  constexpr bool kDist = (std::is_same_v<Ext, ServoEventsExt> || ...);
+  constexpr bool kEv = (std::is_same_v<Ext, catppo_servo_events> || ...) || kDist;
   constexpr bool kCmd = (std::is_same_v<Ext, catppo_servo_commands> || ...);
   constexpr bool kTerm = (std::is_same_v<Ext, catppo_servo_terminations> || ...);
   constexpr bool kAct = (std::is_same_v<Ext, catppo_servo_actions> || ...);
@@ -492,9 +544,11 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
   extern __shared__ float4 lds4[];
   float* lds = reinterpret_cast<float*>(lds4);
   const int tid = threadIdx.x, lane = tid & 15, grp = tid >> 4;
-  // wave lane k < 32 loads word k of the event block, long before the first use
+  // wave lane k < 32 loads word k of the event block (every lane of the wave its word of an extended one), long before the
+  // first use
   float ev_mine = 0.f;
-  if constexpr (kEv)
+  if constexpr (kDist) ev_mine = events_desc<true>(ext...).block[tid & 63];
+  else if constexpr (kEv)
     if ((tid & 63) < CATPPO_SERVO_EVENT_FLOATS) ev_mine = ext_of<catppo_servo_events>(ext...).block[tid & 63];
   // wave lane k < 16 loads word k of the command block
   float cmd_mine = 0.f;
@@ -574,6 +628,8 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
   }
   Events E = {};
   if constexpr (kEv) E = events_of(ev_mine);
+  DisturbRegs<kDist> DX;
+  if constexpr (kDist) DX = disturb_of(ev_mine, events_desc<true>(ext...).reserved);
   float* obs = row + d.off_obs;
   // (episode, episode length) of the state the observation describes: the key of its noise
   uint32_t obs_ep = 0u, obs_t = 0u;
@@ -665,6 +721,9 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
         if (6 + k < D) obs[6 + k] = cmd[k];
       }
       if constexpr (kCmd) row[ext_of<catppo_servo_commands>(ext...).off_cmd_state] = cmd_gen ? cmd_tl : 0.f;
+      // the timer of episode 0 (without the timed push the field stays the zeros the row was filled with)
+      if constexpr (kDist)
+        if (DX.flags & CATPPO_SERVO_EVENT_PUSH_TIMED) row[DX.off_state] = push_time(d, DX, gid, 0u, 0u);
     }
     if constexpr (kEval)
       if (rec) d.eval[rec_at] = 0.f;
@@ -751,11 +810,32 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
 #pragma unroll
       for (int k = 0; k < 5; ++k) red[k] = tree16(gain(k, lane) * dq);
     }
+    // the external wrench of (env, episode) - or of the env, once for all episodes: a force shifts the velocity the legs ask
+    // for by F / W m/s, a torque the yaw rate and the tilt by T / (W * stand_height), Fz lifts the load off the stance feet
+    float load = weight_of(d, RR);                       // what the stance feet share
+    if constexpr (kDist) {
+      if (DX.flags & CATPPO_SERVO_EVENT_WRENCH) {
+        const uint32_t we = (DX.flags & CATPPO_SERVO_EVENT_WRENCH_RESET) ? ep : 0u;
+        const rng::u32x4 a = ev_block(d, gid, we, 0u, kTagWrench), b = ev_block(d, gid, we, 1u, kTagWrench);
+        const float W = load, L = W * d.stand_height;
+        const float Fx = DX.force[0] + rng::uniform_open(a.x) * DX.force[1], Fy = DX.force[0] + rng::uniform_open(a.y) * DX.force[1];
+        const float Fz = DX.force[0] + rng::uniform_open(a.z) * DX.force[1];
+        const float Tx = DX.torque[0] + rng::uniform_open(b.x) * DX.torque[1], Ty = DX.torque[0] + rng::uniform_open(b.y) * DX.torque[1];
+        const float Tz = DX.torque[0] + rng::uniform_open(b.z) * DX.torque[1];
+        red[0] = red[0] + Fx / W;
+        red[1] = red[1] + Fy / W;
+        red[2] = red[2] + Tz / L;
+        red[3] = red[3] + Tx / L;
+        red[4] = red[4] + Ty / L;
+        load = fmaxf(W - Fz, 0.f);
+      }
+    }
     const float step_dt = d.dt * (float)d.decimation;
     // events: the root of a first state, and the push of this step on the state the step starts from (after the reset
     // select).  roll_k, pitch_k: the kicked tilt the lags start from; the rates keep differentiating against roll0, pitch0
     float first_xy[2] = {0.f, 0.f}, first_v[3] = {0.f, 0.f, 0.f}, push_v[3] = {0.f, 0.f, 0.f}, kick[2] = {0.f, 0.f};
     bool pushed = false;
+    float ev_tl = 0.f;                                   // timed push: the time left, as the output row keeps it
     if constexpr (kEv) {
       if (rst) first_root(d, E, gid, ep, first_xy, first_v);
       if (E.flags & CATPPO_SERVO_EVENT_PUSH) {
@@ -769,6 +849,33 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
           kick[0] = (E.push[6] + rng::uniform_open(r1.x) * E.push[7]) * step_dt;
           kick[1] = (E.push[8] + rng::uniform_open(r1.y) * E.push[9]) * step_dt;
         }
+      }
+    }
+    // the timed push: IsaacLab's interval rule on the env's own timer.  A reset step draws the timer and runs no update; a
+    // push ADDS its samples to the velocities (such a step is no reset step: xin is what it starts from).  With both push
+    // bits set the per-step push above wins and the timer keeps running
+    if constexpr (kDist) {
+      bool fire = false;
+      if (DX.flags & CATPPO_SERVO_EVENT_PUSH_TIMED) {
+        if (rst) {
+          ev_tl = push_time(d, DX, gid, ep, 0u);
+        } else {
+          ev_tl = in[DX.off_state] - step_dt;
+          fire = ev_tl < 1e-6f;
+          if (fire) ev_tl = push_time(d, DX, gid, ep, (uint32_t)t + 1u);
+        }
+      } else if (DX.off_state != 0) {
+        ev_tl = in[DX.off_state];                        // the bit cleared at run time: carried over
+      }
+      if (fire && !(E.flags & CATPPO_SERVO_EVENT_PUSH)) {
+        const rng::u32x4 r = ev_block(d, gid, ep, (uint32_t)t << 1, kTagPush);
+        const rng::u32x4 r1 = ev_block(d, gid, ep, ((uint32_t)t << 1) | 1u, kTagPush);
+        pushed = true;
+        push_v[0] = xin[0] + (E.push[0] + rng::uniform_open(r.y) * E.push[1]);
+        push_v[1] = xin[1] + (E.push[2] + rng::uniform_open(r.z) * E.push[3]);
+        push_v[2] = xin[2] + (E.push[4] + rng::uniform_open(r.w) * E.push[5]);
+        kick[0] = (E.push[6] + rng::uniform_open(r1.x) * E.push[7]) * step_dt;
+        kick[1] = (E.push[8] + rng::uniform_open(r1.y) * E.push[9]) * step_dt;
       }
     }
     float v[3];
@@ -802,7 +909,7 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
     const float air0 = rst ? 0.f : xin[5 + f];
     const float last_air0 = rst ? 0.f : in[d.off_last_air_time + foot_body];
     const bool touch = con > 0.f && !(con_prev > 0.f);
-    const float fz = con > 0.f ? weight_of(d, RR) / nsafe + (touch ? d.impact_gain * fabsf(knee_v) : 0.f) : 0.f;
+    const float fz = con > 0.f ? load / nsafe + (touch ? d.impact_gain * fabsf(knee_v) : 0.f) : 0.f;
     const float last_air = touch ? air0 : last_air0;
     const float air = con > 0.f ? 0.f : air0 + step_dt;
     const float fbase = z < d.min_height ? d.base_stiffness * (d.min_height - z) : 0.f;
@@ -985,6 +1092,8 @@ __global__ __launch_bounds__(kThreads, (kMode == kStepResponse && !kRew && sizeo
       row[d.off_reward] = kRew ? rsum : reward;
       row[d.off_hard_reset] = gone_of(TR, fallen) ? 1.f : 0.f;
       if constexpr (kCmd) row[ext_of<catppo_servo_commands>(ext...).off_cmd_state] = cmd_gen ? cmd_tl : 0.f;
+      if constexpr (kDist)
+        if (DX.off_state != 0) row[DX.off_state] = ev_tl;
     }
     if constexpr (kTerm) {
       const catppo_servo_terminations& tm = ext_of<catppo_servo_terminations>(ext...);
@@ -1139,7 +1248,7 @@ void launch(int mode, bool rew, unsigned nblk, size_t lds_bytes, hipStream_t str
   // (packs with an action table likewise)
   constexpr int kEvalAs = ((std::is_same_v<Ext, catppo_servo_terminations> || std::is_same_v<Ext, catppo_servo_actions> ||
                             std::is_same_v<Ext, catppo_servo_actuators> || std::is_same_v<Ext, catppo_servo_randomize> ||
-                            std::is_same_v<Ext, catppo_servo_history>) || ...)
+                            std::is_same_v<Ext, catppo_servo_history> || std::is_same_v<Ext, ServoEventsExt>) || ...)
                               ? kStepResponse : kEvaluate;
   // a plant table is an evaluation input (the entry point has checked that an evaluation pointer is set): its packs have the
   // step-response instances only
@@ -1168,3 +1277,9 @@ void catppo_internal_servo_sim_launch_history(int mode, bool rew, unsigned nblk,
                                               const catppo_servo_sim& d, const ServoExts& x);
 void catppo_internal_servo_sim_launch_plant(int mode, bool rew, unsigned nblk, size_t lds_bytes, hipStream_t stream,
                                             const catppo_servo_sim& d, const ServoExts& x);
+// ... and of every pack whose event block is the extended one (x.ev->floats == CATPPO_SERVO_EVENT_FLOATS_EXT): without a
+// randomisation descriptor, and with one
+void catppo_internal_servo_sim_launch_disturb(int mode, bool rew, unsigned nblk, size_t lds_bytes, hipStream_t stream,
+                                              const catppo_servo_sim& d, const ServoExts& x);
+void catppo_internal_servo_sim_launch_disturb_robot(int mode, bool rew, unsigned nblk, size_t lds_bytes, hipStream_t stream,
+                                                    const catppo_servo_sim& d, const ServoExts& x);

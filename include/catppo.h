@@ -813,18 +813,45 @@ typedef struct catppo_servo_sim_obs {
  * The first state (joint and root terms) serves the init launch, the start of a step whose reset flag is set and the
  * post-reset observation of a step that ends its episode (obs 9..20, 21..32 and wz at obs 2) alike.
  * With the push flag set, float 14 of a trace row is 1.f in a step whose env was pushed.  The block's writer checks its
- * values (Solo12ServoSim.set_event_block); whatever it holds the launch stays inside its row. */
+ * values (Solo12ServoSim.set_event_block); whatever it holds the launch stays inside its row.
+ *
+ * Disturbances ("Disturbances").  ev.floats may also be CATPPO_SERVO_EVENT_FLOATS_EXT: the block then has
+ * 64 words, words 0..31 exactly as above, and three more flag bits count (in a 32-word block they are ignored):
+ *   32 timed push    64 external wrench    128 the wrench is drawn per episode (clear: once per env, for all episodes)
+ *   32 33  T (lo, width) of the timed push's interval, in seconds     34 35 force (lo, width), in N
+ *   36 37  torque (lo, width), in N m                                 38..63 zero
+ * ev.reserved is then off_ev_state: 0, or the row offset of a 4-float state field `ev_state` (float 0: the time left until
+ * the env's next timed push, in seconds; floats 1..3 zero) under the rules of off_cmd_state: a multiple of 4, inside
+ * row_floats, disjoint from every base field and every other field.  With a 32-word block it must be 0; 1 is refused under
+ * either size.  The library cannot read the block: with the timed bit set while off_ev_state == 0 the kernel ignores the bit.
+ *   timed push   IsaacLab's push_by_setting_velocity under the interval rule with is_global_time = False.  tag "PSHT".  First
+ *                state of episode ep (init launch, or a step whose reset flag is set, which runs no update):
+ *                tl = T_lo + u * T_width from {gid, ep, 0, tag} word 0.  Any other step, starting at episode length t:
+ *                tl = tl - step_dt; fire = tl < 1e-6f; if fire, tl is redrawn from {gid, ep, t + 1, tag} word 0.  A fired step
+ *                takes the push's samples (tag "PUSH", third = (t << 1) | b, words and ranges as above; word 0 of block 0 is not
+ *                used) and ADDS them: v0[k] = xin[k] + s_k; tilt kick, ang and trace float 14 as for the push.  Every step
+ *                writes tl into ev_state of its output row; with the bit cleared the field is carried over unchanged.  With
+ *                both push bits set the per-step push wins and the timer keeps running.
+ *   wrench       IsaacLab's apply_external_force_torque on the base.  tag "WRNC", e = ep with bit 128, else 0:
+ *                {gid, e, 0, tag} words 0..2 sample F[0..2] from the force range, {gid, e, 1, tag} words 0..2 T[0..2] from the
+ *                torque range.  With W the load the stance feet share (d.weight, or the env's drawn or pinned one) and
+ *                L = W * d.stand_height, after the five reductions: red[0] += F[0] / W, red[1] += F[1] / W, red[2] += T[2] / L,
+ *                red[3] += T[0] / L, red[4] += T[1] / L, and the stance feet share fmaxf(W - F[2], 0.f).  Stateless. */
 #define CATPPO_SERVO_EXT_EVENTS 0x45565431   /* "EVT1": value of catppo_servo_sim.reserved that announces catppo_servo_sim_events */
 #define CATPPO_SERVO_EVENT_FLOATS 32
+#define CATPPO_SERVO_EVENT_FLOATS_EXT 64     /* the second accepted value of catppo_servo_events.floats */
 #define CATPPO_SERVO_EVENT_PUSH 1u
 #define CATPPO_SERVO_EVENT_JOINT_SCALE 2u
 #define CATPPO_SERVO_EVENT_JOINT_OFFSET 4u
 #define CATPPO_SERVO_EVENT_ROOT 8u
 #define CATPPO_SERVO_EVENT_FRICTION 16u
+#define CATPPO_SERVO_EVENT_PUSH_TIMED 32u    /* this bit and the two below: in a block of CATPPO_SERVO_EVENT_FLOATS_EXT words only */
+#define CATPPO_SERVO_EVENT_WRENCH 64u
+#define CATPPO_SERVO_EVENT_WRENCH_RESET 128u
 typedef struct catppo_servo_events {
-  const float* block;                     /* DEVICE array [CATPPO_SERVO_EVENT_FLOATS], 16-byte aligned */
-  int32_t floats;                         /* CATPPO_SERVO_EVENT_FLOATS */
-  int32_t reserved;                       /* 0 */
+  const float* block;                     /* DEVICE array [floats], 16-byte aligned */
+  int32_t floats;                         /* CATPPO_SERVO_EVENT_FLOATS or CATPPO_SERVO_EVENT_FLOATS_EXT */
+  int32_t reserved;                       /* off_ev_state: 0, or with CATPPO_SERVO_EVENT_FLOATS_EXT the row offset of ev_state */
 } catppo_servo_events;
 typedef struct catppo_servo_sim_events {
   catppo_servo_sim sim;                   /* sim.reserved = CATPPO_SERVO_EXT_EVENTS */

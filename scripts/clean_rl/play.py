@@ -75,6 +75,8 @@ def main(argv=None):
                         help="Interval events (pushes) of a task with cfg.events (default: what the task's cfg says).")
     parser.add_argument("--randomization", choices=("on", "off"), default=None,
                         help="Randomised robot of a task whose cfg.events randomises it (default: on; off: the nominal robot).")
+    parser.add_argument("--wrench", choices=("on", "off"), default=None,
+                        help="External force and torque of a task whose cfg.events has apply_external_force_torque (default: on).")
     parser.add_argument("--push_probability", type=float, default=None, metavar="P",
                         help="Push probability per env and control step of a task with a push term (default: the reference's).")
     cli_args.add_clean_rl_args(parser)
@@ -130,6 +132,11 @@ def main(argv=None):
         if em is None or em.randomization is None:
             parser.error("--randomization needs a task whose cfg.events randomises the robot")
         em.set_randomization_enabled(args_cli.randomization == "on")
+    if args_cli.wrench is not None:
+        em = getattr(env.unwrapped, "event_manager", None)
+        if em is None or "wrench" not in em.block:
+            parser.error("--wrench needs a task whose cfg.events has apply_external_force_torque")
+        em.set_wrench_enabled(args_cli.wrench == "on")
     actor = Agent(env, hidden=tuple(agent_cfg.hidden), mlp_precision=str(getattr(agent_cfg, "mlp_precision", "fp32")))
     actor.load_state_dict(torch.load(resume_path, map_location=actor.flat.device))
     actor.eval()

@@ -99,6 +99,15 @@ def explain_task(task, plant=False):
         pack += ["catppo_servo_history"]
     row = 308 + (48 if has["observations"] else 0) + (4 if has["commands"] else 0) + (4 if has["terminations"] else 0)
     row += 48 if robot is not None or rnd_terms or history is not None else 0
+    # a timed push or a wrench among the events: the same instance on the extended block; the timed push keeps its timer in the row
+    disturb = None
+    if event_terms:
+        from cat_envs.tasks.utils.mdp import event_manager as EM
+        block = EM.build_block(cfg.events, cfg.sim.dt, cfg.episode_length_s)
+        disturb = block if EM.extended(block) else None
+        row += 4 if disturb is not None and "interval_range" in disturb else 0
+        if disturb is not None:                  # the extended block reaches the kernel as a type of its own
+            pack = ["ServoEventsExt" if n == "catppo_servo_events" else n for n in pack]
     has["scene.robot"] = robot is not None
     out = [f"== {task}: " + ", ".join(f"cfg.{k} {'set' if v else 'unset'}" for k, v in has.items()),
            f"servo_sim_kernel<kTrain, {'true' if has['rewards'] else 'false'}{''.join(', ' + n for n in pack)}>: row of {row} floats "
@@ -107,6 +116,17 @@ def explain_task(task, plant=False):
         T = history.history_floats
         out.append(f"observation history (servo_sim_history.hip): {T} floats behind the row (stride {row + (T + 3) // 4 * 4}), "
                    f"outside LDS; depths " + ", ".join(f"'{n}' {h} x {history.widths[n]}" for n, h in history.depths.items()))
+    if disturb is not None:
+        kinds = [k for k in ("push_timed", "wrench") if k in disturb["kinds"].values()]
+        timer = disturb.get("interval_range")
+        unit = "servo_sim_disturb_robot.hip" if rnd_terms or history is not None else "servo_sim_disturb.hip"
+        out.append(f"disturbances ({', '.join(kinds)}; {unit}): an event block of 64 words; ServoEventsExt stands in the place of "
+                   f"catppo_servo_events, a template parameter of the events path"
+                   + (f"; the push fires every {timer[0]:g} .. {timer[0] + timer[1]:g} s on the env's own timer, 4 floats 'ev_state' "
+                      f"at the end of the row" if timer is not None else "")
+                   + (f"; wrench per {'episode' if disturb['wrench']['mode'] == 'reset' else 'env'}, force (lo, width) "
+                      f"{tuple(float(f'{v:g}') for v in disturb['wrench']['force'])} N, torque "
+                      f"{tuple(float(f'{v:g}') for v in disturb['wrench']['torque'])} N m" if "wrench" in disturb else ""))
     if plant:
         if robot is None and not rnd_terms and history is None:
             out.append("pinned plants: not on this task - the row has no act_hist field (the task needs cfg.scene.robot, "
@@ -114,7 +134,7 @@ def explain_task(task, plant=False):
         else:
             pinned = pack + [n for n in ("catppo_servo_actions", "catppo_servo_actuators", "catppo_servo_randomize") if n not in pack]
             pinned += ["catppo_servo_plant"]
-            out.append(f"pinned plants (servo_sim_plant.hip): an evaluation with a plant table launches servo_sim_kernel<kStepResponse, "
+            out.append(f"pinned plants ({'servo_sim_disturb_robot.hip' if disturb is not None else 'servo_sim_plant.hip'}): an evaluation with a plant table launches servo_sim_kernel<kStepResponse, "
                        f"{'true' if has['rewards'] else 'false'}{''.join(', ' + n for n in pinned)}> on the same row; the table is "
                        f"[N, 8] fp32, 32 bytes per env beside a row of {row * 4} bytes")
     if has["commands"]:

@@ -55,6 +55,12 @@ library with --obs, --history 3 and --history 5, alternating in one session, eve
 (kp_scale 0.8 .. 1.2, mass_scale 0.8 .. 1.3, lag 0 .. 8 physics steps), so that the simulator's launch is the plant instance of the
 pack whose step-response instance the same arm without --plant launches.  profiles/servo_plant_kernel_stats.csv: the two arms
 alternating in one session, every run listed.
+--disturbances runs the task with ``DisturbanceEventCfg`` (Isaac-Velocity-CaT-Flat-Solo12-Servo-Disturbances-v0: the reference's
+reset and startup terms, a push on the env's own timer and an external wrench per episode), so that the simulator's launch is the
+events-on training instance on an extended block, both new branches taken.  The arm draws the timer from 0.2 .. 0.4 s (the cfg:
+2 .. 4 s) so that every one of the 240 launches pushes some envs - about one in fifteen - and the fired branch is part of what
+is timed.  profiles/servo_disturb_kernel_stats.csv: the parent's library with --events, this library with --events and this
+library with --disturbances, alternating in one session, every run listed.
 
 Per env step the trace shows servo_sim_kernel (the simulator), the two launches of catppo_rollout_pre, the one of
 catppo_rollout_post and the policy forward."""
@@ -78,6 +84,8 @@ def main():
     ap.add_argument("--rewards", action="store_true", help="the task with ShapedRewardsCfg: reward terms inside the simulator launch")
     ap.add_argument("--obs", action="store_true", help="the task with ObservationsCfg: observation terms inside the simulator launch")
     ap.add_argument("--events", action="store_true", help="the task with EventCfg (push probability 0.01): events inside the simulator launch")
+    ap.add_argument("--disturbances", action="store_true",
+                    help="the task with DisturbanceEventCfg (timer 0.2 .. 0.4 s): timed pushes and a wrench inside the simulator launch")
     ap.add_argument("--commands", action="store_true", help="the task with CommandsCfg (p_move 0.01): the command term inside the simulator launch")
     ap.add_argument("--terminations", action="store_true", help="the task with TerminationsCfg: termination terms inside the simulator launch")
     ap.add_argument("--actions", action="store_true", help="the task with ActionsCfg: joint action terms inside the simulator launch")
@@ -93,8 +101,8 @@ def main():
     a = ap.parse_args()
     if a.plant and not (a.trace and (a.randomize or a.actuators or a.history)):
         ap.error("--plant goes with --trace and one of --randomize, --actuators, --history")
-    if a.obs + a.rewards + a.events + a.commands + a.terminations + a.actions + a.reference_actions + (a.actuators is not None) + a.randomize + (a.history > 0) > 1:
-        ap.error("--obs, --rewards, --events, --commands, --terminations, --actions, --reference-actions and --actuators are "
+    if a.obs + a.rewards + a.events + a.disturbances + a.commands + a.terminations + a.actions + a.reference_actions + (a.actuators is not None) + a.randomize + (a.history > 0) > 1:
+        ap.error("--obs, --rewards, --events, --disturbances, --commands, --terminations, --actions, --reference-actions and --actuators are "
                  "separate arms")
     import cat_envs.tasks  # noqa: F401
     from cat_envs.shim import load_cfg_from_registry, make
@@ -102,6 +110,7 @@ def main():
     task = ("Isaac-Velocity-CaT-Flat-Solo12-Servo-Rewards-v0" if a.rewards else
             "Isaac-Velocity-CaT-Flat-Solo12-Servo-Obs-v0" if a.obs else
             "Isaac-Velocity-CaT-Flat-Solo12-Servo-Events-v0" if a.events else
+            "Isaac-Velocity-CaT-Flat-Solo12-Servo-Disturbances-v0" if a.disturbances else
             "Isaac-Velocity-CaT-Flat-Solo12-Servo-Commands-v0" if a.commands else
             "Isaac-Velocity-CaT-Flat-Solo12-Servo-Terminations-v0" if a.terminations else
             "Isaac-Velocity-CaT-Flat-Solo12-Servo-Actions-v0" if a.actions else
@@ -119,6 +128,8 @@ def main():
     if a.events:
         push = env_cfg.events.push_robot
         push.params = {**push.params, "probability": 0.01}
+    if a.disturbances:
+        env_cfg.events.push_robot.interval_range_s = (0.2, 0.4)
     if a.commands:
         env_cfg.commands.base_velocity.p_move = 0.01
     if a.actuators == "delayed":
@@ -165,6 +176,10 @@ def main():
     if a.events:
         em = env_u.event_manager
         print(f"events: {em.active_terms}, push probability {em.block['p']:g}, |v| mean {float(env_u.sim.view('servo')[:, 0:3].abs().mean()):.4f}")
+    if a.disturbances:
+        em, sim = env_u.event_manager, env_u.sim
+        print(f"disturbances: {em.active_terms}, block of {len(sim.event_words)} words, row of {sim.F} floats, mean time left "
+              f"{float(sim.view('ev_state')[:, 0].mean()):.3f} s, |v| mean {float(sim.view('servo')[:, 0:3].abs().mean()):.4f}")
     if a.commands:
         km, sim = env_u.command_manager, env_u.sim
         zero = (sim.view("command") == 0).all(1).float().mean()
